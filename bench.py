@@ -14,11 +14,17 @@ including the 8-byte result read-back the reference blocks on (A3..A7 of SURVEY.
 Search paths (--path): `segment` = single-pass overlap-save in registers/LDS (no HBM intermediate; bound
 by the fp32 vector rate), `twopass` = length-N two-pass transforms through HBM (bound by HBM).  `auto`
 (default) takes the segment path for short filters -- every shipped protocol.  The JSON line carries the
-roofline of the path that ran the timed steps and, at N=1, a short measurement of the other one.
+roofline of the path that ran the timed steps (from the timed steps' own kernel timings).
+
+A plain run does what the headline needs and no more: set-up, warm-up, EXACTLY --steps timed steps (one repeat unless
+--repeats says otherwise), the outputs of the last timed step (--dump-outputs DIR), the line.  --full adds everything else
+the line has carried: five repeats of the timed loop, the S2 (white noise) loop, the other search path, the opt-in search
+forms, the demodulation and one-call figures, the sync correlator, the other banks and C3, C5, the receive chain, the N>1
+time-chunk-sharded leg, and the CPU baseline with its full-size parity gate.
 
 Launch for N>1 (driver):  python -m torch.distributed.run --nnodes=1 --nproc-per-node N
                           --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
-Prints ONE JSON line on rank 0.  Exits non-zero if the full-size parity spot check fails.
+Prints ONE JSON line on rank 0.  Exits non-zero if the carrier check or (--full) the full-size parity spot check fails.
 """
 import argparse
 import json
@@ -34,7 +40,8 @@ sys.path.insert(0, ROOT)
 HBM_PEAK = 8.0e12        # B/s, MI355X spec (MI355X_MICROARCH.md)
 VALU_FP32_PEAK = 157.3e12  # FLOP/s, MI355X fp32 vector peak (MI355X_MICROARCH.md)
 PARITY_TOL = 1e-5        # north_star: correlation magnitudes within 1e-5
-SETTLE_S = 0.05          # untimed work before the clock starts (profiles/r03_ramp.md: the clock settles within ~30 ms)
+SETTLE_S = 0.15          # untimed work before the clock starts (profiles/r03_ramp.md: the clock settles within ~30 ms; after 50 ms a
+                         # single 40-step C2 repeat still read ~0.6 % slower than the third of five, hence the margin)
 
 
 def b_alg(D, M, N):
@@ -699,11 +706,17 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=40)
     ap.add_argument('--warmup', type=int, default=25,
-                    help='untimed steps before the clock starts; whatever the value, untimed steps go on until 50 ms of work have '
+                    help='untimed steps before the clock starts; whatever the value, untimed steps go on until 150 ms of work have '
                          'passed: after an idle spell the device needs ~30 ms to settle its clock (tools/ramp_probe.py)')
-    ap.add_argument('--repeats', type=int, default=5,
-                    help='the --steps loop is timed this many times back to back; value / ms_per_step are the median repeat, '
-                         'config.ms_per_step_min / _max the extremes')
+    ap.add_argument('--full', action='store_true',
+                    help='the whole line: besides the headline, every secondary figure, the CPU baseline and the full-size parity '
+                         'gate (see the module docstring); off by default, when a run does only what the headline needs')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy: scores.npy '
+                         '(the Doppler score table, float32) and carrier.npy (the pick: fractional bin index and metric, float64)')
+    ap.add_argument('--repeats', type=int, default=None,
+                    help='the --steps loop is timed this many times back to back (default 1, with --full 5); value / ms_per_step are '
+                         'the median repeat, config.ms_per_step_min / _max the extremes')
     ap.add_argument('--log2n', type=int, default=20)
     ap.add_argument('--bins', type=int, default=256, help='Doppler bins per GPU')
     ap.add_argument('--protocol', default='bench_GMSK')
@@ -739,6 +752,10 @@ def main():
 
     if args.gpus < 1:
         ap.error('--gpus must be >= 1')
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.repeats < 1:
+        ap.error('--repeats must be >= 1')
     env_world = os.environ.get('WORLD_SIZE')
     if env_world is not None and int(env_world) != args.gpus and not (args.force_dist and args.gpus == 1 and int(env_world) == 1):
         sys.stderr.write(f'bench.py: --gpus {args.gpus} but the launcher started WORLD_SIZE={env_world} ranks; refusing to print a '
@@ -835,7 +852,7 @@ def main():
     # noise, examples/benchmark/create_signals.py:115-141): sixteen blocks resident in HBM as well, generated BEFORE the warm-up --
     # half a second of host work with an idle device in front of a timed loop would put that loop into the clock ramp
     s2_blocks = None
-    if G == 1 and not args.force_dist and not args.no_extras or args.signal == 'S2':
+    if args.full and G == 1 and not args.force_dist and not args.no_extras or args.signal == 'S2':
         s2_blocks = torch.from_numpy(sg.s2_noise(nblocks, N).view(np.float32).reshape(nblocks, 2 * N)).to(dev)
     if args.signal == 'S2':            # profiling runs: the whole line on S2
         blocks, host_blocks = s2_blocks, s2_blocks.cpu().numpy().view(np.complex64).reshape(nblocks, N)
@@ -882,7 +899,9 @@ def main():
         res = step(i)
     # ... and keep going, untimed, until at least SETTLE_S of work have passed since the initialisation, whatever --warmup says:
     # after an idle spell the device runs its first ~30 ms 8-20 % slow (profiles/r03_ramp.md), and a receiver on a
-    # continuous stream is never there.  Every rank runs the same number of steps (the sharded step is collective).
+    # continuous stream is never there.  Every rank runs the same number of steps (the sharded step is collective).  The extra
+    # steps come in whole cycles of the resident blocks, so which block each timed step reads -- and what the last one computed
+    # (--dump-outputs) -- follows from the arguments alone, not from how fast the warm-up ran.
     first = 1 + args.warmup
     while True:
         busy = torch.tensor([time.perf_counter() - t_w], dtype=torch.float64, device=dev)
@@ -890,7 +909,7 @@ def main():
             dist.all_reduce(busy, op=dist.ReduceOp.MIN)
         if float(busy.item()) >= SETTLE_S and first > 1:
             break
-        for _ in range(8):
+        for _ in range(nblocks):
             res = step(first)
             first += 1
     # the clock: EXACTLY --steps steps between barrier + synchronize on both sides, maximum over ranks -- taken args.repeats times
@@ -921,6 +940,13 @@ def main():
     # scores of the LAST timed block, read before anything else touches the handle (parity spot check)
     last_block = block_index(first - 1)
     gscores = bank.get_scores()[:, 0].astype(np.float64)
+    outputs = None
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: the pick and the score table it was made on (the
+        # sharded path picks on the table gathered over the ranks)
+        table = bank.get_scores() if shard is None else shard.scores.cpu().numpy()
+        outputs = {'scores': np.asarray(table, dtype=np.float32),
+                   'carrier': np.array([float(res[0]), float(res[1])], dtype=np.float64)}
 
     # ---- S2: the SAME loop on white noise (same settle rule, --steps, --repeats, sixteen blocks resident) --------------------
     s2 = None
@@ -954,7 +980,7 @@ def main():
     # ---- untimed secondary figures -----------------------------------------------------
     extras = {}
     other = None
-    if shard is None and not args.no_extras:
+    if args.full and shard is None and not args.no_extras:
         # find_carrier + demodulate (A3..A11 device part), host arithmetic as Demodulator.findCodeRateAndPhaseGPU
         k_off = int(N / (1.1 * 16))
         k_len = int(N / (0.9 * 16)) - k_off
@@ -1101,22 +1127,22 @@ def main():
                                                  and np.array_equal(hits[0][1], ref0[ref0 >= thr])),
             'includes': 'H2D of the packed streams from page-locked memory, kernels, D2H of the hits'}
 
-    if shard is None and G == 1 and not args.no_extras and not args.no_other_banks:
+    if args.full and shard is None and G == 1 and not args.no_extras and not args.no_other_banks:
         # the other BASELINE-named banks at the same geometry (C5's two filter sets at D = 256) and C3 (D = 1024)
         extras['other_banks'] = [bank_figure(dev, local_rank, p, args.bins, log2N, blocks, esz, nblocks, s2_blocks=s2_blocks, span=True)
                                  for p in ('CC11xx', 'bench_BPSK') if p != args.protocol]
         extras['c3'] = bank_figure(dev, local_rank, args.protocol, 1024, log2N, blocks, esz, nblocks, steps=4, warmup=1, twopass_steps=3)
 
     c5 = None
-    if shard is None and G == 1 and not args.no_extras and not args.no_c5 and rank == 0 and log2N == 20 and args.bins == 256:
+    if args.full and shard is None and G == 1 and not args.no_extras and not args.no_c5 and rank == 0 and log2N == 20 and args.bins == 256:
         c5 = c5_inprocess_figures(dev, local_rank, blocks, esz, nblocks)
         c5.update(c5_concurrent_figures())
     blocks_leg = None
-    if dist is not None and G > 1 and shard is not None and not args.no_blocks_leg:
+    if args.full and dist is not None and G > 1 and shard is not None and not args.no_blocks_leg:
         blocks_leg = run_blocks_leg(args, dist, rank, G, local_rank, dev)
     chain = None
-    if shard is None and G == 1 and not args.no_extras and not args.no_chain and rank == 0 and log2N == 20 and args.bins == 256:
-        chain = chain_figures(local_rank)           # (the default run only: C2's line carries the chain at the reference's own block sizes)
+    if args.full and shard is None and G == 1 and not args.no_extras and not args.no_chain and rank == 0 and log2N == 20 and args.bins == 256:
+        chain = chain_figures(local_rank)           # (C2's geometry only: its line carries the chain at the reference's own block sizes)
 
     # who took part: one entry per rank (process rank, device index, device uuid / name), gathered over the communicator
     props = torch.cuda.get_device_properties(dev)
@@ -1318,7 +1344,7 @@ def main():
         # the roofline object the same way: the contract's scalars first
         out['roofline'] = {**{k: roof[k] for k in ('bound', 'achieved', 'peak', 'unit', 'frac', 'traffic') if k in roof},
                            **{k: v for k, v in roof.items() if k not in ('bound', 'achieved', 'peak', 'unit', 'frac', 'traffic')}}
-        if not args.no_cpu_baseline and G == 1:
+        if args.full and not args.no_cpu_baseline and G == 1:
             # C2 on two whole blocks when ~26 s of CPU work allow -- the last timed block and its successor
             second = (last_block + 1) % nblocks
             cb, cscores_all, single = cpu_baseline(masks, shifts[lo:hi], [host_blocks[last_block], host_blocks[second]], N, ov, Dl)
@@ -1342,6 +1368,10 @@ def main():
             out['cpu_baseline'] = None
         if carrier_ok is False:
             rc = 1
+        if outputs is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, arr in outputs.items():
+                np.save(os.path.join(args.dump_outputs, name + '.npy'), arr)
         print(json.dumps(out), flush=True)
     bank.close()
     if dist is not None:

@@ -1,13 +1,21 @@
-"""load_config: the reference's config format (JSON with // comments, layered through "configBase").  When the reference
-tree is present (the authoring container; never the GPU box) its own bench and CC11xx configs are loaded and compared
-with the dictionaries our builders produce, on every key the demodulator reads."""
+"""load_config: the reference's config format (JSON with // comments, layered through "configBase").  The reference's own
+bench and CC11xx configs, as load_config read them (fixture tests/golden/ref_configs.json, recorded by
+tests/golden/make_golden_configs.py), are compared with the dictionaries our builders produce, on every key the
+demodulator reads."""
+import json
 import os
 
 import pytest
 
 from pycusdr_amd import config as cfg
 
-REF = '/root/reference/config'
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'ref_configs.json')
+
+
+@pytest.fixture(scope='module')
+def ref_configs():
+    with open(GOLDEN) as f:
+        return json.load(f)
 
 
 def test_comments_layers_and_overrides(tmp_path):
@@ -33,10 +41,9 @@ def test_comments_layers_and_overrides(tmp_path):
         cfg.load_config(sub / 'loop.json')
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference tree not present')
 @pytest.mark.parametrize('name', ['bench_GMSK', 'bench_FSK', 'bench_GFSK', 'bench_BPSK'])
-def test_reference_bench_configs_equal_our_builder(name):
-    ref = cfg.load_config(os.path.join(REF, 'benchmark', name + '.json'))
+def test_reference_bench_configs_equal_our_builder(ref_configs, name):
+    ref = ref_configs[name]
     ours = cfg.bench_config(name, blockSize=ref['GPU']['UHF']['blockSize'])
     assert ref['Main']['protocols']['UHF'] == name == ours['Main']['protocols']['UHF']
     for k in ('PacketLen', 'RandSeed'):
@@ -50,9 +57,8 @@ def test_reference_bench_configs_equal_our_builder(name):
             assert ref['GPU'][gpu_set][k] == v, (gpu_set, k)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference tree not present')
-def test_reference_cc11xx_config_equals_our_builder():
-    ref = cfg.load_config(os.path.join(REF, 'CC11xx.json'))
+def test_reference_cc11xx_config_equals_our_builder(ref_configs):
+    ref = ref_configs['CC11xx']
     ours = cfg.cc11xx_config(blockSize=ref['GPU']['UHF']['blockSize'])
     rx_name = next(iter(ours['Radios']['Rx']))
     r = ref['Radios']['Rx'][rx_name] if rx_name in ref['Radios']['Rx'] else next(iter(ref['Radios']['Rx'].values()))

@@ -1,9 +1,11 @@
-"""bench.py end to end on the GPU at a small geometry: one JSON line with the contract's keys, parity gate included."""
+"""bench.py end to end on the GPU at a small geometry: one JSON line with the contract's keys; with --full the secondary figures
+and the parity gate, without it a lean run that can write its outputs."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -12,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 @pytest.mark.parametrize('extra', [[], ['--path', 'twopass']])
 def test_bench_runs_and_prints_one_json_line(extra):
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '4', '--warmup', '2', '--log2n', '16', '--bins', '32'] + extra
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--steps', '4', '--warmup', '2', '--log2n', '16', '--bins', '32'] + extra
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -26,12 +28,40 @@ def test_bench_runs_and_prints_one_json_line(extra):
 
 
 @pytest.mark.gpu
+def test_plain_bench_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full: exactly --steps timed steps (one repeat), none of the secondary figures or the CPU baseline, and
+    --dump-outputs writes what the last timed step computed -- the same arrays on a second run with the same arguments."""
+    dumps = []
+    for run in ('a', 'b'):
+        out = tmp_path / run
+        cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '5', '--warmup', '2', '--log2n', '16',
+               '--bins', '32', '--dump-outputs', str(out)]
+        r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        c = d['config']
+        assert d['steps'] == 5 and c['repeats'] == 1 and d['ms_per_step'] > 0 and c['carrier_found'] is True
+        assert abs(d['value'] - (2 ** 16 - 2 ** 10) / (d['ms_per_step'] * 1e-3) / 1e6) / d['value'] < 1e-3
+        assert d['cpu_baseline'] is None and 'roofline_other_path' not in d
+        for k in ('s2', 'energy_search', 'span_basis_search', 'sync_correlator', 'other_banks', 'c3'):
+            assert k not in c, k
+        scores, carrier = np.load(out / 'scores.npy'), np.load(out / 'carrier.npy')
+        assert scores.dtype == np.float32 and scores.shape[0] == 32 and np.isfinite(scores).all() and scores[:, 0].max() > 0
+        assert carrier.dtype == np.float64 and carrier.shape == (2,) and 0 <= carrier[0] < 32
+        assert sorted(os.listdir(out)) == ['carrier.npy', 'scores.npy']
+        dumps.append((scores, carrier))
+    assert np.array_equal(dumps[0][0], dumps[1][0]) and np.array_equal(dumps[0][1], dumps[1][1])
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize('mode', [[], ['--single-comm'], ['--single-comm', '--no-prefetch']])
 def test_bench_sharded_path_on_one_rank(mode):
     """`bench.py --gpus 1 --force-dist`: the whole sharded step (block hand-over, search, RCCL exchange on a one-rank
     communicator, pick on the gathered table) in both broadcast modes; the line names the communicator's size and the
     device behind every rank."""
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--force-dist', '--steps', '4', '--warmup', '2',
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--force-dist', '--full', '--steps', '4', '--warmup', '2',
            '--log2n', '16', '--bins', '32', '--repeats', '2', '--watchdog', '60'] + mode
     env = dict(os.environ)
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT', 'MASTER_ADDR'):
@@ -108,8 +138,8 @@ def test_bench_two_ranks_fall_back_to_the_conservative_mode(launcher):
 def test_bench_two_ranks_report_both_sharding_axes():
     """An undisturbed two-rank job (gloo on one GPU): the default mode produces the line, and the same job carries the
     time-chunk-sharded leg (SURVEY 8e's other axis) as flat keys among the first twenty."""
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--steps', '3', '--warmup', '1', '--log2n', '16',
-           '--bins', '32', '--repeats', '2', '--watchdog', '60', '--no-cpu-baseline']
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--full', '--steps', '3', '--warmup', '1',
+           '--log2n', '16', '--bins', '32', '--repeats', '2', '--watchdog', '60', '--no-cpu-baseline']
     env = dict(os.environ)
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT', 'MASTER_ADDR', 'BENCH_WORKER', 'BENCH_FAIL_FIRST_ATTEMPT'):
         env.pop(k, None)

@@ -1,5 +1,6 @@
 """Write profiles/<round>_pmc_summary.md, the kernel-stats CSVs and the segment entries of profiles/pmc_traffic.json from the three
-tools/prof_bench.sh runs of a round (tags <t>, <t>_cc, <t>_bpsk under gpurun_out/) and the bench line gpurun_out/<t>_bench.json.
+tools/prof_bench.sh runs of a round (tags <t>, <t>_cc, <t>_bpsk in prof_bench.sh's output folder) and the bench line
+tools/round_profiles.sh wrote ($TOOLS_OUT/<t>_bench.json, default tools_out/).
 usage: python tools/pmc_summary.py r4 r04"""
 import collections
 import csv
@@ -21,8 +22,9 @@ def newest(pattern):
     return sorted(best.values())
 
 tag, rnd = sys.argv[1], sys.argv[2]
-line = json.loads(open(f'gpurun_out/{tag}_bench.json').read().strip().splitlines()[-1])
-shutil.copy(f'gpurun_out/{tag}_bench.json', f'profiles/{rnd}_bench.json')
+bench_line = os.path.join(os.environ.get('TOOLS_OUT', 'tools_out'), f'{tag}_bench.json')
+line = json.loads(open(bench_line).read().strip().splitlines()[-1])
+shutil.copy(bench_line, f'profiles/{rnd}_bench.json')
 banks = {b['protocol']: b for b in line['config']['other_banks']}
 cols = [('', 'C2: GMSK, 48 taps, M = 8', line['roofline'], line['value'], 'kernel_stats'),
         ('_cc', 'CC11xx FSK-2, 384 taps, M = 8', banks['CC11xx']['roofline'], banks['CC11xx']['msamples'], 'cc11xx_kernel_stats'),

@@ -1,10 +1,13 @@
 #!/bin/bash
 # The round's evidence in one call on ONE GPU box: the un-profiled bench line, then the kernel-trace and PMC passes of its three
 # banks and of the two-pass path, then the batched receive chain's kernel trace.  usage: tools/round_profiles.sh r5
-# (afterwards, here: python tools/pmc_summary.py r5 r05)
+# (afterwards, here: python tools/pmc_summary.py r5 r05).  The bench line (--full: every figure of the line) goes to $TOOLS_OUT
+# (default tools_out/), where pmc_summary.py reads it.
 tag=${1:-r5}
+out=${TOOLS_OUT:-tools_out}
 mkdir -p gpurun_out
-python bench.py > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err || { echo "bench failed"; tail -5 gpurun_out/${tag}_bench.err; exit 1; }
+mkdir -p "$out"
+python bench.py --full > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.err" || { echo "bench failed"; tail -5 "$out/${tag}_bench.err"; exit 1; }
 echo "bench done"
 tools/prof_bench.sh $tag > gpurun_out/${tag}_report.txt 2>&1 && echo "prof C2 done"
 tools/prof_bench.sh ${tag}_cc --protocol CC11xx > gpurun_out/${tag}_cc_report.txt 2>&1 && echo "prof CC11xx done"
