@@ -336,10 +336,10 @@ int mfb_receive_blocks_end(mfb_ctx *ctx, int slot, mfb_block_result *results, in
  * from batch to batch; mfb_stream_seed sets it from the host's (start of a stream, after an irregular block, after blocks
  * that went another way).  Batches of more than 64 blocks run without the stages (their records carry layout.stream_stages = 0: the
  * host does A12 ... A14 for them): one workgroup chains the kept-bit counts of a batch's blocks through one wave, 64 lanes.  So do
- * batches at a FIXED shift (MFB_BLOCK_FIXED_SHIFT, the S-band back end demodulator/STX.py:8-24): that back end clips interference
- * peaks out of every block on the host before the block is transformed and tags the symbols next to them in the trust bytes
- * afterwards (DB:670-707, 830-837) -- from sample indices only the host holds, block by block, so the bits of such a block are
- * finished on the host anyway.  p == NULL switches the stages off. */
+ * batches at a FIXED shift (MFB_BLOCK_FIXED_SHIFT, the S-band back end demodulator/STX.py:8-24): that back end tags the symbols
+ * next to clipped interference peaks in the trust bytes (DB:670-707, 830-837) from the block's clipped-sample indices -- on the
+ * host, also when the device clips the block (mfb_set_peak_clip hands the indices out) -- so the bits of such a block are
+ * finished on the host.  p == NULL switches the stages off. */
 typedef struct mfb_stream_params {
     int32_t overlap_samples;     /* 2^overlap (config GPU.overlap) */
     int32_t overlap_offset;      /* symbol_check_overlap_offset (DB:19-26): 20 */
@@ -393,6 +393,32 @@ int mfb_debug_stream_stages(mfb_ctx *ctx, int nb, int symbols, const int32_t *co
  * of the spectrum windows.  No effect on the handle's state. */
 int mfb_debug_block_scalars(mfb_ctx *ctx, int n, const float *picks, const float *triples, int spsym_min, int snr_window,
                             int max_symbols, mfb_block_result *results, float *launch_args, int32_t *band_pieces);
+
+/* Interference-peak clipping on the device, in front of the forward transform of mfb_receive_block(_begin) and
+ * mfb_receive_blocks_begin -- the reference's __thresholdInput (DB:670-707), which the S-band back end runs on every block on the
+ * host.  Twice: |x| of every sample, t = (float)scale * mean|x|, every sample above t scaled to magnitude t; |x| of the clipped
+ * samples again, a second threshold, a second clip.  The clipped samples and the ascending indices of the second round
+ * (clippedPeakIPure) equal numpy's on the host bit for bit -- its |x| (max * sqrt(fma(r, r, 1)), r = min / max), its pairwise
+ * float32 mean over 8192-element chunks, its complex arithmetic -- for blocks of N = 2^k >= 4096 samples (smaller handles:
+ * MFB_ERR_UNSUPPORTED).  The clipped block goes to a buffer of the flight (the caller's samples and windows stay as they are),
+ * which the transforms and the matched filters then read.
+ *   scale      0 switches clipping off (the default), > 0 is the reference's peakThresholdScale.
+ *   overlap    > 0: chain consecutive blocks as the reference's loop does (it carries the overlap AFTER clipping,
+ *              DP:293,337): a block's first `overlap` samples are replaced by the previous block's clipped last `overlap`
+ *              samples -- inside a batch and from call to call; 0: every block is clipped as given.
+ * Every call restarts the chain; MFB_INPUT_UPLOADED with clipping on returns MFB_ERR_UNSUPPORTED.  Nothing may be in flight. */
+int mfb_set_peak_clip(mfb_ctx *ctx, float scale, int overlap);
+/* The next block's overlap is taken as given (the previous block did not go through the device clip; DB:670-707). */
+int mfb_restart_peak_clip(mfb_ctx *ctx);
+/* The chain's tail (DB:670-707): the last device-clipped block's clipped last `overlap` samples (count must equal the overlap of
+ * mfb_set_peak_clip), *valid = 0 when there is none (clipping off, no overlap, chain restarted).  For a caller that goes on with
+ * the host's clip after device-clipped blocks: the reference carries the overlap after clipping (DP:293,337).  Synchronises;
+ * nothing may be in flight. */
+int mfb_get_peak_clip_tail(mfb_ctx *ctx, float *host_c64, int count, int32_t *valid);
+/* clippedPeakIPure (DB:670-707) of block `block` (0 for mfb_receive_block_*) of the flight collected last from `slot`: *count =
+ * the number of indices, the first min(count, cap) of them (ascending) into idx.  Valid until `slot` is begun again (each slot keeps its own buffers).
+ * MFB_ERR_STATE if that flight is not collected or was not clipped. */
+int mfb_get_block_clips(mfb_ctx *ctx, int slot, int block, int32_t *idx, int cap, int32_t *count);
 
 /* Symbol centres on the matched-filter outputs left by mfb_demodulate.  Replaces findCentres
  * (CU:78-146) + the three memcpy_dtoh of cudaFindCentres (DB:996-1006).  Writes `count` =

@@ -102,6 +102,10 @@ PROTOTYPES = {
     'mfb_window_buffer': (_i, [_vp, _i, _i, _i, C.POINTER(_fp)]),
     'mfb_receive_blocks_begin': (_i, [_vp, C.POINTER(BlockParams), _i, _i]),
     'mfb_set_batch_overlap': (_i, [_vp, _i]),
+    'mfb_set_peak_clip': (_i, [_vp, C.c_float, _i]),
+    'mfb_restart_peak_clip': (_i, [_vp]),
+    'mfb_get_peak_clip_tail': (_i, [_vp, _vp, _i, _ip]),
+    'mfb_get_block_clips': (_i, [_vp, _i, _i, _vp, _i, _ip]),
     'mfb_get_batch_scores': (_i, [_vp, _i, _vp]),
     'mfb_get_search_info': (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     'mfb_set_cu_share': (_i, [_vp, _i, _i]),

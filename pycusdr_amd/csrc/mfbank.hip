@@ -53,6 +53,7 @@
 #include "sync_kernels.hpp"
 #include "energy_kernels.hpp"
 #include "stream_kernels.hpp"
+#include "clip_kernels.hpp"
 #include "hostcopy.hpp"
 
 // ------------------------------------------------------------------------------------------------
@@ -66,6 +67,7 @@ struct BlockFlight {      // one block -- or one batch of nb blocks -- between m
     size_t ext;           // offset of the stream-stage outputs inside a record (0: none)
     size_t off[5];
     unsigned long long seq;
+    bool clip;            // the block(s) went through the peak clip (mfb_get_block_clips)
 };
 
 constexpr int WG_NB = 32;
@@ -196,6 +198,19 @@ struct mfb_ctx {
     int gs_span = -1;                    // ... and for which basis
     int gs_l = 0;                        // ... and segment length (log2)
     int fsm_fb = 0, fsm_fs = 0;          // rectangle of a wave: bins x slots (0: default)
+    // interference-peak clipping before the forward transform (clip_kernels.hpp, mfb_set_peak_clip; DB:670-707)
+    float clip_scale = 0.f;              // 0: off
+    int clip_ov = 0;                     // > 0: block b's first clip_ov samples are block b - 1's clipped tail
+    bool clip_restart = false;           // the next block's overlap is taken as given
+    int clip_cap[2] = {};                // blocks the flight buffers below hold, per slot
+    int clip_ws_cap = 0;                 // ... and the shared workspace
+    cf *d_clipx[2] = {};                 // [flight slot]: clipped blocks [clip_cap][N] -- what the transforms and part 2 read
+    int *d_clipi[2] = {}, *d_cliph[2] = {};   // ... their indices [clip_cap][N] and heads [clip_cap][CLIP_HEAD]
+    int32_t *h_cliph[2] = {};            // page-locked copies of the heads (read back with the flight)
+    float *d_clips = nullptr;            // leaf sums of the two rounds [2][clip_ws_cap][N / 128] and thresholds [clip_ws_cap][2]
+    int *d_clipw = nullptr;              // per-wave counts and tail flags [2][clip_ws_cap][N / 1024]
+    ClipTail *d_ctail = nullptr;         // the last clipped block's tail (stable address: captured graphs hold it)
+    int ctail_cap = 0;
 };
 
 #define HIPCHK(x)                                                                            \
@@ -669,6 +684,15 @@ extern "C" int mfb_destroy(mfb_ctx *c) {
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->d_Gs) (void)hipFree(c->d_Gs);
     if (c->d_Qs) (void)hipFree(c->d_Qs);
+    for (int i = 0; i < 2; ++i) {
+        if (c->d_clipx[i]) (void)hipFree(c->d_clipx[i]);
+        if (c->d_clipi[i]) (void)hipFree(c->d_clipi[i]);
+        if (c->d_cliph[i]) (void)hipFree(c->d_cliph[i]);
+        if (c->h_cliph[i]) (void)hipHostFree(c->h_cliph[i]);
+    }
+    if (c->d_clips) (void)hipFree(c->d_clips);
+    if (c->d_clipw) (void)hipFree(c->d_clipw);
+    if (c->d_ctail) (void)hipFree(c->d_ctail);
     delete c->bank;
     delete c;
     return MFB_OK;
@@ -1897,9 +1921,10 @@ struct BlkBufs {
     size_t rec;
     size_t ext;          // offset of the stream-stage outputs inside a record (0: the stages run on the host)
     int parity;          // carry buffer the stream stages read
+    const struct ClipLaunch *clip;   // peak clip in front of the forward transform (nullptr: none); x is then its output
 };
 static BlkBufs single_bufs(mfb_ctx *c) {
-    return BlkBufs{1, c->d_in, 0, c->d_X, c->d_sum, c->d_res, c->d_xc, c->d_env, c->d_P, c->d_cr, c->d_blkout, 0, 0, 0};
+    return BlkBufs{1, c->d_in, 0, c->d_X, c->d_sum, c->d_res, c->d_xc, c->d_env, c->d_P, c->d_cr, c->d_blkout, 0, 0, 0, nullptr};
 }
 
 // A9 + A10 enqueued on the handle's stream: matched filters at one shift per block (a value, or -- shift_dev != nullptr -- an
@@ -2034,6 +2059,150 @@ static RecPtrs rec_ptrs(const BlkBufs &bb, int nthreads, int bcap) {
     r.mag = (float *)((uint8_t *)r.cen + align16((size_t)nthreads * sizeof(int)));
     return r;
 }
+// ---- interference-peak clipping (clip_kernels.hpp; reference __thresholdInput, DB:670-707) -----------------------------------
+struct ClipLaunch {
+    ClipArgs a;
+    int32_t *h_head;     // page-locked copy of the heads, read back with the flight
+};
+// buffers of the clip: the flight's own (clipped blocks, indices, heads: slot `slot`, up to nb blocks -- the other slot's flight,
+// pending or collected, keeps its own), the shared workspace of part 1 and the chain tail (stable addresses: captured graphs
+// hold them)
+static int clip_reserve(mfb_ctx *c, int slot, int nb) {
+    if (nb > c->clip_cap[slot]) {
+        HIPCHK(sync_streams(c));
+        ++c->epoch;
+        if (c->d_clipx[slot]) HIPCHK(hipFree(c->d_clipx[slot]));
+        if (c->d_clipi[slot]) HIPCHK(hipFree(c->d_clipi[slot]));
+        if (c->d_cliph[slot]) HIPCHK(hipFree(c->d_cliph[slot]));
+        if (c->h_cliph[slot]) HIPCHK(hipHostFree(c->h_cliph[slot]));
+        c->d_clipx[slot] = nullptr;
+        c->d_clipi[slot] = c->d_cliph[slot] = nullptr;
+        c->h_cliph[slot] = nullptr;
+        c->clip_cap[slot] = 0;
+        const size_t nbN = (size_t)nb * c->N;
+        HIPCHK(dev_alloc((void **)&c->d_clipx[slot], nbN * sizeof(cf)));
+        HIPCHK(dev_alloc((void **)&c->d_clipi[slot], nbN * sizeof(int)));
+        HIPCHK(dev_alloc((void **)&c->d_cliph[slot], (size_t)nb * CLIP_HEAD * sizeof(int)));
+        HIPCHK(hipHostMalloc((void **)&c->h_cliph[slot], (size_t)nb * CLIP_HEAD * sizeof(int), hipHostMallocDefault));
+        memset(c->h_cliph[slot], 0, (size_t)nb * CLIP_HEAD * sizeof(int));
+        c->clip_cap[slot] = nb;
+    }
+    if (nb > c->clip_ws_cap) {       // part 1 only, on the handle's stream: nothing in flight reads it after the wait
+        HIPCHK(sync_streams(c));
+        ++c->epoch;
+        if (c->d_clips) HIPCHK(hipFree(c->d_clips));
+        if (c->d_clipw) HIPCHK(hipFree(c->d_clipw));
+        c->d_clips = nullptr;
+        c->d_clipw = nullptr;
+        c->clip_ws_cap = 0;
+        const size_t nbN = (size_t)nb * c->N;
+        HIPCHK(dev_alloc((void **)&c->d_clips, (2 * nbN / CLIP_LEAF + 2 * (size_t)nb) * sizeof(float)));
+        HIPCHK(dev_alloc((void **)&c->d_clipw, 2 * nbN / CLIP_WAVE * sizeof(int)));
+        c->clip_ws_cap = nb;
+    }
+    if (c->clip_ov > c->ctail_cap) {
+        HIPCHK(sync_streams(c));
+        ++c->epoch;
+        if (c->d_ctail) HIPCHK(hipFree(c->d_ctail));
+        c->d_ctail = nullptr;
+        c->ctail_cap = 0;
+        const size_t bytes = sizeof(ClipTail) + (size_t)c->clip_ov * sizeof(cf);
+        HIPCHK(dev_alloc((void **)&c->d_ctail, bytes));
+        HIPCHK(hipMemset(c->d_ctail, 0, bytes));
+        c->ctail_cap = c->clip_ov;
+    }
+    return MFB_OK;
+}
+// The clip of nb blocks (block b at raw + b * xstride) for flight `slot`: its arguments, and the chain's restart if one is due
+static int clip_prepare(mfb_ctx *c, int slot, const cf *raw, long long xstride, int nb, ClipLaunch *L) {
+    // (a window's batches: room for the window's blocks at once, as batch_reserve does, so that sizes 1 ... B share the buffers)
+    int rc = clip_reserve(c, slot, nb > c->win_blocks ? nb : (c->win_blocks > 0 && xstride != 0 ? c->win_blocks : nb));
+    if (rc) return rc;
+    ClipArgs &a = L->a;
+    const size_t nbN = (size_t)c->clip_ws_cap * c->N;
+    a.x = (const float2 *)raw;
+    a.xstride = xstride;
+    a.y = (float2 *)c->d_clipx[slot];
+    a.idx = c->d_clipi[slot];
+    a.head = c->d_cliph[slot];
+    a.s1 = c->d_clips;
+    a.s2 = c->d_clips + nbN / CLIP_LEAF;
+    a.thr = c->d_clips + 2 * nbN / CLIP_LEAF;
+    a.wcnt = c->d_clipw;
+    a.wflag = c->d_clipw + nbN / CLIP_WAVE;
+    a.tail = c->clip_ov > 0 ? c->d_ctail : nullptr;
+    a.N = c->N;
+    a.ov = c->clip_ov;
+    a.nb = nb;
+    a.scale = c->clip_scale;
+    L->h_head = c->h_cliph[slot];
+    if (c->clip_restart) {       // outside any captured graph: the next block's overlap is taken as it is
+        if (c->d_ctail) HIPCHK(hipMemsetAsync(c->d_ctail, 0, sizeof(int32_t), c->stream));
+        c->clip_restart = false;
+    }
+    return MFB_OK;
+}
+// sum, sum again, clip, compact for every block at once; the chain in order (ov > 0); the heads to the flight's staging
+static int clip_enqueue(mfb_ctx *c, const ClipLaunch &L) {
+    const ClipArgs &a = L.a;
+    const dim3 grid(c->N / (CLIP_WAVE * (CLIP_THREADS / 64)), a.nb);
+    hipLaunchKernelGGL(k_clip_sum1, grid, dim3(CLIP_THREADS), 0, c->stream, a);
+    hipLaunchKernelGGL(k_clip_sum2, grid, dim3(CLIP_THREADS), 0, c->stream, a);
+    hipLaunchKernelGGL(k_clip_apply, grid, dim3(CLIP_THREADS), 0, c->stream, a);
+    hipLaunchKernelGGL(k_clip_compact, grid, dim3(CLIP_THREADS), 0, c->stream, a);
+    if (a.tail) hipLaunchKernelGGL(k_clip_chain, dim3(1), dim3(CLIP_CHAIN_THREADS), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(L.h_head, a.head, (size_t)a.nb * CLIP_HEAD * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    return MFB_OK;
+}
+extern "C" int mfb_set_peak_clip(mfb_ctx *c, float scale, int overlap) {
+    if (!c || !(scale >= 0.f) || isinf(scale) || overlap < 0 || overlap >= c->N) return MFB_ERR_ARG;
+    if (scale > 0.f && c->N < CLIP_THREADS / 64 * CLIP_WAVE) return MFB_ERR_UNSUPPORTED;
+    if (c->flight[0].active || c->flight[1].active) return MFB_ERR_STATE;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(sync_streams(c));
+    ++c->epoch;                  // the recorded graphs hold the old settings
+    c->clip_scale = scale;
+    c->clip_ov = scale > 0.f ? overlap : 0;
+    c->clip_restart = true;
+    return MFB_OK;
+}
+extern "C" int mfb_get_peak_clip_tail(mfb_ctx *c, float *host_c64, int count, int32_t *valid) {
+    if (!c || !valid || count < 0 || (count > 0 && !host_c64)) return MFB_ERR_ARG;
+    if (c->flight[0].active || c->flight[1].active) return MFB_ERR_STATE;
+    if (c->clip_ov <= 0 || !c->d_ctail || c->clip_restart) {
+        *valid = 0;
+        return MFB_OK;
+    }
+    if (count != c->clip_ov) return MFB_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(sync_streams(c));
+    HIPCHK(hipMemcpy(valid, &c->d_ctail->valid, sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (*valid) HIPCHK(hipMemcpy(host_c64, c->d_ctail->s, (size_t)count * sizeof(cf), hipMemcpyDeviceToHost));
+    return MFB_OK;
+}
+extern "C" int mfb_restart_peak_clip(mfb_ctx *c) {
+    if (!c) return MFB_ERR_ARG;
+    c->clip_restart = true;
+    return MFB_OK;
+}
+extern "C" int mfb_get_block_clips(mfb_ctx *c, int slot, int block, int32_t *idx, int cap, int32_t *count) {
+    if (!c || slot < 0 || slot > 1 || block < 0 || cap < 0 || !count || (cap > 0 && !idx)) return MFB_ERR_ARG;
+    const BlockFlight &f = c->flight[slot];
+    if (f.active || !f.clip || block >= (f.nb ? f.nb : 1)) return MFB_ERR_STATE;
+    const int32_t *h = c->h_cliph[slot] + (size_t)block * CLIP_HEAD;
+    const int n = h[0];
+    *count = n;
+    const int m = n < cap ? n : cap;
+    if (m <= CLIP_HEAD - 1) {
+        if (m > 0) memcpy(idx, h + 1, (size_t)m * sizeof(int32_t));
+    } else {
+        HIPCHK(hipSetDevice(c->device));
+        HIPCHK(hipMemcpy(idx, c->d_clipi[slot] + (size_t)block * c->N, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    return MFB_OK;
+}
+
 // Part 1 of a block / batch: forward transform(s), Doppler search, pick (or, at a fixed shift, the cleared scalars).
 static int block_enqueue_p1(mfb_ctx *c, const mfb_block_params *p, const BlkBufs &bb, int nthreads, int bcap) {
     int rc;
@@ -2045,6 +2214,7 @@ static int block_enqueue_p1(mfb_ctx *c, const mfb_block_params *p, const BlkBufs
         if (!batch) {
             if ((rc = before_fft(c))) return rc;
         }
+        if (bb.clip && (rc = clip_enqueue(c, *bb.clip))) return rc;
         if ((rc = forward_fft(c, bb.x, nullptr, bb.X, 1, nb, (size_t)bb.xstride))) return rc;
         if (!batch) {
             if ((rc = after_fft(c))) return rc;
@@ -2268,6 +2438,7 @@ static int block_begin(mfb_ctx *c, const mfb_block_params *p, int slot) {
     HIPCHK(hipSetDevice(c->device));
     BlockFlight &f = c->flight[slot];
     if (f.active) return MFB_ERR_STATE;          // its results have not been collected
+    if (c->clip_scale > 0.f && p->input == MFB_INPUT_UPLOADED) return MFB_ERR_UNSUPPORTED;     // its samples are transformed already
     const int bcap = p->mode == MFB_BLOCK_SEARCH ? p->band_capacity : 0;
     if ((rc = blkout_reserve(c, bcap > c->band_cap ? bcap : c->band_cap))) return rc;
     const int capacity = p->max_symbols < c->cap ? p->max_symbols : c->cap;
@@ -2283,14 +2454,23 @@ static int block_begin(mfb_ctx *c, const mfb_block_params *p, int slot) {
     // the samples of a page-locked buffer are (being) copied by block_input_copy on the input stream; this stream waits there
     if (pinned_in) c->d_in = which ? c->d_x2 : c->d_x;
     else if (p->input == MFB_INPUT_DEVICE) c->d_in = (const cf *)p->device_block;
+    // peak clip (mfb_set_peak_clip): the block's samples are clipped into the flight's buffer, which is then the block
+    const bool clip = c->clip_scale > 0.f;
+    ClipLaunch cl{};
+    if (clip) {
+        if ((rc = clip_prepare(c, slot, c->d_in, 0, 1, &cl))) return rc;
+        c->d_in = c->d_clipx[slot];
+    }
     const bool allowed = pinned_in && graphs_allowed() && !c->prof && !c->mirror && (p->input == MFB_INPUT_PINNED || c->h_in2);
     // two parts on two streams (mfb_set_batch_overlap), as for batches: the NEXT block's forward transform and search run beside this
     // block's matched filters, envelope transform, rate, centres and read-back.  Part 2 reads the samples (the STORE kernel), so the
     // input has to be one of the two page-locked buffers' device copies or the caller's device block -- not the handle's upload
     const bool split = batch_split(c) && p->input != MFB_INPUT_UPLOADED && c->path == MFB_PATH_SEGMENT;
     if (!split) {
+        BlkBufs bb = single_bufs(c);
+        if (clip) bb.clip = &cl;
         rc = graph_or_launch(c, c->bgraph[which][slot], p, 0, allowed,
-                             [&]() { return block_enqueue(c, p, single_bufs(c), c->h_blk[slot], nthreads, bcap, capacity, &shift); });
+                             [&]() { return block_enqueue(c, p, bb, c->h_blk[slot], nthreads, bcap, capacity, &shift); });
         if (rc) return rc;
         c->have_input = true;
         HIPCHK(hipEventRecord(c->ev_blk[slot], c->stream));
@@ -2304,6 +2484,7 @@ static int block_begin(mfb_ctx *c, const mfb_block_params *p, int slot) {
         }
         BlkBufs bb = single_bufs(c);
         bb.out = slot ? c->d_blkout2 : c->d_blkout;
+        if (clip) bb.clip = &cl;
         rc = graph_or_launch(c, c->bgraph[which][slot], p, -1, allowed, [&]() { return block_enqueue_p1(c, p, bb, nthreads, bcap); });
         if (rc) return rc;
         c->have_input = true;
@@ -2340,6 +2521,7 @@ static int block_begin(mfb_ctx *c, const mfb_block_params *p, int slot) {
     f.op = p->op;
     f.nb = 0;
     f.rec = 0;
+    f.clip = clip;
     c->have_xc = true;
     return MFB_OK;
 }
@@ -2578,7 +2760,17 @@ extern "C" int mfb_receive_blocks_begin(mfb_ctx *c, const mfb_block_params *p, i
     // (the two flights' records live in buffers of their own: the next batch's pick writes into its records while this batch's
     // are still being read on the other stream)
     BlkBufs bb{nblocks, win_in ? (const cf *)c->d_win[which] : (const cf *)p->device_block, stride, c->d_Xb, c->d_sumb, c->d_resb, c->d_xcb,
-               c->d_envb, c->d_Pb, c->d_crb, slot ? c->d_batout2 : c->d_batout, rec, stages ? core : 0, parity};
+               c->d_envb, c->d_Pb, c->d_crb, slot ? c->d_batout2 : c->d_batout, rec, stages ? core : 0, parity, nullptr};
+    // peak clip: the window's blocks are clipped into the flight's buffer (stride N), which the transforms and part 2 then read;
+    // the window itself -- where neighbouring blocks share their overlap -- stays as it is
+    const bool clip = c->clip_scale > 0.f;
+    ClipLaunch cl{};
+    if (clip) {
+        if ((rc = clip_prepare(c, slot, bb.x, stride, nblocks, &cl))) return rc;
+        bb.x = c->d_clipx[slot];
+        bb.xstride = c->N;
+        bb.clip = &cl;
+    }
     int shift = p->mode == MFB_BLOCK_FIXED_SHIFT ? ((p->fixed_shift % c->N) + c->N) % c->N : 0;
     const bool allowed = win_in && graphs_allowed() && !c->prof;
     mfb_block_params q = *p;
@@ -2632,6 +2824,7 @@ extern "C" int mfb_receive_blocks_begin(mfb_ctx *c, const mfb_block_params *p, i
     f.nb = nblocks;
     f.rec = rec;
     f.ext = stages ? core : 0;
+    f.clip = clip;
     c->last_batch_blocks = p->mode == MFB_BLOCK_SEARCH ? nblocks : 0;
     // the handle's one-block buffers (spectrum, matched-filter outputs) hold nothing of this batch
     c->have_xc = false;

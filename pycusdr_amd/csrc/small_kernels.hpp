@@ -299,7 +299,9 @@ DEVI void code_rate_body(const cf *P, float *out, int offset, int len, float *sv
         __syncthreads();
     }
     if (tid == 0) {
-        const int k = (len > 0) ? si[0] : 0;
+        int k = (len > 0) ? si[0] : 0;
+        // a window without a single ordered value (all NaN: a block holding a NaN sample) keeps the sentinel; stay inside it
+        if (len > 0 && (k < offset || k >= offset + len)) k = offset;
         const cf z = P[k];
         out[0] = (float)k;
         out[1] = atan2f(z.y, z.x);

@@ -14,6 +14,9 @@ class Demodulator(_HostDriver):
         """Clip interference peaks in place (their indices are kept for the trust tagging), then
         forward-FFT the block.  The first, second and fourth results are the constants the
         reference returns in place of a Doppler estimate."""
+        if self._device_clip:
+            # clipped here: the device takes the block as it is (after device-clipped blocks, the overlap is their clipped tail)
+            self._armDeviceClip(False, samples)
         self._thresholdInput(samples)
         if self._one_call:
             self.dopplerIdxlast = self.doppOffsetIdx

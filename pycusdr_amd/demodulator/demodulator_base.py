@@ -57,6 +57,21 @@ def doppler_bin_table(confRadio, rangeRateMax, Nfft):
     return grid, grid * spsym * baud, shifts, int(stx_idx)
 
 
+def fill_peak_gaps(hot, Nfft, min_gap):
+    """clippedPeakI: the clipped indices ``hot`` (ascending) with gaps of fewer than ``min_gap`` samples between them filled
+    (reference DB:696-707).  Shared by the host clip and the indices the device clip hands out."""
+    if len(hot) > 0:
+        gaps = np.diff(hot)
+        real_gaps = np.where(gaps > 1)[0]
+        small = np.where(gaps[real_gaps] < min_gap)[0]
+        marks = np.zeros(Nfft, dtype=np.int8)
+        marks[hot] = 1
+        for gi in real_gaps[small]:
+            marks[hot[gi]:hot[gi] + gaps[gi]] = 1
+        return np.where(marks == 1)[0]
+    return hot.copy()
+
+
 def _first_true(mask):
     """Index of the first True -- ``np.where(mask)[0][0]`` (reference DB:880-881) without building the index array; like it,
     IndexError when there is none."""
@@ -191,6 +206,13 @@ class Demodulator:
                             'it is fetched afterwards when no later block is on the device yet, else that block reports SNR = nan',
                             radioName, longest)
 
+        # interference-peak clipping on the device (S-band back end; the reference clips on the host, DB:670-707):
+        #   "HIP": {"device_clip": true}
+        # Off by default.  When on, beginBlock / endBlock clip every block on the device before its transform, chained from block to
+        # block as the reference's loop carries the overlap after clipping; uploadAndFindCarrier keeps clipping on the host.
+        self._device_clip = bool(hip_cfg.get('device_clip', False)) and self._one_call and self.backend != 'UHF'
+        self._clip_armed = False
+
         # windowed argmax range of the symbol-rate estimate (reference DB:508-512)
         self.symsTolLow = 0.9 * spsym
         self.symsTolHigh = 1.1 * spsym
@@ -265,17 +287,23 @@ class Demodulator:
         self.clippedPeakIPure = hot
         samples[hot] = thresh * (samples[hot] / mag[hot])
         if len(hot) > 0:
-            gaps = np.diff(hot)
-            real_gaps = np.where(gaps > 1)[0]
             self.peakMinGap = 100
-            small = np.where(gaps[real_gaps] < self.peakMinGap)[0]
-            marks = np.zeros(self.Nfft, dtype=np.int8)
-            marks[hot] = 1
-            for gi in real_gaps[small]:
-                marks[hot[gi]:hot[gi] + gaps[gi]] = 1
-            self.clippedPeakI = np.where(marks == 1)[0]
-        else:
-            self.clippedPeakI = hot.copy()
+        self.clippedPeakI = fill_peak_gaps(hot, self.Nfft, 100)
+
+    def _armDeviceClip(self, on, samples=None):
+        """Device clipping on for the next block (chained to the blocks after it), or off for a block clipped on the host.
+        Turning it on restarts the chain: the block before did not go through the device clip.  Turning it off with the block
+        ``samples`` about to be clipped on the host: their overlap becomes the last device-clipped block's clipped tail, as
+        the reference's loop carries it (DP:293,337).  Nothing may be in flight."""
+        if on != self._clip_armed:
+            if on:
+                self.bank.set_peak_clip(self.peakThresholdScale, self.sigOverlap)
+            else:
+                tail = self.bank.peak_clip_tail(self.sigOverlap) if samples is not None else None
+                if tail is not None:
+                    samples[:self.sigOverlap] = tail
+                self.bank.set_peak_clip(0)
+            self._clip_armed = on
 
     def uploadAndFindUHF(self, samples):
         self._thresholdInput(samples)
@@ -305,6 +333,9 @@ class Demodulator:
         return at once; ``endBlock(slot)`` collects it.  Lets the caller run the sequential host stages of the previous
         block (and assemble the next one in the other buffer) while the device works -- the blocks themselves still
         execute, and are collected, strictly in order."""
+        if self._device_clip:           # STX: the fixed IF-offset shift, the block clipped on the device first
+            self._armDeviceClip(True)
+            fixed_shift = int(self.doppOffsetIdx)
         self.bank.begin_block(slot, self.codeRateAndPhaseOffsetHigh, self.codeRateAndPhaseOffsetLow - self.codeRateAndPhaseOffsetHigh,
                               self.spsymMin, op=Operations.CENTRES_ABS.value, snr_window=5, fixed_shift=fixed_shift, source=source,
                               device_ptr=device_ptr)
@@ -316,6 +347,11 @@ class Demodulator:
         if self.backend == 'UHF':
             return self._estimate_from_block(self._pending)
         self.dopplerIdxlast = self.doppOffsetIdx
+        if 'clipped' in self._pending:
+            self.clippedPeakIPure = self._pending['clipped']
+            if len(self.clippedPeakIPure) > 0:
+                self.peakMinGap = 100
+            self.clippedPeakI = fill_peak_gaps(self.clippedPeakIPure, self.Nfft, 100)
         return 0, 0, self.clippedPeakIPure, 0
 
     # ---- B consecutive blocks per call ----------------------------------------------------------
@@ -326,10 +362,15 @@ class Demodulator:
 
     def beginBlocks(self, slot, nblocks, source='window'):
         """``beginBlock`` for the first ``nblocks`` blocks of window ``source`` ('window' / 'window2'): the device side of all of
-        them as one set of launches (mfb_receive_blocks_begin); ``endBlocks(slot)`` collects.  UHF back end, one-call path."""
+        them as one set of launches (mfb_receive_blocks_begin); ``endBlocks(slot)`` collects.  UHF back end, one-call path -- or STX
+        with the device clip: the blocks at the IF-offset shift, clipped on the device and chained from block to block."""
+        fixed_shift = None
+        if self._device_clip:
+            self._armDeviceClip(True)
+            fixed_shift = int(self.doppOffsetIdx)
         self.bank.begin_blocks(slot, nblocks, self.codeRateAndPhaseOffsetHigh,
                                self.codeRateAndPhaseOffsetLow - self.codeRateAndPhaseOffsetHigh, self.spsymMin,
-                               op=Operations.CENTRES_ABS.value, snr_window=5, source=source)
+                               op=Operations.CENTRES_ABS.value, snr_window=5, fixed_shift=fixed_shift, source=source)
 
     # ---- A12 / A13 / A14 of a batch on the device (stream_kernels.hpp) -----------------------------
     def enableStreamStages(self, decoder=None):
@@ -403,8 +444,12 @@ class Demodulator:
         # attributes once behind the loop)
         pick_valid, low, high, frac, picks, counts = s['pick_valid'], s['low'], s['high'], s['frac'], s['pick'], s['count']
         hz, hz_off, clipped = self.doppHzLUT, self.centreFreqOffset, self.clippedPeakIPure
+        fixed = not R.searched          # STX: no search; the device clip's indices per block (DB:670-707)
         for b in range(nb):
-            if not pick_valid[b]:       # NaN index (all-zero block): skip the block (reference DB:625-630)
+            if fixed:
+                clipped = R.clipped[b] if R.clipped is not None else self.clippedPeakIPure
+                est = (0, 0, clipped, 0)
+            elif not pick_valid[b]:       # NaN index (all-zero block): skip the block (reference DB:625-630)
                 log.error('Error occurred during find_UHF -- skipping block. Message: cannot convert float NaN to integer')
                 est = (0., 0., clipped, 0.)
             else:
@@ -428,7 +473,7 @@ class Demodulator:
             if s['rate_fallback'][b]:
                 log.error('Code rate result 0 should not happen but happened -- fixing it to 10')
             rec = {'spSym': s['spSym'][b], 'symbols': R.sym[b, :n], 'centres': R.cen[b, :n],
-                   'trust': R.mag[b].view(TRUSTTYPE)[:n], 'clipped': empty}
+                   'trust': R.mag[b].view(TRUSTTYPE)[:n], 'clipped': np.asarray(clipped, dtype=np.int64) if fixed else empty}
             if stages:
                 if s['a13_status'][b]:
                     nw = s['a13_nwin'][b]
@@ -459,7 +504,14 @@ class Demodulator:
         if nb:
             # what the object remembers of its last block (DB:612-632, 730-752)
             last = nb - 1
-            if pick_valid[last]:
+            if fixed:
+                self.dopplerIdxlast = self.doppOffsetIdx
+                if R.clipped is not None:
+                    self.clippedPeakIPure = R.clipped[last]
+                    if len(self.clippedPeakIPure) > 0:
+                        self.peakMinGap = 100
+                    self.clippedPeakI = fill_peak_gaps(self.clippedPeakIPure, self.Nfft, 100)
+            elif pick_valid[last]:
                 self._pick_bin = low[last]
                 self.dopplerIdxlast = np.int32(s['shift'][last])
             else:

@@ -99,10 +99,16 @@ class DemodulatorRunner:
 
     def feed_resident(self, device_ptr):
         """``feed_device`` for a whole block (N complex64 samples, overlap included) that already sits in device memory
-        at ``device_ptr``: no host copy, no overlap carry."""
-        if self.radioBackend != 'UHF':
+        at ``device_ptr``: no host copy, no overlap carry.  STX with the device clip: consecutive resident blocks are taken
+        as neighbouring blocks of ONE stream -- the device replaces a block's first ``overlap`` samples by the previous
+        device-clipped block's clipped tail, as the reference's loop carries the overlap after clipping (DP:293,337); call
+        ``self.demod.bank.restart_peak_clip()`` before a block that does not continue the previous one."""
+        if self.radioBackend != 'UHF' and not self._device_clip():
             # the STX back end starts with peak clipping of the samples on the host (reference STX.py:13, DB:670-707)
-            raise ValueError('device-resident blocks are only supported by the UHF back end: STX clips the samples on the host first')
+            raise ValueError('device-resident blocks of the STX back end need "HIP": {"device_clip": true}: it clips the samples first')
+        if self.radioBackend != 'UHF':
+            self.feed_resident_begin(device_ptr)
+            return self.feed_device_end()
         stamp = time.time()
         part = {'count': self.count, 'timestamp': stamp}
         part['doppler'], part['doppler_std'], _, part['SNR'] = self.demod.uploadAndFindCarrier(None, device_ptr=device_ptr)
@@ -113,7 +119,7 @@ class DemodulatorRunner:
 
     def feed_resident_begin(self, device_ptr):
         """``feed_resident`` in two halves (``feed_device_end`` collects): the block's device work is enqueued and the call returns."""
-        if not (self.radioBackend == 'UHF' and getattr(self.demod, '_one_call', False)):
+        if not self._one_block_path():
             self._flight = ('done', self.feed_resident(device_ptr))
             return
         stamp = time.time()
@@ -148,6 +154,14 @@ class DemodulatorRunner:
         self.count += 1
         return part
 
+    def _device_clip(self):
+        return getattr(self.demod, '_device_clip', False)
+
+    def _one_block_path(self):
+        """The block-call path (beginBlock / endBlock) is in use: UHF on the one-call path, or STX with the device clip (the
+        host clip would otherwise have to run on every block before its upload)."""
+        return getattr(self.demod, '_one_call', False) and (self.radioBackend == 'UHF' or self._device_clip())
+
     def _block_buffers(self):
         """The library's two page-locked input buffers, by the NAME the library knows them under ('pinned' = index 0,
         'pinned2' = index 1), and the index of the one ``self.raw`` -- where the next block is being assembled, carried
@@ -167,7 +181,7 @@ class DemodulatorRunner:
         Doppler-sharded handles, ``"one_call": false``)."""
         if len(new_samples) != self.samplesPerSlice:
             raise ValueError(f'expected {self.samplesPerSlice} new samples per block, got {len(new_samples)}')
-        if not (self.radioBackend == 'UHF' and getattr(self.demod, '_one_call', False)):
+        if not self._one_block_path():
             self._flight = ('done', self.feed_device(new_samples))
             return
         bufs, cur = self._block_buffers()
@@ -269,7 +283,7 @@ class DemodulatorRunner:
                         return
             return self.run(blocks(), sink=sink, decoder=decoder, pipelined=True)
         from .sigFIFO import BlockAssembler
-        if not (overlapped and self.radioBackend == 'UHF' and getattr(self.demod, '_one_call', False)):
+        if not (overlapped and self._one_block_path()):
             asm = BlockAssembler(self.raw, self.overlap)
             return self.run((None for chunk in chunk_source if chunk is not None for _ in asm.push(chunk)), sink=sink, decoder=decoder)
         # how many blocks per device call: the caller's word, else the configuration's, else ("auto") whatever the source has ready.

@@ -80,6 +80,8 @@ class BatchRecord:
     """A finished batch of blocks as it came off the device (mfb_receive_blocks_end_record): ``nb`` records in one buffer, read
     in place.  Scalars come as one Python list per field (``s['count'][b]``); arrays as 2-D views, block b in row b."""
 
+    clipped = None             # per block: the device's clippedPeakIPure (int64), when the blocks were clipped (set_peak_clip)
+
     def __init__(self, buf, lay, searched):
         nb, rec, n = lay.nblocks, lay.record_bytes, lay.symbols
         self.nb, self.searched, self.bcap, self.mode = nb, searched, lay.band_capacity, lay.mode
@@ -116,6 +118,8 @@ class BatchRecord:
              'cr': tuple(np.float32(v) for v in s['cr'][b]), 'spSym': s['spSym'][b], 'codeOffset': s['codeOffset'][b],
              'rate_fallback': bool(s['rate_fallback'][b]), 'symbols': self.sym[b, :n], 'centres': self.cen[b, :n],
              'magnitudes': self.mag[b, :n], 'bands': None}
+        if self.clipped is not None:
+            d['clipped'] = self.clipped[b]
         l0, l1 = s['band_len'][b]
         if self.searched and self.bands is not None and l0 <= self.bcap and l1 <= self.bcap:
             d['bands'] = (self.bands[b, 0, :l0], self.bands[b, 1, :l1])
@@ -367,7 +371,44 @@ class MFBank:
         sym, cen, mag, bands = self._block_arrays()
         _lib.check(self._lib.mfb_receive_block(self._h, C.byref(P), C.byref(R), _ptr(sym), _ptr(cen), _ptr(mag), _ptr(bands)),
                    'mfb_receive_block')
-        return self._block_result(R, fixed_shift is None)
+        out = self._block_result(R, fixed_shift is None)
+        if getattr(self, '_clip', False):
+            out['clipped'] = self.get_block_clips(0)
+        return out
+
+    # -- interference-peak clipping on the device (reference __thresholdInput, DB:670-707) ---------
+    def set_peak_clip(self, scale, overlap=0):
+        """Clip interference peaks out of every block on the device before it is transformed (mfb_set_peak_clip): twice, above
+        ``scale`` times the mean magnitude, bit for bit as ``Demodulator._thresholdInput`` does it on the host.  ``overlap`` > 0
+        chains consecutive blocks (a block's first ``overlap`` samples are the previous block's clipped tail); every call
+        restarts the chain.  ``scale`` 0 switches clipping off.  Block results then carry 'clipped' (int64 indices)."""
+        _lib.check(self._lib.mfb_set_peak_clip(self._h, C.c_float(float(scale)), int(overlap)), 'mfb_set_peak_clip')
+        self._clip = float(scale) > 0
+
+    def peak_clip_tail(self, overlap):
+        """The last device-clipped block's clipped last ``overlap`` samples (mfb_get_peak_clip_tail), or None when the chain holds
+        none."""
+        out = np.empty(int(overlap), np.complex64)
+        v = C.c_int32(0)
+        _lib.check(self._lib.mfb_get_peak_clip_tail(self._h, _ptr(out), out.size, C.byref(v)), 'mfb_get_peak_clip_tail')
+        return out if v.value else None
+
+    def restart_peak_clip(self):
+        """The next block's overlap is taken as given (mfb_restart_peak_clip): the previous block was not clipped here."""
+        _lib.check(self._lib.mfb_restart_peak_clip(self._h), 'mfb_restart_peak_clip')
+
+    def get_block_clips(self, slot, block=0):
+        """clippedPeakIPure of block ``block`` of the flight collected last from ``slot`` (mfb_get_block_clips), int64."""
+        n = C.c_int32(0)
+        buf = getattr(self, '_clipbuf', None)
+        if buf is None:
+            buf = self._clipbuf = np.empty(256, np.int32)
+        _lib.check(self._lib.mfb_get_block_clips(self._h, int(slot), int(block), _ptr(buf), buf.size, C.byref(n)), 'mfb_get_block_clips')
+        if n.value > buf.size:
+            buf = np.empty(n.value, np.int32)
+            _lib.check(self._lib.mfb_get_block_clips(self._h, int(slot), int(block), _ptr(buf), buf.size, C.byref(n)),
+                       'mfb_get_block_clips')
+        return buf[:n.value].astype(np.int64)
 
     def debug_block_scalars(self, picks, triples, spsym_min, snr_window=5, max_symbols=None):
         """Test seam (mfb_debug_block_scalars): the one-call path's two float64 device stages on injected picks
@@ -411,6 +452,8 @@ class MFBank:
         (``slot`` 0 / 1) may be in flight."""
         P = self._block_params(k_offset, k_len, spsym_min, op, snr_window, fixed_shift, source, device_ptr)
         _lib.check(self._lib.mfb_receive_block_begin(self._h, C.byref(P), int(slot)), 'mfb_receive_block_begin')
+        self._clipped = getattr(self, '_clipped', {})
+        self._clipped[int(slot)] = getattr(self, '_clip', False)
         self._searched = getattr(self, '_searched', {})
         self._searched[int(slot)] = fixed_shift is None
         self._flying = getattr(self, '_flying', set()) | {int(slot)}
@@ -424,7 +467,10 @@ class MFBank:
                        'mfb_receive_block_end')
         finally:            # collected, or failed: either way the slot holds no block any more
             self._flying = getattr(self, '_flying', set()) - {int(slot)}
-        return self._block_result(R, self._searched.get(int(slot), True))
+        out = self._block_result(R, self._searched.get(int(slot), True))
+        if getattr(self, '_clipped', {}).get(int(slot), False):
+            out['clipped'] = self.get_block_clips(slot)
+        return out
 
     # -- B consecutive blocks per call -----------------------------------------------------------
     def windows(self, max_blocks, block_stride):
@@ -450,6 +496,8 @@ class MFBank:
         device memory, ``block_stride`` required)."""
         P = self._block_params(k_offset, k_len, spsym_min, op, snr_window, fixed_shift, source, device_ptr, block_stride)
         _lib.check(self._lib.mfb_receive_blocks_begin(self._h, C.byref(P), int(nblocks), int(slot)), 'mfb_receive_blocks_begin')
+        self._clipped = getattr(self, '_clipped', {})
+        self._clipped[int(slot)] = getattr(self, '_clip', False)
         self._searched = getattr(self, '_searched', {})
         self._searched[int(slot)] = fixed_shift is None
         self._batch = getattr(self, '_batch', {})
@@ -484,7 +532,10 @@ class MFBank:
             # saying so (computeSNR's stale-spectrum guard reads it)
             self._flying = getattr(self, '_flying', set()) - {slot}
         _lib.check(rc, 'mfb_receive_blocks_end_record')
-        return BatchRecord(buf, lay, self._searched.get(slot, True))
+        R = BatchRecord(buf, lay, self._searched.get(slot, True))
+        if getattr(self, '_clipped', {}).get(slot, False):
+            R.clipped = [self.get_block_clips(slot, b) for b in range(R.nb)]
+        return R
 
     def end_blocks(self, slot):
         """Wait for the batch begun in ``slot``; one dict per block, each exactly what ``receive_block`` returns for that block
