@@ -15,6 +15,7 @@
 #pragma once
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <algorithm>
 #include <complex>
@@ -281,6 +282,78 @@ static inline void segment_spectra_shifted(const Bank &b, const int *rows, int n
         }
     };
     run_striped(nthr, work);
+}
+
+// The wrap-around outputs of the 256-point search on the matrix cores (wrap_kernels.hpp): per bin the shifted taps h_u[r] = tap(u, r)
+// e^{+2 pi i s r / N} (r < T, the rows of segment_spectra_shifted) as the B operand of v_mfma_f32_16x16x32_f16 in real form
+// [[Hr, Hi], [-Hi, Hr]]: K-step kk holds taps 16 kk ... 16 kk + 15, rows k < 16 multiply the window's real parts, k >= 16 its imaginary
+// parts; column c = 2 u + (0: re, 1: im) of the output.  The bin is scaled by 2^e_b (its largest |component| into [2^14, 2^15)) and
+// split into hi = fp16(h) and lo = fp16(h - hi).  Storage: [shift][kk][hi, lo][lane][8] fp16 bits, lane l holding B[8 (l >> 4) + j]
+// [l & 15] -- one 16-byte load per fragment; exps[shift] = 2 log2(N) - 2 e_b (the wrap energy comes out as N^2 sum |conv|^2).
+// IEEE binary16 bits of a float, rounded to nearest even (subnormals included; the tables stay far below the overflow threshold), and back
+static inline uint16_t half_bits(float f) {
+    uint32_t x;
+    memcpy(&x, &f, 4);
+    const uint16_t sign = (uint16_t)((x >> 16) & 0x8000u);
+    x &= 0x7fffffffu;
+    if (x >= 0x47800000u) return (uint16_t)(sign | (x > 0x7f800000u ? 0x7e00u : 0x7c00u));
+    if (x < 0x38800000u) {                         // below 2^-14: a multiple of 2^-24, rounded by nearbyint (to even)
+        float a;
+        memcpy(&a, &x, 4);
+        return (uint16_t)(sign | (uint16_t)std::nearbyint(a * 16777216.0f));
+    }
+    uint32_t r = x - 0x38000000u;                  // exponent bias 127 -> 15
+    r += 0x0fffu + ((r >> 13) & 1u);
+    return (uint16_t)(sign | (uint16_t)(r >> 13));
+}
+static inline double half_value(uint16_t h) {
+    const int e = (h >> 10) & 31, m = h & 1023;
+    const double v = e == 0 ? std::ldexp((double)m, -24) : std::ldexp((double)(m | 1024), e - 25);
+    return (h & 0x8000u) ? -v : v;
+}
+static inline void wrap_taps_shifted(const Bank &b, const int *rows, int nrows, const int *shifts, int nshifts, int KT,
+                                     std::vector<uint16_t> *out, std::vector<int> *exps) {
+    const size_t per_bin = (size_t)KT * 2 * 64 * 8;
+    out->assign((size_t)nshifts * per_bin, 0);
+    exps->assign((size_t)nshifts, 0);
+    int log2n = 0;
+    while ((1 << log2n) < b.N) ++log2n;
+    std::vector<cd> h((size_t)nrows * 16 * KT);
+    for (int j = 0; j < nshifts; ++j) {
+        const long long s = shifts[j];
+        std::fill(h.begin(), h.end(), cd(0.0, 0.0));
+        double mx = 0.0;
+        for (int u = 0; u < nrows; ++u) {
+            const int m = rows ? rows[u] : u;
+            for (int r = 0; r < b.T && r < 16 * KT; ++r) {
+                const double ang = 2.0 * M_PI * (double)((s * r) % b.N) / (double)b.N;
+                const cd v = tap(b, m, r) * cd(cos(ang), sin(ang));
+                h[(size_t)u * 16 * KT + r] = v;
+                mx = std::max(mx, std::max(std::fabs(v.real()), std::fabs(v.imag())));
+            }
+        }
+        int e = 0;
+        (void)std::frexp(mx, &e);
+        const int eb = 15 - e;
+        (*exps)[j] = 2 * log2n - 2 * eb;
+        uint16_t *o = out->data() + (size_t)j * per_bin;
+        for (int kk = 0; kk < KT; ++kk)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int jj = 0; jj < 8; ++jj) {
+                    const int k = 8 * (lane >> 4) + jj, c = lane & 15, u = c >> 1;
+                    double val = 0.0;
+                    if (u < nrows) {
+                        const cd t = h[(size_t)u * 16 * KT + 16 * kk + (k & 15)];
+                        // rows k < 16 (window re): (Hr, Hi); rows k >= 16 (window im): (-Hi, Hr)
+                        val = k < 16 ? ((c & 1) ? t.imag() : t.real()) : ((c & 1) ? t.real() : -t.imag());
+                    }
+                    const double sv = std::ldexp(val, eb);
+                    const uint16_t bh = half_bits((float)sv);
+                    const uint16_t bl = half_bits((float)(sv - half_value(bh)));
+                    o[((size_t)(kk * 2 + 0) * 64 + lane) * 8 + jj] = bh;
+                    o[((size_t)(kk * 2 + 1) * 64 + lane) * 8 + jj] = bl;
+                }
+    }
 }
 
 // ---- span basis (opt-in, SUM_ALL_MASKS search only) ---------------------------------------------------------

@@ -48,6 +48,7 @@
 #include "fft_core.hpp"
 #include "filter_taps.hpp"
 #include "seg_kernels.hpp"
+#include "wrap_kernels.hpp"
 #include "twopass_kernels.hpp"
 #include "small_kernels.hpp"
 #include "sync_kernels.hpp"
@@ -197,6 +198,9 @@ struct mfb_ctx {
     int gs_rows = 0;                     // rows per bin d_Gs was built for (0: not built)
     int gs_span = -1;                    // ... and for which basis
     int gs_l = 0;                        // ... and segment length (log2)
+    u32x4 *d_Wb = nullptr;               // [Dtot][KT][2][64]: B fragments of the wrap-around outputs (wrap_kernels.hpp), built with d_Gs
+    int *d_Wexp = nullptr;               // [Dtot]: their powers of two
+    int wb_kt = 0;                       // K-steps d_Wb was built for (0: not built)
     int fsm_fb = 0, fsm_fs = 0;          // rectangle of a wave: bins x slots (0: default)
     // interference-peak clipping before the forward transform (clip_kernels.hpp, mfb_set_peak_clip; DB:670-707)
     float clip_scale = 0.f;              // 0: off
@@ -477,6 +481,10 @@ static int set_kernel_attributes(const mfb_ctx *c) {
     if constexpr (segf_has_presum<L_, PV_>())                                                                                         \
         HIPCHK(hipFuncSetAttribute((const void *)k_segf<L_, PV_, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, B_))
         MFB_ATTR_Q(256, 11, b); MFB_ATTR_Q(256, 12, b); MFB_ATTR_Q(256, 13, b); MFB_ATTR_Q(256, 14, b); MFB_ATTR_Q(256, 15, b);
+        {
+            const int bw = (int)SegWCfg<13, 3>::lds_bytes();
+            HIPCHK(hipFuncSetAttribute((const void *)k_segw<13, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, bw));
+        }
         const int b2 = (int)(SegCfg<2048>::LDS_ELEMS * sizeof(cf) + (size_t)(SegCfg<2048>::BLOCK / 64) * 8 * SEG_ACC_STRIDE * sizeof(float));
 #define MFB_ATTR_F(PV_) HIPCHK(hipFuncSetAttribute((const void *)k_segf<2048, PV_>, hipFuncAttributeMaxDynamicSharedMemorySize, b2))
         MFB_ATTR_F(16); MFB_ATTR_F(17); MFB_ATTR_F(18); MFB_ATTR_F(19); MFB_ATTR_F(20); MFB_ATTR_F(21); MFB_ATTR_F(22); MFB_ATTR_F(23); MFB_ATTR_F(24);
@@ -684,6 +692,8 @@ extern "C" int mfb_destroy(mfb_ctx *c) {
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->d_Gs) (void)hipFree(c->d_Gs);
     if (c->d_Qs) (void)hipFree(c->d_Qs);
+    if (c->d_Wb) (void)hipFree(c->d_Wb);
+    if (c->d_Wexp) (void)hipFree(c->d_Wexp);
     for (int i = 0; i < 2; ++i) {
         if (c->d_clipx[i]) (void)hipFree(c->d_clipx[i]);
         if (c->d_clipi[i]) (void)hipFree(c->d_clipi[i]);
@@ -1464,11 +1474,34 @@ static bool fsm_enabled() {
     static const int on = getenv("MFB_SEG_FSM") ? atoi(getenv("MFB_SEG_FSM")) : 1;
     return on != 0 && MFB_FFT_FUSED;
 }
+// MFB_SEG_WRAP_MFMA=0 in the environment keeps the wrap-around energy of the 256-point search on the vector ALUs (segf_body) instead of
+// the matrix cores (wrap_kernels.hpp, k_segw): the A/B switch of profiles/r07_wrap_mfma.md
+static bool wrap_mfma_enabled() {
+    static const int on = getenv("MFB_SEG_WRAP_MFMA") ? atoi(getenv("MFB_SEG_WRAP_MFMA")) : 1;
+    return on != 0;
+}
+// K-steps of the matrix-core form of the search, 0 where it does not run: 256-point segments, SUM_ALL searches whose rows k_finalize
+// counts equally (segf_body's SUMQ = 2 form), one 16-column tile per bin (MU <= 8) and the instantiated shape -- 13 valid register
+// slots, 33 ... 48 taps (the 8-filter GMSK banks).  The BPSK bank (80 taps, 16 rows) keeps segf_body.
+// Blocks of 2^18 samples and more only: a single small block (2^15 ... 2^17 samples x 64 bins) gets one-bin rectangles from fsm_plan, and
+// there the forward transform and the A fragments, built per (slot, bin) at one wave per SIMD, made the search slower than segf_body
+// (bench.py --full, recv_b1_n17_d64: 607 against 763 Msamples/s).  The choice depends on the bank and the block length alone -- never on
+// the number of bins, the rectangle or the grid -- so that a (block, shift) scores the same bits from any handle, shard, tuning or batch.
+static int wrap_kt(const mfb_ctx *c, bool span, int MU) {
+    if (!wrap_mfma_enabled() || c->segl != 8 || c->N < (1 << 18) || !c->sum_all || !MFB_SEG_SUMQ || !c->bank || MU > 8) return 0;
+    const bool presum = span || std::all_of(c->h_mult.begin(), c->h_mult.end(), [&](int m) { return m == c->h_mult[0]; });
+    if (!presum || !segf_has_presum<256, 13>() || c->V != 13 * SegCfg<256>::NT) return 0;
+    const int T = c->bank->T;
+    return (T > 32 && T <= 48) ? 3 : 0;
+}
 // per-bin spectra of the bank in force (the unique filters, or the span basis), built when the shifts or the filters have changed
 static int fsm_prepare(mfb_ctx *c, bool span, int rows) {
-    if (c->d_Gs && c->gs_rows == rows && c->gs_span == (span ? 1 : 0) && c->gs_l == c->segl) return MFB_OK;
+    const int wkt = wrap_kt(c, span, rows);
+    if (c->d_Gs && c->gs_rows == rows && c->gs_span == (span ? 1 : 0) && c->gs_l == c->segl && c->wb_kt == wkt) return MFB_OK;
     if ((int)c->h_shifts.size() != c->Dtot || !c->bank) return MFB_ERR_STATE;
     std::vector<float> G, Q;
+    std::vector<uint16_t> W;
+    std::vector<int> Wexp;
     // SUM_ALL searches: the per-bin table of sum_rows w |G|^2 (segf_body, SUMQ); w = how often k_finalize counts the row, relative to
     // row 0, whose partial sums carry the bin's total
     std::vector<float> *q = (c->sum_all && MFB_SEG_SUMQ) ? &Q : nullptr;
@@ -1477,11 +1510,13 @@ static int fsm_prepare(mfb_ctx *c, bool span, int rows) {
         taps::Bank sb;
         if (taps::span_basis(*c->bank, &sb) != rows) return MFB_ERR_STATE;
         taps::segment_spectra_shifted(sb, nullptr, rows, c->h_shifts.data(), c->Dtot, L, Te, &G, seg_ppl(L), q, nullptr);
+        if (wkt) taps::wrap_taps_shifted(sb, nullptr, rows, c->h_shifts.data(), c->Dtot, wkt, &W, &Wexp);
     } else {
         if ((int)c->h_uniq.size() != rows || (int)c->h_mult.size() != rows || c->h_mult[0] < 1) return MFB_ERR_STATE;
         std::vector<double> wts((size_t)rows);
         for (int u = 0; u < rows; ++u) wts[(size_t)u] = (double)c->h_mult[(size_t)u] / (double)c->h_mult[0];
         taps::segment_spectra_shifted(*c->bank, c->h_uniq.data(), rows, c->h_shifts.data(), c->Dtot, L, Te, &G, seg_ppl(L), q, wts.data());
+        if (wkt) taps::wrap_taps_shifted(*c->bank, c->h_uniq.data(), rows, c->h_shifts.data(), c->Dtot, wkt, &W, &Wexp);
     }
     HIPCHK(sync_streams(c));
     if (c->d_Gs) HIPCHK(hipFree(c->d_Gs));
@@ -1489,11 +1524,23 @@ static int fsm_prepare(mfb_ctx *c, bool span, int rows) {
     c->gs_rows = 0;
     if (c->d_Qs) HIPCHK(hipFree(c->d_Qs));
     c->d_Qs = nullptr;
+    if (c->d_Wb) HIPCHK(hipFree(c->d_Wb));
+    c->d_Wb = nullptr;
+    if (c->d_Wexp) HIPCHK(hipFree(c->d_Wexp));
+    c->d_Wexp = nullptr;
+    c->wb_kt = 0;
     HIPCHK(dev_alloc((void **)&c->d_Gs, G.size() * sizeof(float)));
     HIPCHK(hipMemcpy(c->d_Gs, G.data(), G.size() * sizeof(float), hipMemcpyHostToDevice));
     if (q) {
         HIPCHK(dev_alloc((void **)&c->d_Qs, Q.size() * sizeof(float)));
         HIPCHK(hipMemcpy(c->d_Qs, Q.data(), Q.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    if (wkt) {
+        HIPCHK(dev_alloc((void **)&c->d_Wb, W.size() * sizeof(uint16_t)));
+        HIPCHK(hipMemcpy(c->d_Wb, W.data(), W.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+        HIPCHK(dev_alloc((void **)&c->d_Wexp, Wexp.size() * sizeof(int)));
+        HIPCHK(hipMemcpy(c->d_Wexp, Wexp.data(), Wexp.size() * sizeof(int), hipMemcpyHostToDevice));
+        c->wb_kt = wkt;
     }
     c->gs_rows = rows;
     c->gs_span = span ? 1 : 0;
@@ -1618,6 +1665,18 @@ static int launch_fsm(mfb_ctx *c, int nb, const cf *x, int xstride, int MU, int 
     if (w32) {
         const size_t lds = SegCfg<2048>::LDS_ELEMS * sizeof(cf) + (size_t)wpb * MU * SEG_ACC_STRIDE * sizeof(float);
         return launch_segf_pv<2048, 16, 32>(c, a, grid, lds, pv);
+    }
+    // the wrap-around energy on the matrix cores (wrap_kernels.hpp)
+    if (a.Qs && a.presum && c->d_Wb && c->wb_kt == 3 && pv == 13 && MU <= 8 && wrap_kt(c, c->gs_span == 1, MU) == 3) {
+        SegWArgs w;
+        w.f = a;
+        w.Wb = c->d_Wb;
+        w.Wexp = c->d_Wexp;
+        w.T = c->bank->T;
+        const size_t wlds = SegWCfg<13, 3>::lds_bytes();
+        hipLaunchKernelGGL((k_segw<13, 3>), dim3(grid), dim3(SegCfg<256>::BLOCK), wlds, c->stream, w);
+        HIPCHK(hipGetLastError());
+        return MFB_OK;
     }
     const size_t lds = SegCfg<256>::LDS_ELEMS * sizeof(cf) + (size_t)wpb * MU * SEG_ACC_STRIDE * sizeof(float);
     return launch_segf_pv<256, 8, 16>(c, a, grid, lds, pv);

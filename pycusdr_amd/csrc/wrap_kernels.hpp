@@ -1,0 +1,250 @@
+// wrap_kernels.hpp -- the 256-point filter-side search (segf_body, SUMQ = 2) with the wrap-around energy on the matrix cores.
+//
+// segf_body scores a (bin, segment) as  L sum_k |A[k]|^2 Q_b[k] - sum_f sum_{n in [V, L)} |v_{b,f}[n]|^2 : a Parseval total shared by the
+// bin's filters, minus the energy of the L - V outputs whose filter support wraps around the segment, which it gets from a product and a
+// pruned inverse transform per (bin, filter) on the vector ALUs.  Those outputs are short dot products over the segment's edges:
+//     v_{b,f}[V + n'] = N sum_{r < T} h_{b,f}[r] x_seg[(n' - r) mod L],   n' < L - V,   h_{b,f}[r] = tap_f[r] e^{+2 pi i s_b r / N}
+// (the Te - 1 = L - V rotation of segment_spectra_shifted: output V + n' reads samples n' - r, i.e. the last T - 1 and the first L - V of
+// the segment).  For one segment that is the matrix product  Toeplitz(x_seg)[L - V x T] . H_b[T x MU], in real form
+//     [Xr Xi] [[Hr, Hi], [-Hi, Hr]]   (K = 2T real rows, 2 MU <= 16 columns: one 16-column tile per bin, columns (filter, re / im)),
+// run here as v_mfma_f32_16x16x32_f16: row tile rt (16 outputs) x K-step kk (taps 16 kk ... 16 kk + 15, real and imaginary halves of the
+// window).  The Toeplitz block of (rt, kk) depends on rt - kk only, so a segment has RT + KT - 1 distinct A fragments.
+//
+// fp16 precision from a split: each operand is scaled by a power of two chosen from the data (the segment window: its largest
+// |component|; the bin's taps: theirs, host side) into [2^14, 2^15), and split into hi = fp16(v) and lo = fp16(v - hi).  Three products
+// lo.hi + hi.lo + hi.hi accumulate in fp32 (lo.lo, ~2^-22 relative, is dropped).  Because both scales are powers of two taken from the
+// data, scaling the input by 2^k leaves the fp16 operands and the accumulators bit for bit the same and the score scales exactly.
+//
+// Everything else is segf_body's: the XCD-aware rectangle of bins x slots, the unmixed forward transform (via the inverse one on swapped
+// samples), the Parseval total from pp = |A|^2 and Q, and the PRESUM store (row 0 carries the (bin, slot) sum, the other rows zero).
+// A bin's number depends on its own tables and the slot's samples only, summed in one fixed order: the same bits whichever bins share
+// the rectangle, whatever the grid or the batch.
+#pragma once
+#include "seg_kernels.hpp"
+
+typedef _Float16 seg_h8 __attribute__((ext_vector_type(8)));
+typedef float seg_f4 __attribute__((ext_vector_type(4)));
+
+struct SegWArgs {
+    SegFArgs f;          // the segf_body arguments (presum form: Qs set, rows counting equally)
+    const u32x4 *Wb;     // [Dtot][KT][2 = hi, lo][64 lanes]: B fragments, 8 fp16 per lane (filter_taps.hpp, wrap_taps_shifted)
+    const int *Wexp;     // [Dtot]: 2 log2(N) - 2 e_b, the bin's power of two of the wrap energy (e_b: its taps' scale)
+    int T;               // taps of the layout (T <= 16 KT)
+};
+
+template <int PV, int KT>
+struct SegWCfg {
+    static constexpr int L = 256, PPL = 16, NT = 16, CT = 4;
+    static constexpr int RT = PPL - PV;               // row tiles = wrap outputs / 16
+    static constexpr int ND = RT + KT - 1;            // distinct Toeplitz blocks of a segment
+    static constexpr int OFF = 16 * KT - 1;           // window index of sample offset 0: t = n' - r in [-(16 KT - 1), 16 RT - 1]
+    static constexpr int WSTR = 16 * (RT + KT);       // window elements per segment (one spare)
+    static_assert(RT >= 1 && RT + KT <= PPL, "the window is the first RT and the last KT register slots of a lane");
+    // one wave per SIMD: the four segments' fragments (160 registers) and two sets of B fragments stay in the register file (with the
+    // accumulation registers); two waves spill 61 registers.  The matrix loop is 27 k cycles per slot, the forward transform ~1 k.
+    static constexpr int WAVES = 1;
+    static constexpr size_t lds_bytes() {
+        return (size_t)SegCfg<256>::LDS_ELEMS * sizeof(cf) + (size_t)(SegCfg<256>::BLOCK / 64) * CT * WSTR * sizeof(cf);
+    }
+};
+
+template <int PV, int KT>
+DEVI void segw_body(const SegWArgs &w, const int blk) {
+    static_assert(MFB_FFT_FUSED, "the fused 256-point transform");
+    using Cfg = SegCfg<256>;
+    using WC = SegWCfg<PV, KT>;
+    constexpr int L = 256, NT = Cfg::NT, CT = Cfg::CT, PPL = Cfg::PPL, RT = WC::RT, ND = WC::ND, OFF = WC::OFF, WSTR = WC::WSTR;
+    static_assert(NT == WC::NT && CT == WC::CT && PPL == WC::PPL, "256-point geometry");
+    const SegFArgs &a = w.f;
+    extern __shared__ __attribute__((aligned(16))) cf lds[];
+    const int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lane = tid & 63;
+    const int g = lane % NT;
+    const int col = lane / NT;
+    cf *mylds = lds + wave * Cfg::LDS_PER_TEAM + col * padlen(L);
+    cf *wlds = lds + Cfg::LDS_ELEMS + wave * CT * WSTR;          // this wave's segment windows
+    F256Regs f256;
+    f256_setup(f256, a.twL + L, g);
+
+    // ---- this wave's rectangle (segf_body) ----
+    const int grp = blk % a.nsg;
+    const int u = (blk / a.nsg) * (Cfg::BLOCK / 64) + wave;
+    const int per_sc = a.nblk * a.nbc;
+    const int sc = u / per_sc, rest = u - sc * per_sc;
+    const int bk = rest / a.nbc, bc = rest - bk * a.nbc;
+    const int gs0 = a.gbins ? 0 : (int)((long long)grp * a.nslots / a.nsg);
+    const int glen = a.gbins ? a.nslots : (int)((long long)(grp + 1) * a.nslots / a.nsg) - gs0;
+    const int gb0 = a.gbins ? (int)((long long)grp * a.dper / a.nsg) : 0;
+    const int gblen = a.gbins ? (int)((long long)(grp + 1) * a.dper / a.nsg) - gb0 : a.dper;
+    const int s0 = __builtin_amdgcn_readfirstlane(a.slot0 + gs0 + sc * a.fs);
+    const int s1 = __builtin_amdgcn_readfirstlane(min(a.slot0 + gs0 + glen, s0 + a.fs));
+    const int jb0 = __builtin_amdgcn_readfirstlane(gb0 + bc * a.fb);
+    const int jb1 = __builtin_amdgcn_readfirstlane(min(gb0 + gblen, jb0 + a.fb));
+    if (sc >= a.nsc || s0 >= s1 || jb0 >= jb1 || bk >= a.nblk) return;           // (wave-uniform)
+
+    const unsigned nmask = (unsigned)a.N - 1u;
+    const auto xr = mk_rsrc(a.x + (size_t)bk * (size_t)a.xstride, (unsigned)a.N * sizeof(cf));
+    const auto qr = mk_rsrc(a.Qs, (unsigned)a.dper * (unsigned)(L * sizeof(float)));
+    const auto br = mk_rsrc(w.Wb, (unsigned)a.dper * (unsigned)(KT * 2 * 64 * 16));
+    auto load_q = [&](cf (&dst)[PPL / 2], int bin) {
+#pragma unroll
+        for (int jj = 0; jj < PPL / 4; ++jj)
+            buf_load_cf2(qr, g * 4 * (int)sizeof(float), bin * (L * (int)sizeof(float)) + jj * NT * 4 * (int)sizeof(float), dst[2 * jj], dst[2 * jj + 1]);
+    };
+    auto load_b = [&](seg_h8 (&hi)[KT], seg_h8 (&lo)[KT], int bin) {
+#pragma unroll
+        for (int kk = 0; kk < KT; ++kk) {
+            hi[kk] = __builtin_bit_cast(seg_h8, __builtin_amdgcn_raw_buffer_load_b128(br, lane * 16, (bin * KT + kk) * 2 * 1024, 0));
+            lo[kk] = __builtin_bit_cast(seg_h8, __builtin_amdgcn_raw_buffer_load_b128(br, lane * 16, ((bin * KT + kk) * 2 + 1) * 1024, 0));
+        }
+    };
+    constexpr int so_x = NT * (int)sizeof(cf);
+    const int T = w.T;
+    // fragment coordinates of this lane: A[row i16][k = 8 q + j], k < 16 the real halves of the window, k >= 16 the imaginary ones
+    const int i16 = lane & 15, q = lane >> 4;
+    const bool im_half = q >= 2;
+    const int qo = 8 * (q & 1);
+
+    for (int slot = s0; slot < s1; ++slot) {
+        cf v[PPL];
+        {
+            const unsigned e0 = (unsigned)(slot * CT + col) * (unsigned)a.V + (unsigned)g;
+            const unsigned last = (unsigned)(slot * CT + CT - 1) * (unsigned)a.V + (unsigned)L;      // wave-uniform
+            if (__builtin_amdgcn_readfirstlane(last <= (unsigned)a.N ? 1 : 0)) {
+                const int vo_x = (int)(e0 * sizeof(cf));
+#pragma unroll
+                for (int i = 0; i < PPL; ++i) {
+                    const cf t = buf_load_cf(xr, vo_x, i * so_x);
+                    v[i] = mkc(t.y, t.x);
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < PPL; ++i) {
+                    const cf t = buf_load_cf(xr, (int)(((e0 + (unsigned)(NT * i)) & nmask) * sizeof(cf)), 0);
+                    v[i] = mkc(t.y, t.x);
+                }
+            }
+        }
+        // ---- the segment's wrap window -> LDS: sample offsets t in [-(T - 1), L - V) (register slots < RT and >= PPL - KT), zero below
+        int ea;
+        {
+            cf *myw = wlds + col * WSTR;
+            float mx = 0.f;
+#pragma unroll
+            for (int i = 0; i < RT; ++i) {
+                const cf s = mkc(v[i].y, v[i].x);
+                myw[g + NT * i + OFF] = s;
+                mx = fmaxf(mx, fmaxf(fabsf(s.x), fabsf(s.y)));
+            }
+#pragma unroll
+            for (int i = PPL - KT; i < PPL; ++i) {
+                const int t = g + NT * i - L;
+                const cf s = t >= -(T - 1) ? mkc(v[i].y, v[i].x) : mkc(0.f, 0.f);
+                if (t + OFF >= 0) myw[t + OFF] = s;
+                mx = fmaxf(mx, fmaxf(fabsf(s.x), fabsf(s.y)));
+            }
+            // the segment's largest |component| (its 16 lanes): max is exact in any order
+#pragma unroll
+            for (int m = 1; m < NT; m <<= 1) mx = fmaxf(mx, __shfl_xor(mx, m));
+            int e;
+            (void)frexpf(mx, &e);             // mx = f 2^e, f in [0.5, 1): mx 2^(15 - e) in [2^14, 2^15)  (mx = 0: e = 0)
+            ea = 15 - e;
+        }
+        xsync<1>();
+        cf A[PPL];
+        {
+            auto keep = [&](int, cf val, auto, auto nu) { A[decltype(nu)::value / NT] = val; };
+            fft256_fused<0, PPL>(v, mylds, g, f256, keep);
+        }
+        cf pp[PPL / 2], qq[PPL / 2];
+#pragma unroll
+        for (int j = 0; j < PPL / 2; ++j) {
+            const cf p0 = A[2 * j] * A[2 * j], p1 = A[2 * j + 1] * A[2 * j + 1];
+            pp[j] = mkc(p0.x + p0.y, p1.x + p1.y);
+        }
+        load_q(qq, jb0);
+        seg_h8 bhi[KT], blo[KT];
+        load_b(bhi, blo, jb0);
+        // ---- the A fragments of the CT segments: ND Toeplitz blocks each, scaled by 2^ea of the segment and split into hi / lo ----
+        seg_h8 ahi[CT][ND], alo[CT][ND];
+        int eseg[CT];
+#pragma unroll
+        for (int c = 0; c < CT; ++c) {
+            eseg[c] = __builtin_amdgcn_readlane(ea, NT * c);
+            const cf *wc = wlds + c * WSTR;
+#pragma unroll
+            for (int di = 0; di < ND; ++di) {
+                const int base = 16 * (di - (KT - 1)) + i16 - qo + OFF;      // element j: offset t = base - OFF - j
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const cf s = wc[base - j];
+                    const float sv = __builtin_ldexpf(im_half ? s.y : s.x, eseg[c]);
+                    const _Float16 h = (_Float16)sv;
+                    ahi[c][di][j] = h;
+                    alo[c][di][j] = (_Float16)(sv - (float)h);
+                }
+            }
+        }
+        xsync<1>();       // the windows are rewritten by the next slot
+
+        for (int jb = jb0; jb < jb1; ++jb) {
+            // the Parseval total of the bin's filters (segf_body)
+            cf t2[2] = {mkc(0.f, 0.f), mkc(0.f, 0.f)};
+#pragma unroll
+            for (int j = 0; j < PPL / 2; ++j) t2[j & 1] = __builtin_elementwise_fma(pp[j], qq[j], t2[j & 1]);
+            const float tot = (t2[0].x + t2[0].y) + (t2[1].x + t2[1].y);
+            if (jb + 1 < jb1) load_q(qq, jb + 1);
+            const int wexp = w.Wexp[jb];
+            seg_h8 nhi[KT], nlo[KT];            // the next bin's B fragments land while this bin's products run
+            if (jb + 1 < jb1) load_b(nhi, nlo, jb + 1);
+            // the wrap energy: per segment, RT row tiles x KT K-steps x (lo.hi, hi.lo, hi.hi), squared and summed in a fixed order
+            float wacc = 0.f;
+#pragma unroll
+            for (int c = 0; c < CT; ++c) {
+                float sq[RT];
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) {
+                    seg_f4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int kk = 0; kk < KT; ++kk) {
+                        const int di = rt - kk + KT - 1;
+                        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo[c][di], bhi[kk], acc, 0, 0, 0);
+                        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi[c][di], blo[kk], acc, 0, 0, 0);
+                        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi[c][di], bhi[kk], acc, 0, 0, 0);
+                    }
+                    sq[rt] = __builtin_fmaf(acc.x, acc.x, acc.y * acc.y) + __builtin_fmaf(acc.z, acc.z, acc.w * acc.w);
+                }
+                float s = sq[0];
+#pragma unroll
+                for (int rt = 1; rt < RT; ++rt) s += sq[rt];
+                wacc += __builtin_ldexpf(s, wexp - 2 * eseg[c]);
+            }
+            if (jb + 1 < jb1) {
+#pragma unroll
+                for (int kk = 0; kk < KT; ++kk) {
+                    bhi[kk] = nhi[kk];
+                    blo[kk] = nlo[kk];
+                }
+            }
+            // the wave's 64 values in segf_body's fixed order: quads, the four quads of a row, the four rows
+            float sv = __builtin_fmaf((float)L, tot, -wacc);
+            sv += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(sv), 0xB1, 0xF, 0xF, true));       // quad_perm [1,0,3,2]
+            sv += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(sv), 0x4E, 0xF, 0xF, true));       // quad_perm [2,3,0,1]
+            sv += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(sv), 0x124, 0xF, 0xF, true));      // row_ror:4
+            sv += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(sv), 0x128, 0xF, 0xF, true));      // row_ror:8
+            const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sv), 0));
+            const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sv), 16));
+            const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sv), 32));
+            const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sv), 48));
+            const float total = (r0 + r1) + (r2 + r3);
+            if (lane < a.MU)
+                a.partials[((size_t)(a.part_row0 + bk * a.dper + jb) * a.MU + lane) * a.parts + slot] = lane == 0 ? total * a.scale : 0.f;
+        }
+    }
+}
+template <int PV, int KT>
+__global__ void __launch_bounds__(SegCfg<256>::BLOCK) __attribute__((amdgpu_waves_per_eu(SegWCfg<PV, KT>::WAVES, SegWCfg<PV, KT>::WAVES)))
+k_segw(SegWArgs w) {
+    segw_body<PV, KT>(w, (int)blockIdx.x);
+}

@@ -1,0 +1,64 @@
+"""Child of tests/test_gpu_wrap_mfma.py: the doppSum tables of a set of adversarial blocks in THIS process's form of the 256-point
+search (MFB_SEG_WRAP_MFMA in the environment is read once per process).  Writes an .npz with, per input, the scores, the block's
+spectrum (for the oracle) and the pick.
+usage: wrap_child.py <protocol> <log2N> <D> <out.npz>"""
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+from pycusdr_amd import config as cfg, signals as sg                                  # noqa: E402
+from pycusdr_amd.demodulator.demodulator_base import doppler_bin_table                 # noqa: E402
+from pycusdr_amd.mfbank import MFBank                                                  # noqa: E402
+from pycusdr_amd.protocol import loadProtocol                                          # noqa: E402
+
+
+def inputs(N, shifts, V):
+    """name -> complex64 block: a stream, full-scale bursts shorter than a segment on a -60 dB floor at several phases of the wrap
+    window, pure tones on a bin and between two bins, a block that is zero except for one segment, and a peak-clipped stream."""
+    rs = np.random.RandomState(7)
+    out = {}
+    out['stream'] = sg.s1_stream(1, N, 1 << 10, 'GMSK', snr_db=8.0, seed=41)[:N]
+    floor = 1e-3 * (rs.standard_normal(N) + 1j * rs.standard_normal(N)) / np.sqrt(2)
+    seg0 = 37 * V                                         # a segment start; its wrap window is [seg0 - 47, seg0 + 48)
+    for ph in (-60, -40, -20, 0, 20, 40):
+        x = floor.copy()
+        b0 = seg0 + ph
+        x[b0:b0 + 24] += np.exp(2j * np.pi * rs.random_sample(24))
+        out[f'burst{ph:+d}'] = x
+    n = np.arange(N)
+    s_on = int(shifts[len(shifts) // 3])
+    out['tone_on_bin'] = np.exp(2j * np.pi * s_on * n / N) + floor
+    s_mid = 0.5 * (int(shifts[len(shifts) // 2]) + int(shifts[len(shifts) // 2 + 1]))
+    out['tone_between_bins'] = np.exp(2j * np.pi * s_mid * n / N) + floor
+    x = np.zeros(N, dtype=np.complex128)
+    x[seg0:seg0 + 256] = rs.standard_normal(256) + 1j * rs.standard_normal(256)
+    out['one_segment'] = x
+    x = out['stream'].astype(np.complex128) * 3.0
+    x[5000:5400] += 40.0 * np.exp(2j * np.pi * rs.random_sample(400))             # an interference burst
+    mag = np.abs(x)
+    lim = 4.0 * mag.mean()
+    out['clipped'] = np.where(mag > lim, x * (lim / np.maximum(mag, 1e-30)), x)
+    return {k: np.asarray(v, dtype=np.complex64) for k, v in out.items()}
+
+
+name, log2N, D, out = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), sys.argv[4]
+N = 1 << log2N
+conf, sps, ms = cfg.bench_config(name, blockSize=log2N, doppCarrierSteps=D), 16, (5 if name == 'bench_BPSK' else 3)
+_, _, shifts, _ = doppler_bin_table(conf['Radios']['Rx']['UHF-H'], conf['Radios']['rangeRateMax'], N)
+M, masks = loadProtocol(name)(conf=conf).get_filter(N, sps, ms)
+bank = MFBank(log2N, D, M)
+bank.set_filters(masks)
+bank.set_shifts(shifts)
+V = bank.get_search_path()['valid_per_segment']
+res = {'shifts': np.asarray(shifts), 'filter_side': int(bank.get_search_info()['filter_side']), 'log2L': bank.get_search_path()['log2L']}
+for k, x in inputs(N, shifts, V).items():
+    bank.upload(x)
+    pick = bank.find_carrier()
+    res[f'scores_{k}'] = bank.get_scores()
+    res[f'X_{k}'] = bank.get_spectrum()
+    res[f'pick_{k}'] = np.asarray(pick, dtype=np.float64)
+np.savez(out, **res)
+bank.close()
