@@ -1482,7 +1482,9 @@ static bool wrap_mfma_enabled() {
 }
 // K-steps of the matrix-core form of the search, 0 where it does not run: 256-point segments, SUM_ALL searches whose rows k_finalize
 // counts equally (segf_body's SUMQ = 2 form), one 16-column tile per bin (MU <= 8) and the instantiated shape -- 13 valid register
-// slots, 33 ... 48 taps (the 8-filter GMSK banks).  The BPSK bank (80 taps, 16 rows) keeps segf_body.
+// slots and at most three K-steps of 16 taps, which is 34 ... 48 taps (the 8-filter GMSK / FSK banks): seg_valid leaves 33 taps 14 valid
+// slots, and 49 taps, which still have 13, need a fourth K-step.  The BPSK bank (80 taps, 16 rows) keeps segf_body.
+// (tests/seg_model.py, wrap_form, restates this; tests/test_gpu_wrap_sweep.py holds the device to it at 33 | 34 and 48 | 49 taps.)
 // Blocks of 2^18 samples and more only: a single small block (2^15 ... 2^17 samples x 64 bins) gets one-bin rectangles from fsm_plan, and
 // there the forward transform and the A fragments, built per (slot, bin) at one wave per SIMD, made the search slower than segf_body
 // (bench.py --full, recv_b1_n17_d64: 607 against 763 Msamples/s).  The choice depends on the bank and the block length alone -- never on

@@ -9,6 +9,9 @@
 //     [Xr Xi] [[Hr, Hi], [-Hi, Hr]]   (K = 2T real rows, 2 MU <= 16 columns: one 16-column tile per bin, columns (filter, re / im)),
 // run here as v_mfma_f32_16x16x32_f16: row tile rt (16 outputs) x K-step kk (taps 16 kk ... 16 kk + 15, real and imaginary halves of the
 // window).  The Toeplitz block of (rt, kk) depends on rt - kk only, so a segment has RT + KT - 1 distinct A fragments.
+// The instantiated shape (PV = 13 valid register slots, KT = 3) serves banks of 34 ... 48 taps: with 33 taps a segment has 14 valid
+// slots, 49 taps need a fourth K-step (mfbank.hip, wrap_kt).  Taps 16 KT - 1 down to T are zero rows of the B fragments, and the
+// window is zeroed below offset -(T - 1), so that the segment's scale comes from the samples the product reads.
 //
 // fp16 precision from a split: each operand is scaled by a power of two chosen from the data (the segment window: its largest
 // |component|; the bin's taps: theirs, host side) into [2^14, 2^15), and split into hi = fp16(v) and lo = fp16(v - hi).  Three products

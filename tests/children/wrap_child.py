@@ -1,7 +1,7 @@
-"""Child of tests/test_gpu_wrap_mfma.py: the doppSum tables of a set of adversarial blocks in THIS process's form of the 256-point
-search (MFB_SEG_WRAP_MFMA in the environment is read once per process).  Writes an .npz with, per input, the scores, the block's
-spectrum (for the oracle) and the pick.
-usage: wrap_child.py <protocol> <log2N> <D> <out.npz>"""
+"""Child of tests/test_gpu_wrap_mfma.py and tests/test_gpu_wrap_sweep.py: the doppSum tables of a set of adversarial blocks in THIS
+process's form of the 256-point search (MFB_SEG_WRAP_MFMA in the environment is read once per process).  Writes an .npz with, per input, the scores, the block's
+spectrum (for the oracle) and the pick; with ``span`` also the scores and picks of the span basis on the same handle.
+usage: wrap_child.py <protocol> <log2N> <D> <out.npz> [span]"""
 import os
 import sys
 
@@ -44,21 +44,40 @@ def inputs(N, shifts, V):
     return {k: np.asarray(v, dtype=np.complex64) for k, v in out.items()}
 
 
-name, log2N, D, out = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), sys.argv[4]
-N = 1 << log2N
-conf, sps, ms = cfg.bench_config(name, blockSize=log2N, doppCarrierSteps=D), 16, (5 if name == 'bench_BPSK' else 3)
-_, _, shifts, _ = doppler_bin_table(conf['Radios']['Rx']['UHF-H'], conf['Radios']['rangeRateMax'], N)
-M, masks = loadProtocol(name)(conf=conf).get_filter(N, sps, ms)
-bank = MFBank(log2N, D, M)
-bank.set_filters(masks)
-bank.set_shifts(shifts)
-V = bank.get_search_path()['valid_per_segment']
-res = {'shifts': np.asarray(shifts), 'filter_side': int(bank.get_search_info()['filter_side']), 'log2L': bank.get_search_path()['log2L']}
-for k, x in inputs(N, shifts, V).items():
-    bank.upload(x)
-    pick = bank.find_carrier()
-    res[f'scores_{k}'] = bank.get_scores()
-    res[f'X_{k}'] = bank.get_spectrum()
-    res[f'pick_{k}'] = np.asarray(pick, dtype=np.float64)
-np.savez(out, **res)
-bank.close()
+def setup(name, log2N, D):
+    """(handle with the protocol's bank and bin table, masks, shifts)"""
+    N = 1 << log2N
+    conf, sps, ms = cfg.bench_config(name, blockSize=log2N, doppCarrierSteps=D), 16, (5 if name == 'bench_BPSK' else 3)
+    _, _, shifts, _ = doppler_bin_table(conf['Radios']['Rx']['UHF-H'], conf['Radios']['rangeRateMax'], N)
+    M, masks = loadProtocol(name)(conf=conf).get_filter(N, sps, ms)
+    bank = MFBank(log2N, D, M)
+    bank.set_filters(masks)
+    bank.set_shifts(shifts)
+    return bank, masks, shifts
+
+
+def main(name, log2N, D, out, span=False):
+    bank, _, shifts = setup(name, log2N, D)
+    V = bank.get_search_path()['valid_per_segment']
+    res = {'shifts': np.asarray(shifts), 'filter_side': int(bank.get_search_info()['filter_side']), 'log2L': bank.get_search_path()['log2L'],
+           'taps': bank.get_search_path()['taps'], 'rows': bank.get_search_basis()[1]}
+    for k, x in inputs(1 << log2N, shifts, V).items():
+        bank.upload(x)
+        pick = bank.find_carrier()
+        res[f'scores_{k}'] = bank.get_scores()
+        res[f'X_{k}'] = bank.get_spectrum()
+        res[f'pick_{k}'] = np.asarray(pick, dtype=np.float64)
+    if span:                  # ... and once more with the span basis on the same handle
+        bank.set_search_basis('span')
+        res['span_rows'] = bank.get_search_basis()[1]
+        res['span_filter_side'] = int(bank.get_search_info()['filter_side'])
+        for k, x in inputs(1 << log2N, shifts, V).items():
+            bank.upload(x)
+            res[f'spanpick_{k}'] = np.asarray(bank.find_carrier(), dtype=np.float64)
+            res[f'spanscores_{k}'] = bank.get_scores()
+    np.savez(out, **res)
+    bank.close()
+
+
+if __name__ == '__main__':
+    main(sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), sys.argv[4], span=len(sys.argv) > 5 and sys.argv[5] == 'span')

@@ -86,3 +86,24 @@ def segment_xcorr(x, masks, shift, L, thr=1e-13):
         nv = min(V, N - b0)
         y[:, (b0 + np.arange(nv) + off) % N] = v[:, :nv]
     return y
+
+
+def seg_valid(T, L=256, NT=16):
+    """Valid outputs per complete L-point segment (mfbank.hip, seg_valid): whole register slots of NT outputs, 0 when fewer than
+    half of the segment's slots would be valid."""
+    pv = (L - T + 1) // NT
+    return pv * NT if pv >= (L // NT) // 2 else 0
+
+
+def wrap_form(N, counts, T, sum_all, span_rank=None, log2L=8):
+    """Which form of the filter-side search scores a block: 'matrix' (wrap_kernels.hpp, k_segw) or 'vector' (segf_body).  Restates
+    wrap_kt of mfbank.hip as a function of the block length N, how often each unique filter of the bank counts (``counts``: one entry
+    per filter the search transforms; exact copies and exact negatives of an earlier filter count with it), the taps T of the bank's
+    common support, SUM_ALL, and -- for the span basis -- the rank of the bank (None: the default basis, the unique filters)."""
+    rows = len(counts) if span_rank is None else span_rank
+    equal = span_rank is not None or all(c == counts[0] for c in counts)       # the span basis counts every row once
+    if log2L != 8 or N < (1 << 18) or not sum_all or rows > 8 or not equal:
+        return 'vector'
+    if seg_valid(T) != 13 * 16:              # the instantiated shape: 13 valid register slots -- 34 ... 49 taps
+        return 'vector'
+    return 'matrix' if 32 < T <= 48 else 'vector'

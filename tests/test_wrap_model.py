@@ -145,3 +145,73 @@ def test_power_of_two_linearity():
     e1 = wrap_via_mfma_model(x, taps, N, 256, V, 3)
     e4 = wrap_via_mfma_model(4 * x, taps, N, 256, V, 3)
     assert e4 == 16 * e1
+
+
+def test_geometry_at_the_edges_of_the_matrix_form():
+    """13 valid register slots (V = 208) from 34 to 49 taps: 33 taps leave 14, and 49 taps are one more than three K-steps hold."""
+    from seg_model import seg_valid, wrap_form
+    assert [_geometry(T)[0] for T in (32, 33, 34, 48, 49, 50)] == [224, 224, 208, 208, 208, 192]
+    assert all(seg_valid(T) == _geometry(T)[0] for T in range(1, 130))
+    N, eight = 1 << 18, [1] * 8
+    assert [wrap_form(N, eight, T, True) for T in (32, 33, 34, 48, 49, 50)] == ['vector', 'vector', 'matrix', 'matrix', 'vector', 'vector']
+    assert wrap_form(N >> 1, eight, 48, True) == 'vector' and wrap_form(N << 2, eight, 48, True) == 'matrix'
+    assert wrap_form(N, eight, 48, False) == 'vector' and wrap_form(N, [1] * 9, 48, True) == 'vector'
+    assert wrap_form(N, [2, 1, 1], 48, True) == 'vector' and wrap_form(N, [2, 2, 2, 2], 48, True) == 'matrix'
+    assert wrap_form(N, [2, 1, 1], 48, True, span_rank=3) == 'matrix' and wrap_form(N, [1] * 16, 48, True, span_rank=8) == 'matrix'
+    assert wrap_form(N, [1] * 16, 48, True, span_rank=9) == 'vector' and wrap_form(N, eight, 48, True, log2L=11) == 'vector'
+
+
+@pytest.mark.parametrize('T', [34, 40, 47, 48])
+@pytest.mark.parametrize('rows', [1, 3, 6, 8])
+def test_split_fp16_gemm_on_synthetic_banks(T, rows):
+    """Where the device sweep goes (tests/tools/fuzz_wrap.py): complex normal taps of 34 ... 48 taps (three K-steps, the last one partly
+    zero rows) in 1 ... 8 rows (unused tile columns), scaled over eight decades; noise segments, segments with one full-scale sample
+    on a 1e-4 floor, segments scaled over thirty decades.  The wrap energy stays within the same 5e-7 of the fp64 transform."""
+    N, L, KT = 1 << 18, 256, 3
+    V, Te = _geometry(T)
+    assert V == 208 and 16 * (KT - 1) < T <= 16 * KT
+    rs = np.random.RandomState(1000 * T + rows)
+    worst = {}
+    for trial in range(3):
+        taps = 10 ** rs.uniform(-6, 2) * (rs.standard_normal((rows, T)) + 1j * rs.standard_normal((rows, T)))
+        s = int(rs.randint(0, N))
+        hb = taps * np.exp(2j * np.pi * ((s * np.arange(T)) % N) / N)[None, :]
+        noise = rs.standard_normal(L) + 1j * rs.standard_normal(L)
+        spike = 1e-4 * (rs.standard_normal(L) + 1j * rs.standard_normal(L))
+        spike[rs.randint(0, L)] = np.exp(2j * np.pi * rs.random_sample())
+        edge = 1e-4 * (rs.standard_normal(L) + 1j * rs.standard_normal(L))
+        edge[(rs.randint(-(T - 1), L - V)) % L] = np.exp(2j * np.pi * rs.random_sample())     # the full-scale sample inside the window
+        scaled = 10 ** rs.uniform(-15, 15) * (rs.standard_normal(L) + 1j * rs.standard_normal(L))
+        for kind, x_seg in (('noise', noise), ('spike', spike), ('spike', edge), ('scaled', scaled)):
+            ref = wrap_via_transform(x_seg, hb, N, L, Te, V)
+            got = wrap_via_mfma_model(x_seg, hb, N, L, V, KT)
+            worst[kind] = max(worst.get(kind, 0.0), abs(got - ref) / ref)
+    assert max(worst.values()) <= 5e-7, worst
+
+
+def test_the_device_sweep_reaches_the_matrix_form():
+    """tests/tools/fuzz_wrap.py's seeded draw, by the predicate alone: at least half of the cases take the matrix form, the four edge
+    tap counts decide the form of the first four cases by themselves, and the corners the sweep is there for occur."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'tools'))
+    import fuzz_wrap as fw
+    cs = fw.draw()
+    assert len(cs) == fw.CASES >= 25
+    assert [(c['T'], fw.expected(c, 'filters'), fw.expected(c, 'span')) for c in cs[:4]] == \
+        [(33, 'vector', 'vector'), (34, 'matrix', 'matrix'), (48, 'matrix', 'matrix'), (49, 'vector', 'vector')]
+    matrix = [c for c in cs if any(fw.expected(c, b) == 'matrix' for b in fw.bases(c))]
+    assert 2 * len(matrix) >= len(cs)
+    assert 2 * sum(fw.expected(c, 'filters') == 'matrix' for c in cs) >= len(matrix)
+    assert {c['log2N'] for c in cs} == {18, 19, 20} and sum(c['log2N'] == 20 for c in cs) == 1
+    assert sum(c['D'] >= 200 for c in cs) == 1 and all(1 <= c['D'] <= 40 for c in cs if c['D'] < 200)
+    assert {c['M'] for c in cs} == {1, 2, 3, 5, 8, 16} and {c['dup'] for c in cs} == {'none', 'neg', 'twice'}
+    assert {c['kind'] for c in cs} == {'noise', 'scaled', 'segment', 'spikes'} and {c['doff'] for c in matrix} == {0, 1}
+    assert not all(c['sum_all'] for c in cs) and all(30 <= c['T'] <= 52 for c in cs)
+    assert sum(c['start'] + c['T'] > (1 << c['log2N']) for c in matrix) >= 2            # taps that wrap around the end of the block
+    # the default basis on the vector form and the span basis of the same handle on the matrix form: more than 8 unique filters, and
+    # rows that do not count equally
+    split = [c for c in cs if c['sum_all'] and (fw.expected(c, 'filters'), fw.expected(c, 'span')) == ('vector', 'matrix')]
+    assert any(len(fw.counts(c)) > 8 for c in split) and any(c['dup'] == 'neg' for c in split)
+    rows = {len(fw.counts(c)) for c in cs if fw.expected(c, 'filters') == 'matrix'} | {c['rank'] for c in cs if c['sum_all'] and fw.expected(c, 'span') == 'matrix'}
+    assert {1, 2, 3, 5, 8} <= rows
