@@ -317,7 +317,7 @@ int mfb_set_batch_overlap(mfb_ctx *ctx, int on);
 int mfb_receive_blocks_end(mfb_ctx *ctx, int slot, mfb_block_result *results, int32_t *sym, int32_t *centres, float *magnitude,
                            int symbol_stride, float *bands_c64);
 /* The integer stages behind the symbol decisions, on the device, for the blocks of a batch (mfb_receive_blocks_*; UHF search
- * mode).  Replaces, block by block and bit for bit:
+ * mode and S-band fixed-shift mode alike).  Replaces, block by block and bit for bit:
  *   A12  extractBits (DB:1012-1023: bits = bitLUT[sym]) -- lut_mode 1, lut = uint8[lut_rows] of 0 / 1 -- or extractBitsNRZs
  *        (DB:1026-1051) -- lut_mode 2, lut = int32[lut_rows][2][lut_successors] = symbolLUT[sym][is-one | is-zero][successors],
  *        impossible transitions -> 0 and counted (lut_rows <= 256 resp. lut_rows * 2 * lut_successors <= 2048: MFB_ERR_ARG beyond);
@@ -335,11 +335,16 @@ int mfb_receive_blocks_end(mfb_ctx *ctx, int slot, mfb_block_result *results, in
  * overlap_offset + 1 bits inside it: posSymEnd, DB:977-979) and the last bits_overlap bits of the stream -- stays on the device
  * from batch to batch; mfb_stream_seed sets it from the host's (start of a stream, after an irregular block, after blocks
  * that went another way).  Batches of more than 64 blocks run without the stages (their records carry layout.stream_stages = 0: the
- * host does A12 ... A14 for them): one workgroup chains the kept-bit counts of a batch's blocks through one wave, 64 lanes.  So do
- * batches at a FIXED shift (MFB_BLOCK_FIXED_SHIFT, the S-band back end demodulator/STX.py:8-24): that back end tags the symbols
- * next to clipped interference peaks in the trust bytes (DB:670-707, 830-837) from the block's clipped-sample indices -- on the
- * host, also when the device clips the block (mfb_set_peak_clip hands the indices out) -- so the bits of such a block are
- * finished on the host.  p == NULL switches the stages off. */
+ * host does A12 ... A14 for them): one workgroup chains the kept-bit counts of a batch's blocks through one wave, 64 lanes.
+ * Batches at a FIXED shift (MFB_BLOCK_FIXED_SHIFT, the S-band back end demodulator/STX.py:8-24) run the same stages under the
+ * same conditions.  That back end also tags the symbols next to clipped interference peaks in the trust bytes (DB:830-837): with
+ * the peak clip on (mfb_set_peak_clip), a kernel behind A13 sets the kept trust byte of every symbol whose full centre c has a
+ * clipped-sample index p of its block with lo(p) <= c < hi(p) -- s = ceil(spSym) of the record (float64, unclamped), hi(p) =
+ * min(p + 2 s + 1, N), lo(p) = p - 2 s, or max(p - 2 s + N, 0) when that is negative: numpy's slice marks[p - 2s : p + 2s + 1] --
+ * to 254 (int8 -2), from the flight's own clip indices; the record's scalars say so (BlockScalars.clip_tag = 1, clip_count = the
+ * block's number of indices).  Those two fields are written only in such batches (fixed shift, stages, peak clip on): in any
+ * other record they hold whatever an earlier flight left there and mean nothing.  Without the peak clip there is nothing to tag.  An irregular block (a13_status 0) is tagged by
+ * the host with the rest of its stages.  p == NULL switches the stages off. */
 typedef struct mfb_stream_params {
     int32_t overlap_samples;     /* 2^overlap (config GPU.overlap) */
     int32_t overlap_offset;      /* symbol_check_overlap_offset (DB:19-26): 20 */

@@ -2346,6 +2346,13 @@ static int block_enqueue_p2(mfb_ctx *c, const mfb_block_params *p, const BlkBufs
         sa.carry_out = c->d_carry[1 - bb.parity];
         hipLaunchKernelGGL(k_stream_align, dim3(nb), dim3(STREAM_ALIGN_THREADS), 0, c->stream, sa);
         HIPCHK(hipGetLastError());
+        if (p->mode == MFB_BLOCK_FIXED_SHIFT && bb.clip) {
+            // S-band: the clipped-peak tags in the kept trust bytes (DB:830-837), from the flight's own clip indices
+            hipLaunchKernelGGL(k_stream_tag, dim3(nb, (nthreads + STREAM_TAG_THREADS - 1) / STREAM_TAG_THREADS), dim3(STREAM_TAG_THREADS), 0,
+                               c->stream, sa, (const int32_t *)bb.clip->a.idx,
+                               (const int32_t *)bb.clip->a.head, CLIP_HEAD);
+            HIPCHK(hipGetLastError());
+        }
         if (sa.K > 0) {
             int Tmax = 0;
             for (int t = 0; t < sa.K; ++t) Tmax = sa.T[t] > Tmax ? sa.T[t] : Tmax;
@@ -2806,7 +2813,8 @@ extern "C" int mfb_receive_blocks_begin(mfb_ctx *c, const mfb_block_params *p, i
     int nthreads = p->k_offset + p->k_len + 1;
     if (nthreads > capacity) nthreads = capacity;
     const size_t core = blkout_bytes(bcap, nthreads);
-    const bool stages = c->st_on && p->mode == MFB_BLOCK_SEARCH && nblocks <= 64;
+    // (fixed shift: the S-band back end; with its peak clip on, k_stream_tag adds the clipped-peak tags behind the alignment)
+    const bool stages = c->st_on && nblocks <= 64;
     // stream-stage outputs behind the core record: kept bits | kept centres | trust bytes (uint8[nthreads] each), the block's
     // tail (post, end), the sync hits (idx | score per template)
     const size_t ext_bytes = 3 * align16((size_t)nthreads) + STREAM_POST_MAX + STREAM_END_MAX +

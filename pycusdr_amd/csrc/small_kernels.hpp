@@ -384,7 +384,9 @@ struct BlockScalars {
     int sync_valid;        // 1: sync_count / the hit lists are those of the last numBitsOverlap bits before the block + its bits
     int sync_count[2];
     int a13_prev_npost;    // bits the previous block left behind its window (a13_status 2: the operand numpy could not broadcast)
-    int pad_;
+    // fixed-shift batches with the stages and the peak clip on (k_stream_tag writes both; in any other record they are stale):
+    int clip_tag;          // 1 = the kept trust bytes carry the clipped-peak tags (DB:830-837)
+    int clip_count;        // the block's number of clipped-peak indices
 };
 static_assert(sizeof(BlockScalars) == 168 && sizeof(BlockScalars) <= 256, "BlockScalars: the record head (the Python side mirrors this layout)");
 

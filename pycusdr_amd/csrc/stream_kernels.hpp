@@ -706,3 +706,76 @@ __global__ void __launch_bounds__(STREAM_SEARCH_THREADS) k_stream_search(StreamA
         }
     }
 }
+
+// ---- the clipped-peak tag of a fixed-shift (S-band) batch: behind k_stream_align, in front of the search ----------------------
+// The reference marks 2 s + 1 samples around every clipped-peak index p (clippedPeakIPure, ascending; s = ceil(spSym) of the
+// block, float64, unclamped) and sets the trust byte of every kept symbol whose centre is marked to int8 -2 (DB:830-837):
+//     marks[p - 2 s : p + 2 s + 1] = 1;  trustSymbolWin[marks[centresWin]] = -2
+// with numpy's slice bounds: hi(p) = min(p + 2 s + 1, N); lo(p) = p - 2 s when >= 0, else max(p - 2 s + N, 0) -- so a peak
+// below 2 s tags only the block's end, and only when 4 s + 1 > N.  A centre c is marked iff some p has lo(p) <= c < hi(p), i.e.
+//     p >= 2 s:  c - 2 s <= p <= c + 2 s                          (first p >= max(c - 2 s, 2 s), a binary search)
+//     p <  2 s:  max(c - 2 s, 0) <= p <= min(c + 2 s - N, 2 s - 1)  (first p >= max(c - 2 s, 0))
+// All in 64-bit (s can be as large as N).  One in [-N, 0) reads marks[c + N] as numpy does.  A kept centre outside [-N, N) --
+// numpy's IndexError -- hands the block to the host; that check is defensive: k_stream_align keeps the symbols whose centres lie
+// between about ov/2 and N - ov/2 (one symbol more at a -1 slip), so no shipped case reaches it.
+// Grid (block, slice of 256 kept symbols): every thread tests one symbol; workgroup (b, 0) alone also sweeps the block's whole
+// window for that range check and writes the record's clip_tag / clip_count (and a13_status when the check fails) -- the other
+// slices only set trust bytes, which the host ignores for a block it takes over.
+#define STREAM_TAG_THREADS 256
+DEVI int tag_lower_bound(const int32_t *P, int n, long long v) {     // first i with P[i] >= v (n: none)
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((long long)P[mid] < v) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+__global__ void __launch_bounds__(STREAM_TAG_THREADS) k_stream_tag(StreamArgs a, const int32_t *clip_idx, const int32_t *clip_head,
+                                                                   int head_stride) {
+    __shared__ int s_bad;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    uint8_t *rec = a.rec0 + (size_t)b * a.rec;
+    BlockScalars *sc = reinterpret_cast<BlockScalars *>(rec);
+    const int status = sc->a13_status, start = sc->a13_start, nwin = sc->a13_nwin;
+    const int np = clip_head[(size_t)b * head_stride];
+    const double sp = sc->spSym;
+    const long long N = a.N;
+    const int *cen = reinterpret_cast<const int *>(rec + a.off_cen);
+    const bool dev = status != A13_HOST;
+    const int j = (int)blockIdx.y * STREAM_TAG_THREADS + tid;
+    if (dev && np > 0 && j < nwin) {
+        long long c = cen[start + j];
+        if (c >= -N && c < N) {
+            if (c < 0) c += N;
+            const int32_t *P = clip_idx + (size_t)b * a.N;
+            const long long s2 = 2 * (long long)ceil(sp);
+            bool hit = false;
+            int q = tag_lower_bound(P, np, c - s2 > s2 ? c - s2 : s2);
+            if (q < np && (long long)P[q] <= c + s2) hit = true;
+            const long long top = c + s2 - N < s2 - 1 ? c + s2 - N : s2 - 1;
+            if (!hit && top >= 0) {
+                q = tag_lower_bound(P, np, c - s2 > 0 ? c - s2 : 0);
+                if (q < np && (long long)P[q] <= top) hit = true;
+            }
+            if (hit) rec[a.off_trust + j] = (uint8_t)254;        // int8 -2
+        }
+    }
+    if (blockIdx.y != 0) return;
+    if (tid == 0) s_bad = 0;
+    __syncthreads();
+    if (dev && np > 0) {
+        bool bad = false;
+        for (int x = tid; x < nwin; x += STREAM_TAG_THREADS) {
+            const long long c = cen[start + x];
+            bad = bad || c < -N || c >= N;
+        }
+        if (bad) s_bad = 1;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        if (dev && s_bad) sc->a13_status = A13_HOST;
+        sc->clip_tag = dev && !s_bad ? 1 : 0;
+        sc->clip_count = np;
+    }
+}

@@ -379,10 +379,11 @@ class Demodulator:
         searches on the stream without a stash (DEC:89-113).  Returns False (and leaves them on the host) where a precondition
         does not hold: a bit LUT that is not plain 0 / 1, a decoder preprocessor that is not the identity, templates with
         other taps than -1 / 0 / +1, more overlap bits than the device keeps.  Results are the host code's, bit for bit; blocks
-        the device flags as irregular go through the host code."""
+        the device flags as irregular go through the host code.  The STX back end takes them with the device clip (its only
+        batches): the device then also tags the kept symbols next to clipped peaks (DB:830-837)."""
         from ..protocol.protocolBase import ProtocolBase
         self._stages = False
-        if not self._one_call or self.backend != 'UHF' or self.overlapOffset + 1 > 32:
+        if not self._one_call or (self.backend != 'UHF' and not self._device_clip) or self.overlapOffset + 1 > 32:
             return False
         kw = {}
         if self._bitLUT_u8 is not None and len(self._bitLUT_u8) <= 256:
@@ -429,9 +430,12 @@ class Demodulator:
         the per-block results later: the receive loop queues the next window's copies in between)."""
         return self.bank.end_blocks_record(slot)
 
-    def endBlocks(self, slot, record=None):
+    def endBlocks(self, slot, record=None, clips=True):
         """One ``((freqOffset_Hz, metric, clippedPeakIdx, SNR_dB), device record)`` per block of the batch begun in ``slot``,
-        in stream order: what ``endBlock`` + ``demodulateDevice`` return block by block."""
+        in stream order: what ``endBlock`` + ``demodulateDevice`` return block by block.  ``clips=False`` (the receive loop,
+        which reads no estimate's clippedPeakIdx): a device-clipped block's indices are not fetched for the tuple (None there)
+        and its record fetches them only if the host stage needs them -- not for a block whose trust bytes the device tagged;
+        before its slot is begun again."""
         R = self.bank.end_blocks_record(slot) if record is None else record
         s, nb = R.s, R.nb
         snr = self._batch_snr(R)
@@ -445,9 +449,11 @@ class Demodulator:
         pick_valid, low, high, frac, picks, counts = s['pick_valid'], s['low'], s['high'], s['frac'], s['pick'], s['count']
         hz, hz_off, clipped = self.doppHzLUT, self.centreFreqOffset, self.clippedPeakIPure
         fixed = not R.searched          # STX: no search; the device clip's indices per block (DB:670-707)
+        lazy = fixed and R.clipped is not None and not clips
+        tagged = s['clip_tag'] if stages and fixed and R.clipped is not None else None
         for b in range(nb):
             if fixed:
-                clipped = R.clipped[b] if R.clipped is not None else self.clippedPeakIPure
+                clipped = None if lazy else R.clipped[b] if R.clipped is not None else self.clippedPeakIPure
                 est = (0, 0, clipped, 0)
             elif not pick_valid[b]:       # NaN index (all-zero block): skip the block (reference DB:625-630)
                 log.error('Error occurred during find_UHF -- skipping block. Message: cannot convert float NaN to integer')
@@ -473,7 +479,11 @@ class Demodulator:
             if s['rate_fallback'][b]:
                 log.error('Code rate result 0 should not happen but happened -- fixing it to 10')
             rec = {'spSym': s['spSym'][b], 'symbols': R.sym[b, :n], 'centres': R.cen[b, :n],
-                   'trust': R.mag[b].view(TRUSTTYPE)[:n], 'clipped': np.asarray(clipped, dtype=np.int64) if fixed else empty}
+                   'trust': R.mag[b].view(TRUSTTYPE)[:n]}
+            if lazy:
+                rec['_clips'] = (R.clipped, b)          # fetched by demodulateHost where the host tags the block
+            else:
+                rec['clipped'] = np.asarray(clipped, dtype=np.int64) if fixed else empty
             if stages:
                 if s['a13_status'][b]:
                     nw = s['a13_nwin'][b]
@@ -484,6 +494,9 @@ class Demodulator:
                     # (status 2: numpy could not form the alignment's first comparison -- the reference's log line goes out with the block)
                     raised = (min(self.overlapOffset, s['a13_prev_npost'][b]), min(self.overlapOffset, nw)) if s['a13_status'][b] == 2 else None
                     rec['_a13'] = (R.bits[b, :nw], R.cen8[b, :nw], R.trust[b, :nw], post, end, prev_export, raised)
+                    if tagged is not None and tagged[b]:
+                        # the kept trust bytes carry the clipped-peak tags already (k_stream_tag); the host must not add them again
+                        rec['_tagged'] = True
                     prev_export = (post, end)
                 else:
                     prev_export = None
@@ -725,7 +738,8 @@ class Demodulator:
         block (stateful: ``poswinP``, ``posSymEnd``), clipped-peak tagging, uint8 casts.  Must see the blocks in order --
         or be given the previous block's ``overlapTail`` as ``prev_tail`` (then any process may run any block)."""
         a13 = rec.get('_a13')
-        if a13 is not None and prev_tail is None and not getattr(self, '_stream_dirty', True) and not len(rec['clipped']):
+        if (a13 is not None and prev_tail is None and not getattr(self, '_stream_dirty', True) and
+                (rec.get('_tagged') or not len(self._rec_clips(rec)))):
             # the device ran A12 / A13 for this block (stream_kernels.hpp) in front of the tail a13[5]; that must be THIS object's
             # state -- the arrays the previous device block left here, or equal ones
             bits, cen8, trust8, post, end, assumed, raised = a13
@@ -749,13 +763,24 @@ class Demodulator:
         centresWin, dataBitsWin, trustSymbolWin, _ = self.checkSymbolOverlap(noError, centres, idxSymbol, dataBits, trustSymbol)
 
         # tag symbols next to clipped interference peaks (reference DB:830-837)
-        if len(rec['clipped']):
+        clipped = self._rec_clips(rec)
+        if len(clipped):
             marks = np.zeros(self.Nfft, dtype=bool)
             spSymc = int(np.ceil(spSym))
-            for cp in rec['clipped']:
+            for cp in clipped:
                 marks[cp - 2 * spSymc:cp + 2 * spSymc + 1] = 1
             trustSymbolWin[marks[centresWin]] = -2
         return dataBitsWin.astype(np.uint8), centresWin.astype(np.uint8), trustSymbolWin.astype(np.uint8), spSym
+
+    @staticmethod
+    def _rec_clips(rec):
+        """A block record's clippedPeakIPure: as delivered, or -- a batch's block collected with ``endBlocks(..., clips=False)``
+        -- fetched from the batch now."""
+        c = rec.get('clipped')
+        if c is None:
+            src = rec.get('_clips')
+            c = rec['clipped'] = (np.asarray(src[0][src[1]], dtype=np.int64) if src is not None else np.zeros(0, dtype=np.int64))
+        return c
 
     def cudaFindCentres(self, spSym, codePhase, operation=Operations.CENTRES_ABS):
         """Per-symbol argmax over filters and a W-sample window (reference DB:991-1009).

@@ -515,7 +515,8 @@ class DemodulatorRunner:
             """The host side of a finished batch: per-block estimates, A12 / A13 (the device's, or the host code for irregular
             blocks), the result dicts, the decoder."""
             slot, count0, nb, stamp, arrived = fl
-            recs = self.demod.endBlocks(slot, record)
+            # (clips=False: a block's clip indices are fetched only where the host tags it -- before this slot is begun again)
+            recs = self.demod.endBlocks(slot, record, clips=False)
             now = time.time()
             per_block = ((now - last[0]) if last[0] is not None else (now - stamp)) / nb
             last[0] = now

@@ -19,10 +19,10 @@ def _ptr(a):
 BLOCK_SCALARS = np.dtype({
     'names': ['frac', 'spSym', 'codeOffset', 'pick', 'cr', 'spSymF', 'offsetF', 'shift', 'low', 'high', 'pick_valid', 'count',
               'rate_fallback', 'band', 'band_len', 'a13_status', 'a13_start', 'a13_end', 'a13_nwin', 'a13_noerr', 'a13_npost',
-              'a13_nend', 'sync_valid', 'sync_count', 'a13_prev_npost'],
+              'a13_nend', 'sync_valid', 'sync_count', 'a13_prev_npost', 'clip_tag', 'clip_count'],
     'formats': ['<f8', '<f8', '<f8', ('<f4', 2), ('<f4', 3), '<f4', '<f4', '<i4', '<i4', '<i4', '<i4', '<i4', '<i4', ('<i4', (2, 2, 2)),
-                ('<i4', 2), '<i4', '<i4', '<i4', '<i4', '<i4', '<i4', '<i4', '<i4', ('<i4', 2), '<i4'],
-    'offsets': [0, 8, 16, 24, 32, 44, 48, 52, 56, 60, 64, 68, 72, 76, 108, 116, 120, 124, 128, 132, 136, 140, 144, 148, 156],
+                ('<i4', 2), '<i4', '<i4', '<i4', '<i4', '<i4', '<i4', '<i4', '<i4', ('<i4', 2), '<i4', '<i4', '<i4'],
+    'offsets': [0, 8, 16, 24, 32, 44, 48, 52, 56, 60, 64, 68, 72, 76, 108, 116, 120, 124, 128, 132, 136, 140, 144, 148, 156, 160, 164],
     'itemsize': 168})
 
 
@@ -76,11 +76,36 @@ class HostCopy:
             pass
 
 
+class BlockClips:
+    """clippedPeakIPure (int64) of every block of a collected batch, each fetched when first asked for (mfb_get_block_clips): a
+    block whose kept trust bytes the device tagged (BlockScalars.clip_tag) needs none of them, so a batch costs no copy per
+    block.  Valid until the batch's slot is begun again -- the library's buffers then belong to the next flight."""
+
+    def __init__(self, bank, slot, nb):
+        self._bank, self._slot, self._gen = bank, int(slot), bank._slot_gen(slot)
+        self._got = [None] * int(nb)
+
+    def __len__(self):
+        return len(self._got)
+
+    def __getitem__(self, b):
+        b = range(len(self._got))[b]
+        v = self._got[b]
+        if v is None:
+            if self._bank._slot_gen(self._slot) != self._gen:
+                raise RuntimeError('the clip indices of this batch are gone: its slot was begun again')
+            v = self._got[b] = self._bank.get_block_clips(self._slot, b)
+        return v
+
+    def __iter__(self):
+        return (self[b] for b in range(len(self._got)))
+
+
 class BatchRecord:
     """A finished batch of blocks as it came off the device (mfb_receive_blocks_end_record): ``nb`` records in one buffer, read
     in place.  Scalars come as one Python list per field (``s['count'][b]``); arrays as 2-D views, block b in row b."""
 
-    clipped = None             # per block: the device's clippedPeakIPure (int64), when the blocks were clipped (set_peak_clip)
+    clipped = None             # per block: the device's clippedPeakIPure (int64, a BlockClips), when the blocks were clipped (set_peak_clip)
 
     def __init__(self, buf, lay, searched):
         nb, rec, n = lay.nblocks, lay.record_bytes, lay.symbols
@@ -371,10 +396,19 @@ class MFBank:
         sym, cen, mag, bands = self._block_arrays()
         _lib.check(self._lib.mfb_receive_block(self._h, C.byref(P), C.byref(R), _ptr(sym), _ptr(cen), _ptr(mag), _ptr(bands)),
                    'mfb_receive_block')
+        self._begun(0)          # (the one-call path's clip indices live in slot 0's buffers)
         out = self._block_result(R, fixed_shift is None)
         if getattr(self, '_clip', False):
             out['clipped'] = self.get_block_clips(0)
         return out
+
+    def _begun(self, slot):
+        """Slot ``slot`` holds a new flight: what the library kept of the one before it (its clip indices) is gone."""
+        g = self.__dict__.setdefault('_gens', {})
+        g[int(slot)] = g.get(int(slot), 0) + 1
+
+    def _slot_gen(self, slot):
+        return self.__dict__.get('_gens', {}).get(int(slot), 0)
 
     # -- interference-peak clipping on the device (reference __thresholdInput, DB:670-707) ---------
     def set_peak_clip(self, scale, overlap=0):
@@ -452,6 +486,7 @@ class MFBank:
         (``slot`` 0 / 1) may be in flight."""
         P = self._block_params(k_offset, k_len, spsym_min, op, snr_window, fixed_shift, source, device_ptr)
         _lib.check(self._lib.mfb_receive_block_begin(self._h, C.byref(P), int(slot)), 'mfb_receive_block_begin')
+        self._begun(slot)
         self._clipped = getattr(self, '_clipped', {})
         self._clipped[int(slot)] = getattr(self, '_clip', False)
         self._searched = getattr(self, '_searched', {})
@@ -496,6 +531,7 @@ class MFBank:
         device memory, ``block_stride`` required)."""
         P = self._block_params(k_offset, k_len, spsym_min, op, snr_window, fixed_shift, source, device_ptr, block_stride)
         _lib.check(self._lib.mfb_receive_blocks_begin(self._h, C.byref(P), int(nblocks), int(slot)), 'mfb_receive_blocks_begin')
+        self._begun(slot)
         self._clipped = getattr(self, '_clipped', {})
         self._clipped[int(slot)] = getattr(self, '_clip', False)
         self._searched = getattr(self, '_searched', {})
@@ -534,7 +570,7 @@ class MFBank:
         _lib.check(rc, 'mfb_receive_blocks_end_record')
         R = BatchRecord(buf, lay, self._searched.get(slot, True))
         if getattr(self, '_clipped', {}).get(slot, False):
-            R.clipped = [self.get_block_clips(slot, b) for b in range(R.nb)]
+            R.clipped = BlockClips(self, slot, R.nb)       # fetched block by block where they are needed
         return R
 
     def end_blocks(self, slot):

@@ -1,8 +1,9 @@
 """Receive-loop rate of the S-band (STX) back end at its production geometry -- blocks of 2^17 samples, overlap 2^11, peak
 threshold scale 4.5 (pycusdr_amd/config.py) -- on a seeded GMSK packet stream with interference bursts: run_stream with the
 peak clip on the host (the reference's __thresholdInput, DB:670-707) against the same stream with "HIP": {"device_clip": true}
-(one block per call, overlapped, and batches of the auto size), and whether every non-timing result key and every packet
-agree.  Prints one JSON line.
+(one block per call, overlapped, batches of the auto size, and the same batches with "stream_stages": false -- the bit lookup,
+the block-overlap alignment and the clipped-peak tags on the host), and whether every non-timing result key and every packet
+agree.  Prints one JSON line; `<leg>_stage_blocks` counts the blocks whose integer stages the device ran.
 The clip kernels' time per block comes from a run of this script under `rocprofv3 --kernel-trace --stats` (k_clip_*).
 
     python tools/stx_rate.py [blocks] [bs]
@@ -38,6 +39,8 @@ def main(nblocks=64, bs=17, ov_log2=11, scale=4.5):
     conf['Radios']['Rx']['UHF-H']['radioBackend'] = 'STX'
     dconf = copy.deepcopy(conf)
     dconf['GPU']['UHF'].setdefault('HIP', {})['device_clip'] = True
+    hconf = copy.deepcopy(dconf)
+    hconf['GPU']['UHF']['HIP']['stream_stages'] = False
     p = loadProtocol('bench_GMSK')(conf=conf)
     sig = sg.s1_stream(nblocks, N, ov, 'GMSK', snr_db=12.0, seed=17)
     rng = np.random.default_rng(17)
@@ -47,11 +50,14 @@ def main(nblocks=64, bs=17, ov_log2=11, scale=4.5):
     chunks = lambda: [sig[i:i + 65536] for i in range(0, len(sig), 65536)]
     out = {'blockSize': bs, 'overlap': ov, 'peakThresholdScale': scale, 'blocks': nblocks}
     res = {}
-    for name, c, B in (('host_clip', conf, None), ('device_clip_b1', dconf, 1), ('device_clip_auto', dconf, None)):
+    legs = (('host_clip', conf, None), ('device_clip_b1', dconf, 1), ('device_clip_auto', dconf, None),
+            ('device_clip_auto_host_stages', hconf, None))
+    for name, c, B in legs:
         r = DemodulatorRunner(c, p, 'UHF-H')
         try:
             r.run_stream(chunks()[:8], decoder=Decoder(c, p), blocks_per_call=B)        # warm-up: graphs, buffers
             src = chunks()
+            r.demod.stage_blocks = 0
             t0 = time.perf_counter()
             results, packets = r.run_stream(src, decoder=Decoder(c, p), blocks_per_call=B)
             dt = time.perf_counter() - t0
@@ -60,11 +66,12 @@ def main(nblocks=64, bs=17, ov_log2=11, scale=4.5):
         finally:
             r.close()
         out[name + '_msps'] = round(len(results) * (N - ov) / dt / 1e6, 1)
+        out[name + '_stage_blocks'] = int(r.demod.stage_blocks)
         res[name] = (results, packets)
     ra, pa = res['host_clip']
     out['blocks_with_clipped_peaks'] = int(sum(1 for d in ra if (np.asarray(d['trust']) == 254).any()))
     same = True
-    for name in ('device_clip_b1', 'device_clip_auto'):
+    for name in ('device_clip_b1', 'device_clip_auto', 'device_clip_auto_host_stages'):
         rb, pb = res[name]
         same = same and len(ra) == len(rb) and len(pa) == len(pb) and all(np.array_equal(u.bits, v.bits) for u, v in zip(pa, pb))
         for x, y in zip(ra, rb):
