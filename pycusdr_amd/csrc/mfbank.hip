@@ -56,6 +56,7 @@
 #include "stream_kernels.hpp"
 #include "clip_kernels.hpp"
 #include "hostcopy.hpp"
+#include "record_layout.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -64,9 +65,7 @@ struct BlockFlight {      // one block -- or one batch of nb blocks -- between m
     bool active;
     int mode, nthreads, bcap, shift, op;
     int nb;               // 0: a single block (mfb_receive_block_begin); > 0: a batch (mfb_receive_blocks_begin)
-    size_t rec;           // bytes per block record in the staging buffer (batches)
-    size_t ext;           // offset of the stream-stage outputs inside a record (0: none)
-    size_t off[5];
+    RecordLayout lay;     // where things sit inside a record; lay.bytes apart in the staging buffer (batches)
     unsigned long long seq;
     bool clip;            // the block(s) went through the peak clip (mfb_get_block_clips)
 };
@@ -226,7 +225,6 @@ struct mfb_ctx {
         }                                                                                    \
     } while (0)
 
-static size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 // the handle's stream and -- when a batch has put work there since the last wait -- the second stream of the batch path
 static hipError_t sync_streams(mfb_ctx *c) {
     hipError_t e = hipStreamSynchronize(c->stream);
@@ -386,9 +384,12 @@ static int reserve_partials(mfb_ctx *c, size_t floats) {
 
 // Device-side result record of a block: [BlockScalars, 256 B][bands 2 x bcap complex64][sym][cen][mag] (nthreads each),
 // contiguous so that ONE copy brings it to the host.
+// The layout itself is stated in record_layout.hpp; everything below asks rec_layout.
 #define BLK_HEAD 256
-static size_t blkout_bytes(int bcap, int nthreads) {
-    return BLK_HEAD + align16((size_t)2 * bcap * sizeof(cf)) + 3 * align16((size_t)nthreads * sizeof(int));
+static_assert(sizeof(BlockScalars) <= BLK_HEAD && sizeof(cf) == 2 * sizeof(float), "record_layout.hpp counts on both");
+static RecordLayout rec_layout(int bcap, int nthreads, bool stages = false) {
+    static const RecordConsts k = {BLK_HEAD, STREAM_POST_MAX, STREAM_END_MAX, STREAM_MAX_TMPL, STREAM_MAX_HITS, STREAM_EDGE_CANDS, sizeof(StreamEdge)};
+    return record_layout(k, bcap, nthreads, stages);
 }
 static int blkout_reserve(mfb_ctx *c, int bcap) {
     if (c->d_blkout && bcap <= c->band_cap) return MFB_OK;
@@ -399,10 +400,10 @@ static int blkout_reserve(mfb_ctx *c, int bcap) {
     }
     c->d_blkout = nullptr;
     c->band_cap = 0;
-    HIPCHK(dev_alloc((void **)&c->d_blkout, blkout_bytes(bcap, c->cap)));
+    HIPCHK(dev_alloc((void **)&c->d_blkout, rec_layout(bcap, c->cap).bytes));
     if (c->d_blkout2) HIPCHK(hipFree(c->d_blkout2));
     c->d_blkout2 = nullptr;
-    HIPCHK(dev_alloc((void **)&c->d_blkout2, blkout_bytes(bcap, c->cap)));        // flight slot 1 (two streams: mfb_set_batch_overlap)
+    HIPCHK(dev_alloc((void **)&c->d_blkout2, rec_layout(bcap, c->cap).bytes));        // flight slot 1 (two streams: mfb_set_batch_overlap)
     c->band_cap = bcap;
     c->d_scal = (BlockScalars *)c->d_blkout;
     return MFB_OK;
@@ -541,7 +542,7 @@ static int create_impl(mfb_ctx *c) {
     if ((rc = blkout_reserve(c, 1024))) return rc;
     for (int i = 0; i < 2; ++i) {
         // scalars + three arrays of the symbols a rate window of +-10 % around 4 samples per symbol admits + the two windows
-        c->blk_cap[i] = blkout_bytes(c->band_cap, c->N / 3);
+        c->blk_cap[i] = rec_layout(c->band_cap, c->N / 3).bytes;
         HIPCHK(hipHostMalloc((void **)&c->h_blk[i], c->blk_cap[i], hipHostMallocDefault));
         HIPCHK(hipEventCreateWithFlags(&c->ev_blk[i], hipEventDisableTiming));
     }
@@ -632,6 +633,21 @@ extern "C" int mfb_create(mfb_ctx **out, int device, int log2N, int num_dopplers
 }
 
 static void graph_drop(BlockGraph &g);
+// every recorded graph of the handle, or (slot >= 0) those of one flight slot
+template <class F>
+static void for_each_graph(mfb_ctx *c, int slot, F &&f) {
+    for (int in = 0; in < 2; ++in)
+        for (int s = 0; s < 2; ++s) {
+            if (slot >= 0 && s != slot) continue;
+            f(c->bgraph[in][s]);
+            f(c->bgraph2[in][s]);
+            for (int par = 0; par < 2; ++par)
+                for (int nb = 0; nb <= WG_NB; ++nb) {
+                    f(c->wgraph[in][s][par][nb]);
+                    f(c->wgraph2[in][s][par][nb]);
+                }
+        }
+}
 extern "C" int mfb_destroy(mfb_ctx *c) {
     if (!c) return MFB_ERR_ARG;
     (void)hipSetDevice(c->device);
@@ -652,18 +668,7 @@ extern "C" int mfb_destroy(mfb_ctx *c) {
         if (c->ev_wh2d[i]) (void)hipEventDestroy(c->ev_wh2d[i]);
         if (c->ev_wfree[i]) (void)hipEventDestroy(c->ev_wfree[i]);
     }
-    for (auto &row : c->bgraph)
-        for (auto &g : row) graph_drop(g);
-    for (auto &row : c->bgraph2)
-        for (auto &g : row) graph_drop(g);
-    for (auto &row : c->wgraph)
-        for (auto &col : row)
-            for (auto &par : col)
-                for (auto &g : par) graph_drop(g);
-    for (auto &row : c->wgraph2)
-        for (auto &col : row)
-            for (auto &par : col)
-                for (auto &g : par) graph_drop(g);
+    for_each_graph(c, -1, graph_drop);
     for (int i = 0; i < 2; ++i) {
         if (c->h_blk[i]) (void)hipHostFree(c->h_blk[i]);
         if (c->ev_blk[i]) (void)hipEventDestroy(c->ev_blk[i]);
@@ -1978,14 +1983,14 @@ struct BlkBufs {
     float *env;          // symbol-energy envelopes [nb][N]
     cf *P;               // their spectra [nb][N]
     float *cr;           // rate triples [nb][3]
-    uint8_t *out;        // result records [nb][rec]
-    size_t rec;
-    size_t ext;          // offset of the stream-stage outputs inside a record (0: the stages run on the host)
+    uint8_t *out;        // result records [nb][lay.bytes]
+    RecordLayout lay;    // (lay.stages: the stream stages run on the device, behind the centres)
+    bool batch;          // mfb_receive_blocks_*: the handle's one-block state (d_in, have_input, mirror) stays out of it
     int parity;          // carry buffer the stream stages read
     const struct ClipLaunch *clip;   // peak clip in front of the forward transform (nullptr: none); x is then its output
 };
-static BlkBufs single_bufs(mfb_ctx *c) {
-    return BlkBufs{1, c->d_in, 0, c->d_X, c->d_sum, c->d_res, c->d_xc, c->d_env, c->d_P, c->d_cr, c->d_blkout, 0, 0, 0, nullptr};
+static BlkBufs single_bufs(mfb_ctx *c, const RecordLayout &lay = RecordLayout{}) {
+    return BlkBufs{1, c->d_in, 0, c->d_X, c->d_sum, c->d_res, c->d_xc, c->d_env, c->d_P, c->d_cr, c->d_blkout, lay, false, 0, nullptr};
 }
 
 // A9 + A10 enqueued on the handle's stream: matched filters at one shift per block (a value, or -- shift_dev != nullptr -- an
@@ -2059,7 +2064,7 @@ static int demod_enqueue(mfb_ctx *c, const BlkBufs &bb, int shift, const int *sh
     if (rc) return rc;
     if (scal)
         hipLaunchKernelGGL(k_code_rate_block, dim3(nb), dim3(1024), 0, c->stream, (const cf *)bb.P, bb.cr, k_offset, k_len, c->N, spsym_min,
-                           capacity, scal, bb.rec);
+                           capacity, scal, bb.lay.bytes);
     else
         hipLaunchKernelGGL(k_code_rate, dim3(1), dim3(1024), 0, c->stream, (const cf *)bb.P, bb.cr, k_offset, k_len);
     HIPCHK(hipGetLastError());
@@ -2109,16 +2114,25 @@ struct RecPtrs {
     int *sym, *cen;
     float *mag;
 };
-static RecPtrs rec_ptrs(const BlkBufs &bb, int nthreads, int bcap) {
-    RecPtrs r;
-    r.rec = bb.rec ? bb.rec : blkout_bytes(bcap, nthreads);
-    r.d = bb.out;
-    r.scal = (BlockScalars *)r.d;
-    r.bands = (cf *)(r.d + BLK_HEAD);
-    r.sym = (int *)(r.d + BLK_HEAD + align16((size_t)2 * bcap * sizeof(cf)));
-    r.cen = (int *)((uint8_t *)r.sym + align16((size_t)nthreads * sizeof(int)));
-    r.mag = (float *)((uint8_t *)r.cen + align16((size_t)nthreads * sizeof(int)));
-    return r;
+static RecPtrs rec_ptrs(const BlkBufs &bb) {
+    uint8_t *d = bb.out;
+    const RecordLayout &l = bb.lay;
+    return RecPtrs{l.bytes, d, (BlockScalars *)(d + l.scalars), (cf *)(d + l.bands), (int *)(d + l.sym), (int *)(d + l.cen), (float *)(d + l.mag)};
+}
+// the records a launch of the stream stages works on
+static void stream_records(StreamArgs &sa, uint8_t *rec0, const RecordLayout &l) {
+    sa.rec0 = rec0;
+    sa.rec = l.bytes;
+    sa.off_sym = l.sym;
+    sa.off_cen = l.cen;
+    sa.off_mag = l.mag;
+    sa.off_bits = l.bits;
+    sa.off_cenw = l.cenw;
+    sa.off_trust = l.trust;
+    sa.off_post = l.post;
+    sa.off_end = l.end;
+    sa.off_hits = l.hits;
+    sa.off_edges = l.edges;
 }
 // ---- interference-peak clipping (clip_kernels.hpp; reference __thresholdInput, DB:670-707) -----------------------------------
 struct ClipLaunch {
@@ -2265,10 +2279,22 @@ extern "C" int mfb_get_block_clips(mfb_ctx *c, int slot, int block, int32_t *idx
 }
 
 // Part 1 of a block / batch: forward transform(s), Doppler search, pick (or, at a fixed shift, the cleared scalars).
-static int block_enqueue_p1(mfb_ctx *c, const mfb_block_params *p, const BlkBufs &bb, int nthreads, int bcap) {
+// How much of a block's results its record holds: the SNR windows' capacity, the symbols the caller takes at most, and every symbol
+// the rate window admits (k* < k_offset + k_len  =>  count <= k_offset + k_len), bounded by that
+struct BlockGeom {
+    int bcap, capacity, nthreads;
+};
+static BlockGeom block_geom(const mfb_ctx *c, const mfb_block_params *p) {
+    BlockGeom g;
+    g.bcap = p->mode == MFB_BLOCK_SEARCH ? p->band_capacity : 0;
+    g.capacity = p->max_symbols < c->cap ? p->max_symbols : c->cap;
+    g.nthreads = p->k_offset + p->k_len + 1 < g.capacity ? p->k_offset + p->k_len + 1 : g.capacity;
+    return g;
+}
+static int block_enqueue_p1(mfb_ctx *c, const mfb_block_params *p, const BlkBufs &bb, const BlockGeom &geo) {
     int rc;
     const int nb = bb.nb;
-    const bool batch = bb.rec != 0;
+    const bool batch = bb.batch;
     if (!batch && p->input == MFB_INPUT_UPLOADED) {
         if (!c->have_input) return MFB_ERR_STATE;
     } else {
@@ -2283,7 +2309,7 @@ static int block_enqueue_p1(mfb_ctx *c, const mfb_block_params *p, const BlkBufs
             c->have_xc = false;
         }
     }
-    const RecPtrs r = rec_ptrs(bb, nthreads, bcap);
+    const RecPtrs r = rec_ptrs(bb);
     if (p->mode == MFB_BLOCK_SEARCH) {
         if (batch) {
             if (c->path != MFB_PATH_SEGMENT || c->search_mode != MFB_SEARCH_TRANSFORMS) return MFB_ERR_UNSUPPORTED;
@@ -2292,7 +2318,7 @@ static int block_enqueue_p1(mfb_ctx *c, const mfb_block_params *p, const BlkBufs
             return rc;
         }
         hipLaunchKernelGGL(k_pick_block, dim3(nb), dim3(64), 0, c->stream, (const float *)bb.sum, bb.res, c->D, c->Doff, c->M, c->sum_all,
-                           (const int *)c->d_shifts, c->Dtot, c->N, p->snr_window, (const cf *)bb.X, r.scal, r.bands, bcap, r.rec);
+                           (const int *)c->d_shifts, c->Dtot, c->N, p->snr_window, (const cf *)bb.X, r.scal, r.bands, geo.bcap, r.rec);
         HIPCHK(hipGetLastError());
     } else {
         hipLaunchKernelGGL(k_block_clear, dim3(nb), dim3(1), 0, c->stream, r.scal, r.rec);
@@ -2302,44 +2328,27 @@ static int block_enqueue_p1(mfb_ctx *c, const mfb_block_params *p, const BlkBufs
 }
 // Part 2: matched filters at the picked (or fixed) shift, envelope, its spectrum, rate / phase, symbol centres, the integer stages
 // of a batch, and the ONE device-to-host copy of the record(s).
-static int block_enqueue_p2(mfb_ctx *c, const mfb_block_params *p, const BlkBufs &bb, uint8_t *h_dst, int nthreads, int bcap, int capacity,
-                            int *shift_out) {
+static int block_enqueue_p2(mfb_ctx *c, const mfb_block_params *p, const BlkBufs &bb, uint8_t *h_dst, const BlockGeom &geo) {
     int rc;
-    const int nb = bb.nb;
-    const bool batch = bb.rec != 0;
-    const RecPtrs r = rec_ptrs(bb, nthreads, bcap);
+    const int nb = bb.nb, nthreads = geo.nthreads;
+    const RecPtrs r = rec_ptrs(bb);
     const size_t rec = r.rec;
-    uint8_t *d = r.d;
     BlockScalars *scal = r.scal;
-    int *d_sym = r.sym, *d_cen = r.cen;
-    float *d_mag = r.mag;
     const int *shift_dev = nullptr;
     int shift = 0;
     if (p->mode == MFB_BLOCK_SEARCH) shift_dev = &scal->shift;
     else shift = ((p->fixed_shift % c->N) + c->N) % c->N;
-    if ((rc = demod_enqueue(c, bb, shift, shift_dev, (int)(rec / sizeof(int)), p->k_offset, p->k_len, p->spsym_min, capacity, scal))) return rc;
+    if ((rc = demod_enqueue(c, bb, shift, shift_dev, (int)(rec / sizeof(int)), p->k_offset, p->k_len, p->spsym_min, geo.capacity, scal))) return rc;
     // (entries past nthreads are not part of the record: the kernel's capacity bounds what it writes; the k* == 0 fallback --
     // spSym = 10, DB:737-740, unreachable while the rate window starts above bin 0 -- is completed in block_end)
-    hipLaunchKernelGGL(k_centres_block, dim3((nthreads + 255) / 256, nb), dim3(256), 0, c->stream, d_sym, d_cen, d_mag, (const cf *)bb.xc,
+    hipLaunchKernelGGL(k_centres_block, dim3((nthreads + 255) / 256, nb), dim3(256), 0, c->stream, r.sym, r.cen, r.mag, (const cf *)bb.xc,
                        (const BlockScalars *)scal, c->N, c->M, c->W, p->op, nthreads, rec);
     HIPCHK(hipGetLastError());
-    if (batch && bb.ext) {
+    if (bb.lay.stages) {         // (batches only)
         // A12 / A13 / A14 of every block of the batch on the device (stream_kernels.hpp); the state they chain on -- the previous
         // batch's tail and bit ring -- sits in carry[cur], this batch leaves its own in carry[1 - cur]
         StreamArgs sa = c->st;
-        sa.rec0 = d;
-        sa.rec = rec;
-        sa.off_sym = (size_t)((uint8_t *)d_sym - d);
-        sa.off_cen = (size_t)((uint8_t *)d_cen - d);
-        sa.off_mag = (size_t)((uint8_t *)d_mag - d);
-        const size_t a1 = align16((size_t)nthreads);
-        sa.off_bits = bb.ext;
-        sa.off_cenw = bb.ext + a1;
-        sa.off_trust = bb.ext + 2 * a1;
-        sa.off_post = bb.ext + 3 * a1;
-        sa.off_end = sa.off_post + STREAM_POST_MAX;
-        sa.off_hits = sa.off_end + STREAM_END_MAX;
-        sa.off_edges = sa.off_hits + (size_t)STREAM_MAX_TMPL * 2 * STREAM_MAX_HITS * sizeof(int32_t);
+        stream_records(sa, r.d, bb.lay);
         sa.nb = nb;
         sa.nsym = nthreads;
         sa.carry_in = c->d_carry[bb.parity];
@@ -2360,14 +2369,12 @@ static int block_enqueue_p2(mfb_ctx *c, const mfb_block_params *p, const BlkBufs
             HIPCHK(hipGetLastError());
         }
     }
-    HIPCHK(hipMemcpyAsync(h_dst, d, rec * nb, hipMemcpyDeviceToHost, c->stream));
-    *shift_out = shift;
+    HIPCHK(hipMemcpyAsync(h_dst, r.d, rec * nb, hipMemcpyDeviceToHost, c->stream));
     return MFB_OK;
 }
-static int block_enqueue(mfb_ctx *c, const mfb_block_params *p, const BlkBufs &bb, uint8_t *h_dst, int nthreads, int bcap, int capacity,
-                         int *shift_out) {
-    const int rc = block_enqueue_p1(c, p, bb, nthreads, bcap);
-    return rc ? rc : block_enqueue_p2(c, p, bb, h_dst, nthreads, bcap, capacity, shift_out);
+static int block_enqueue(mfb_ctx *c, const mfb_block_params *p, const BlkBufs &bb, uint8_t *h_dst, const BlockGeom &geo) {
+    const int rc = block_enqueue_p1(c, p, bb, geo);
+    return rc ? rc : block_enqueue_p2(c, p, bb, h_dst, geo);
 }
 
 // Host-to-device copy of a page-locked input buffer into its own device copy, on the input stream: it starts as soon as the
@@ -2476,14 +2483,7 @@ static int check_block_params(const mfb_ctx *c, const mfb_block_params *p) {
 // page-locked staging of a flight: at least `need` bytes (the address is baked into the slot's graphs)
 static int staging_reserve(mfb_ctx *c, int slot, size_t need) {
     if (need <= c->blk_cap[slot]) return MFB_OK;
-    for (auto &row : c->bgraph) graph_drop(row[slot]);
-    for (auto &row : c->bgraph2) graph_drop(row[slot]);
-    for (auto &row : c->wgraph)
-        for (auto &par : row[slot])
-            for (auto &g : par) graph_drop(g);
-    for (auto &row : c->wgraph2)
-        for (auto &par : row[slot])
-            for (auto &g : par) graph_drop(g);
+    for_each_graph(c, slot, graph_drop);
     if (c->s2) HIPCHK(hipStreamSynchronize(c->s2));
     if (c->h_blk[slot]) HIPCHK(hipHostFree(c->h_blk[slot]));
     c->h_blk[slot] = nullptr;
@@ -2495,6 +2495,62 @@ static int staging_reserve(mfb_ctx *c, int slot, size_t need) {
 
 static bool batch_split(const mfb_ctx *c);
 static int second_stream(mfb_ctx *c, int slot);
+// While one of these lives, every launch helper enqueues on the second stream (they all use c->stream) and the transforms use the
+// second intermediate: part 2 of a block / batch.  The handle's stream comes back on every way out.
+struct Part2Scope {
+    mfb_ctx *c;
+    hipStream_t s1;
+    explicit Part2Scope(mfb_ctx *c_) : c(c_), s1(c_->stream) {
+        c->stream = c->s2;
+        c->use_z2 = true;
+        c->s2_busy = true;
+    }
+    ~Part2Scope() {
+        c->stream = s1;
+        c->use_z2 = false;
+    }
+    Part2Scope(const Part2Scope &) = delete;
+    Part2Scope &operator=(const Part2Scope &) = delete;
+};
+// The launches of one flight -- a block or a batch -- into slot `slot`, up to the event its _end waits for.  In one piece on the handle's
+// stream (g1), or (split; second_stream has been called) part 1 there and part 2 behind it on the second stream (g2): the NEXT
+// flight's part 1 is enqueued behind this one's part 1 only, and runs beside this one's part 2.  ev_free (may be null) is recorded
+// behind the last reader of the input's device copy: from there on it may be overwritten.
+static int flight_launch(mfb_ctx *c, BlockGraph &g1, BlockGraph &g2, const BlkBufs &bb, const mfb_block_params *p, const BlockGeom &geo,
+                         int graph_nb, bool allowed, bool split, int slot, hipEvent_t ev_free) {
+    int rc;
+    if (!split) {
+        rc = graph_or_launch(c, g1, p, graph_nb, allowed, [&]() { return block_enqueue(c, p, bb, c->h_blk[slot], geo); });
+        if (rc) return rc;
+        if (!bb.batch) c->have_input = true;
+        HIPCHK(hipEventRecord(c->ev_blk[slot], c->stream));
+        if (ev_free) HIPCHK(hipEventRecord(ev_free, c->stream));
+        return MFB_OK;
+    }
+    rc = graph_or_launch(c, g1, p, graph_nb, allowed, [&]() { return block_enqueue_p1(c, p, bb, geo); });
+    if (rc) return rc;
+    if (!bb.batch) c->have_input = true;      // (the spectrum is this block's from here on, whatever becomes of part 2)
+    HIPCHK(hipEventRecord(c->ev_p1[slot], c->stream));
+    Part2Scope part2(c);
+    if (hipStreamWaitEvent(c->stream, c->ev_p1[slot], 0) != hipSuccess) return MFB_ERR_HIP;
+    rc = graph_or_launch(c, g2, p, graph_nb, allowed, [&]() { return block_enqueue_p2(c, p, bb, c->h_blk[slot], geo); });
+    if (rc) return rc;
+    if (hipEventRecord(c->ev_blk[slot], c->stream) != hipSuccess) return MFB_ERR_HIP;
+    if (ev_free && hipEventRecord(ev_free, c->stream) != hipSuccess) return MFB_ERR_HIP;
+    return MFB_OK;
+}
+static void flight_fill(mfb_ctx *c, BlockFlight &f, const mfb_block_params *p, const BlockGeom &geo, const RecordLayout &lay, int nb, bool clip) {
+    f.active = true;
+    f.mode = p->mode;
+    f.nthreads = geo.nthreads;
+    f.bcap = geo.bcap;
+    f.shift = p->mode == MFB_BLOCK_FIXED_SHIFT ? ((p->fixed_shift % c->N) + c->N) % c->N : 0;
+    f.seq = ++c->blk_seq;
+    f.op = p->op;
+    f.nb = nb;
+    f.lay = lay;
+    f.clip = clip;
+}
 // Enqueue: everything up to and including the ONE device-to-host copy into the flight's page-locked staging; no wait.
 static int block_begin(mfb_ctx *c, const mfb_block_params *p, int slot) {
     if (!c || !p || slot < 0 || slot > 1) return MFB_ERR_ARG;
@@ -2507,15 +2563,11 @@ static int block_begin(mfb_ctx *c, const mfb_block_params *p, int slot) {
     BlockFlight &f = c->flight[slot];
     if (f.active) return MFB_ERR_STATE;          // its results have not been collected
     if (c->clip_scale > 0.f && p->input == MFB_INPUT_UPLOADED) return MFB_ERR_UNSUPPORTED;     // its samples are transformed already
-    const int bcap = p->mode == MFB_BLOCK_SEARCH ? p->band_capacity : 0;
-    if ((rc = blkout_reserve(c, bcap > c->band_cap ? bcap : c->band_cap))) return rc;
-    const int capacity = p->max_symbols < c->cap ? p->max_symbols : c->cap;
-    // every symbol the rate window admits (k* < k_offset + k_len  =>  count <= k_offset + k_len), bounded by the capacity
-    int nthreads = p->k_offset + p->k_len + 1;
-    if (nthreads > capacity) nthreads = capacity;
-    if ((rc = staging_reserve(c, slot, blkout_bytes(bcap, nthreads)))) return rc;
+    const BlockGeom geo = block_geom(c, p);
+    if ((rc = blkout_reserve(c, geo.bcap > c->band_cap ? geo.bcap : c->band_cap))) return rc;
+    const RecordLayout lay = rec_layout(geo.bcap, geo.nthreads);
+    if ((rc = staging_reserve(c, slot, lay.bytes))) return rc;
     if (!c->ev_blk[slot]) HIPCHK(hipEventCreateWithFlags(&c->ev_blk[slot], hipEventDisableTiming));
-    int shift = p->mode == MFB_BLOCK_FIXED_SHIFT ? ((p->fixed_shift % c->N) + c->N) % c->N : 0;
     const bool pinned_in = p->input == MFB_INPUT_PINNED || p->input == MFB_INPUT_PINNED2;
     const int which = p->input == MFB_INPUT_PINNED2 ? 1 : 0;
     if (pinned_in && (rc = block_input_copy(c, which))) return rc;
@@ -2534,62 +2586,22 @@ static int block_begin(mfb_ctx *c, const mfb_block_params *p, int slot) {
     // block's matched filters, envelope transform, rate, centres and read-back.  Part 2 reads the samples (the STORE kernel), so the
     // input has to be one of the two page-locked buffers' device copies or the caller's device block -- not the handle's upload
     const bool split = batch_split(c) && p->input != MFB_INPUT_UPLOADED && c->path == MFB_PATH_SEGMENT;
-    if (!split) {
-        BlkBufs bb = single_bufs(c);
-        if (clip) bb.clip = &cl;
-        rc = graph_or_launch(c, c->bgraph[which][slot], p, 0, allowed,
-                             [&]() { return block_enqueue(c, p, bb, c->h_blk[slot], nthreads, bcap, capacity, &shift); });
-        if (rc) return rc;
-        c->have_input = true;
-        HIPCHK(hipEventRecord(c->ev_blk[slot], c->stream));
-        if (pinned_in) HIPCHK(hipEventRecord(c->ev_xfree[which], c->stream));      // this device copy may be overwritten from here on
-    } else {
+    if (split) {
         if ((rc = second_stream(c, slot))) return rc;
         if (c->z2_rows < 1) {
             HIPCHK(sync_streams(c));
             HIPCHK(dev_alloc((void **)&c->d_Z2, (size_t)c->N * sizeof(cf)));
             c->z2_rows = 1;
         }
-        BlkBufs bb = single_bufs(c);
-        bb.out = slot ? c->d_blkout2 : c->d_blkout;
-        if (clip) bb.clip = &cl;
-        rc = graph_or_launch(c, c->bgraph[which][slot], p, -1, allowed, [&]() { return block_enqueue_p1(c, p, bb, nthreads, bcap); });
-        if (rc) return rc;
-        c->have_input = true;
-        HIPCHK(hipEventRecord(c->ev_p1[slot], c->stream));
-        hipStream_t s1 = c->stream;
-        c->stream = c->s2;
-        c->use_z2 = true;
-        c->s2_busy = true;
-        hipError_t e = hipStreamWaitEvent(c->s2, c->ev_p1[slot], 0);
-        rc = e != hipSuccess ? MFB_ERR_HIP
-                             : graph_or_launch(c, c->bgraph2[which][slot], p, -1, allowed,
-                                               [&]() { return block_enqueue_p2(c, p, bb, c->h_blk[slot], nthreads, bcap, capacity, &shift); });
-        if (!rc) {
-            e = hipEventRecord(c->ev_blk[slot], c->s2);
-            if (e == hipSuccess && pinned_in) e = hipEventRecord(c->ev_xfree[which], c->s2);
-            if (e != hipSuccess) rc = MFB_ERR_HIP;
-        }
-        c->stream = s1;
-        c->use_z2 = false;
-        if (rc) return rc;
     }
-    const size_t sym_off = BLK_HEAD + align16((size_t)2 * bcap * sizeof(cf)), arr = align16((size_t)nthreads * sizeof(int));
-    f.off[0] = 0;
-    f.off[4] = BLK_HEAD;
-    f.off[1] = sym_off;
-    f.off[2] = sym_off + arr;
-    f.off[3] = sym_off + 2 * arr;
-    f.active = true;
-    f.mode = p->mode;
-    f.nthreads = nthreads;
-    f.bcap = bcap;
-    f.shift = shift;
-    f.seq = ++c->blk_seq;
-    f.op = p->op;
-    f.nb = 0;
-    f.rec = 0;
-    f.clip = clip;
+    BlkBufs bb = single_bufs(c, lay);
+    if (split && slot) bb.out = c->d_blkout2;
+    if (clip) bb.clip = &cl;
+    // (ev_xfree: this device copy of the input may be overwritten once the block has read it)
+    rc = flight_launch(c, c->bgraph[which][slot], c->bgraph2[which][slot], bb, p, geo, split ? -1 : 0, allowed, split, slot,
+                       pinned_in ? c->ev_xfree[which] : nullptr);
+    if (rc) return rc;
+    flight_fill(c, f, p, geo, lay, 0, clip);
     c->have_xc = true;
     return MFB_OK;
 }
@@ -2612,6 +2624,20 @@ static void fill_result(mfb_block_result *r, const BlockScalars &hs, int mode, i
     r->band_len[0] = hs.band_len[0];
     r->band_len[1] = hs.band_len[1];
 }
+// One record of a collected flight to the caller: the first n symbol decisions, centres and magnitudes, the two SNR windows, the scalars
+static void record_unpack(const BlockFlight &f, const uint8_t *h, const BlockScalars &hs, int n, mfb_block_result *r, int32_t *sym, int32_t *cen,
+                          float *mag, float *bands_c64) {
+    const RecordLayout &l = f.lay;
+    memcpy(sym, h + l.sym, (size_t)n * sizeof(int));
+    memcpy(cen, h + l.cen, (size_t)n * sizeof(int));
+    memcpy(mag, h + l.mag, (size_t)n * sizeof(float));
+    if (f.mode == MFB_BLOCK_SEARCH && f.bcap > 0) {
+        const int l0 = hs.band_len[0] < f.bcap ? hs.band_len[0] : f.bcap, l1 = hs.band_len[1] < f.bcap ? hs.band_len[1] : f.bcap;
+        memcpy(bands_c64, h + l.bands, (size_t)l0 * sizeof(cf));
+        memcpy(bands_c64 + (size_t)2 * f.bcap, h + l.bands + (size_t)f.bcap * sizeof(cf), (size_t)l1 * sizeof(cf));
+    }
+    fill_result(r, hs, f.mode, f.shift);
+}
 
 // Collect: wait for the flight's event, hand the results out.
 static int block_end(mfb_ctx *c, int slot, mfb_block_result *r, int32_t *sym, int32_t *cen, float *mag, float *bands_c64) {
@@ -2624,7 +2650,7 @@ static int block_end(mfb_ctx *c, int slot, mfb_block_result *r, int32_t *sym, in
     f.active = false;
     const uint8_t *h = c->h_blk[slot];
     BlockScalars hs;
-    memcpy(&hs, h + f.off[0], sizeof(hs));
+    memcpy(&hs, h + f.lay.scalars, sizeof(hs));
     int n = hs.count;
     if (n > f.nthreads) {
         // rate fallback (k* == 0 -> spSym = 10, DB:737-740; unreachable while the rate window starts above bin 0): the
@@ -2643,15 +2669,7 @@ static int block_end(mfb_ctx *c, int slot, mfb_block_result *r, int32_t *sym, in
         if (rc) return rc;
         n = f.nthreads;
     }
-    memcpy(sym, h + f.off[1], (size_t)n * sizeof(int));
-    memcpy(cen, h + f.off[2], (size_t)n * sizeof(int));
-    memcpy(mag, h + f.off[3], (size_t)n * sizeof(float));
-    if (f.mode == MFB_BLOCK_SEARCH && f.bcap > 0) {
-        const int l0 = hs.band_len[0] < f.bcap ? hs.band_len[0] : f.bcap, l1 = hs.band_len[1] < f.bcap ? hs.band_len[1] : f.bcap;
-        memcpy(bands_c64, h + f.off[4], (size_t)l0 * sizeof(cf));
-        memcpy(bands_c64 + (size_t)2 * f.bcap, h + f.off[4] + (size_t)f.bcap * sizeof(cf), (size_t)l1 * sizeof(cf));
-    }
-    fill_result(r, hs, f.mode, f.shift);
+    record_unpack(f, h, hs, n, r, sym, cen, mag, bands_c64);
     return MFB_OK;
 }
 
@@ -2707,56 +2725,47 @@ extern "C" int mfb_set_batch_overlap(mfb_ctx *c, int on) {
     }
     return MFB_OK;
 }
+// Device buffers whose addresses recorded graphs hold grow as a group: wait for what uses them, drop the graphs (epoch), free, allocate.
+// The capacity is 0 -- and the pointers of whatever is missing null -- until all of the group exist again.
+struct GrowBuf {
+    void **p;
+    size_t bytes;
+};
+template <class Cap>
+static int grow_buffers(mfb_ctx *c, Cap *cap, Cap want, std::initializer_list<GrowBuf> bufs) {
+    HIPCHK(sync_streams(c));
+    ++c->epoch;
+    for (const GrowBuf &b : bufs) {
+        if (*b.p) HIPCHK(hipFree(*b.p));
+        *b.p = nullptr;
+    }
+    *cap = 0;
+    for (const GrowBuf &b : bufs) HIPCHK(dev_alloc(b.p, b.bytes));
+    *cap = want;
+    return MFB_OK;
+}
 static int batch_reserve(mfb_ctx *c, int nb, size_t rec) {
-    if (nb > c->bat_cap) {
-        HIPCHK(sync_streams(c));
-        ++c->epoch;        // recorded graphs hold the old addresses
-        void **bufs[] = {(void **)&c->d_Xb, (void **)&c->d_xcb, (void **)&c->d_Pb, (void **)&c->d_envb, (void **)&c->d_sumb, (void **)&c->d_resb,
-                         (void **)&c->d_crb};
-        for (void **b : bufs) {
-            if (*b) HIPCHK(hipFree(*b));
-            *b = nullptr;
-        }
-        c->bat_cap = 0;
-        const size_t nbN = (size_t)nb * c->N;
-        HIPCHK(dev_alloc((void **)&c->d_Xb, nbN * sizeof(cf)));
-        HIPCHK(dev_alloc((void **)&c->d_xcb, nbN * c->M * sizeof(cf)));
-        HIPCHK(dev_alloc((void **)&c->d_Pb, nbN * sizeof(cf)));
-        HIPCHK(dev_alloc((void **)&c->d_envb, nbN * sizeof(float)));
-        HIPCHK(dev_alloc((void **)&c->d_sumb, (size_t)nb * c->Dtot * c->M * sizeof(float)));
-        HIPCHK(dev_alloc((void **)&c->d_resb, (size_t)nb * 2 * sizeof(float)));
-        HIPCHK(dev_alloc((void **)&c->d_crb, (size_t)nb * 3 * sizeof(float)));
-        c->bat_cap = nb;
-    }
-    if ((size_t)nb > c->z_rows) {       // the plain forward transforms of the batch take one row of the intermediate each
-        HIPCHK(sync_streams(c));
-        ++c->epoch;
-        if (c->d_Z) HIPCHK(hipFree(c->d_Z));
-        c->d_Z = nullptr;
-        c->z_rows = 0;
-        HIPCHK(dev_alloc((void **)&c->d_Z, (size_t)nb * c->N * sizeof(cf)));
-        c->z_rows = (size_t)nb;
-    }
-    if (rec * nb > c->batout_cap) {
-        HIPCHK(sync_streams(c));
-        ++c->epoch;
-        if (c->d_batout) HIPCHK(hipFree(c->d_batout));
-        if (c->d_batout2) HIPCHK(hipFree(c->d_batout2));
-        c->d_batout = c->d_batout2 = nullptr;
-        c->batout_cap = 0;
-        HIPCHK(dev_alloc((void **)&c->d_batout, rec * nb));
-        HIPCHK(dev_alloc((void **)&c->d_batout2, rec * nb));
-        c->batout_cap = rec * nb;
-    }
-    if (batch_split(c) && (size_t)nb > c->z2_rows) {       // part 2's transforms (the envelopes' spectra) get an intermediate of their own
-        HIPCHK(sync_streams(c));
-        ++c->epoch;
-        if (c->d_Z2) HIPCHK(hipFree(c->d_Z2));
-        c->d_Z2 = nullptr;
-        c->z2_rows = 0;
-        HIPCHK(dev_alloc((void **)&c->d_Z2, (size_t)nb * c->N * sizeof(cf)));
-        c->z2_rows = (size_t)nb;
-    }
+    int rc;
+    const size_t nbN = (size_t)nb * c->N;
+    if (nb > c->bat_cap &&
+        (rc = grow_buffers(c, &c->bat_cap, nb,
+                           {{(void **)&c->d_Xb, nbN * sizeof(cf)},
+                            {(void **)&c->d_xcb, nbN * c->M * sizeof(cf)},
+                            {(void **)&c->d_Pb, nbN * sizeof(cf)},
+                            {(void **)&c->d_envb, nbN * sizeof(float)},
+                            {(void **)&c->d_sumb, (size_t)nb * c->Dtot * c->M * sizeof(float)},
+                            {(void **)&c->d_resb, (size_t)nb * 2 * sizeof(float)},
+                            {(void **)&c->d_crb, (size_t)nb * 3 * sizeof(float)}})))
+        return rc;
+    // the plain forward transforms of the batch take one row of the intermediate each
+    if ((size_t)nb > c->z_rows && (rc = grow_buffers(c, &c->z_rows, (size_t)nb, {{(void **)&c->d_Z, nbN * sizeof(cf)}}))) return rc;
+    // the two flights' records (the next batch's search writes its picks while this one's records are still read)
+    if (rec * nb > c->batout_cap &&
+        (rc = grow_buffers(c, &c->batout_cap, rec * nb, {{(void **)&c->d_batout, rec * nb}, {(void **)&c->d_batout2, rec * nb}})))
+        return rc;
+    // part 2's transforms (the envelopes' spectra) get an intermediate of their own
+    if (batch_split(c) && (size_t)nb > c->z2_rows && (rc = grow_buffers(c, &c->z2_rows, (size_t)nb, {{(void **)&c->d_Z2, nbN * sizeof(cf)}})))
+        return rc;
     return MFB_OK;
 }
 
@@ -2808,18 +2817,12 @@ extern "C" int mfb_receive_blocks_begin(mfb_ctx *c, const mfb_block_params *p, i
     if (c->path != MFB_PATH_SEGMENT || (p->mode == MFB_BLOCK_SEARCH && c->search_mode != MFB_SEARCH_TRANSFORMS)) return MFB_ERR_UNSUPPORTED;
     BlockFlight &f = c->flight[slot];
     if (f.active) return MFB_ERR_STATE;
-    const int bcap = p->mode == MFB_BLOCK_SEARCH ? p->band_capacity : 0;
-    const int capacity = p->max_symbols < c->cap ? p->max_symbols : c->cap;
-    int nthreads = p->k_offset + p->k_len + 1;
-    if (nthreads > capacity) nthreads = capacity;
-    const size_t core = blkout_bytes(bcap, nthreads);
+    const BlockGeom geo = block_geom(c, p);
+    // the stream stages' outputs go behind the core record (record_layout.hpp)
     // (fixed shift: the S-band back end; with its peak clip on, k_stream_tag adds the clipped-peak tags behind the alignment)
     const bool stages = c->st_on && nblocks <= 64;
-    // stream-stage outputs behind the core record: kept bits | kept centres | trust bytes (uint8[nthreads] each), the block's
-    // tail (post, end), the sync hits (idx | score per template)
-    const size_t ext_bytes = 3 * align16((size_t)nthreads) + STREAM_POST_MAX + STREAM_END_MAX +
-                             (size_t)STREAM_MAX_TMPL * 2 * STREAM_MAX_HITS * sizeof(int32_t) + align16(STREAM_EDGE_CANDS * sizeof(StreamEdge));
-    const size_t rec = core + (stages ? ext_bytes : 0);
+    const RecordLayout lay = rec_layout(geo.bcap, geo.nthreads, stages);
+    const size_t rec = lay.bytes;
     if ((rc = batch_reserve(c, nblocks > c->win_blocks ? nblocks : (c->win_blocks > 0 ? c->win_blocks : nblocks), rec))) return rc;
     if ((rc = staging_reserve(c, slot, rec * nblocks))) return rc;
     if (!c->ev_blk[slot]) HIPCHK(hipEventCreateWithFlags(&c->ev_blk[slot], hipEventDisableTiming));
@@ -2829,7 +2832,7 @@ extern "C" int mfb_receive_blocks_begin(mfb_ctx *c, const mfb_block_params *p, i
     // (the two flights' records live in buffers of their own: the next batch's pick writes into its records while this batch's
     // are still being read on the other stream)
     BlkBufs bb{nblocks, win_in ? (const cf *)c->d_win[which] : (const cf *)p->device_block, stride, c->d_Xb, c->d_sumb, c->d_resb, c->d_xcb,
-               c->d_envb, c->d_Pb, c->d_crb, slot ? c->d_batout2 : c->d_batout, rec, stages ? core : 0, parity, nullptr};
+               c->d_envb, c->d_Pb, c->d_crb, slot ? c->d_batout2 : c->d_batout, lay, true, parity, nullptr};
     // peak clip: the window's blocks are clipped into the flight's buffer (stride N), which the transforms and part 2 then read;
     // the window itself -- where neighbouring blocks share their overlap -- stays as it is
     const bool clip = c->clip_scale > 0.f;
@@ -2840,60 +2843,17 @@ extern "C" int mfb_receive_blocks_begin(mfb_ctx *c, const mfb_block_params *p, i
         bb.xstride = c->N;
         bb.clip = &cl;
     }
-    int shift = p->mode == MFB_BLOCK_FIXED_SHIFT ? ((p->fixed_shift % c->N) + c->N) % c->N : 0;
     const bool allowed = win_in && graphs_allowed() && !c->prof;
     mfb_block_params q = *p;
     q.block_stride = stride;
     const int gi = nblocks <= WG_NB ? nblocks : 0;
-    if (!batch_split(c)) {
-        rc = graph_or_launch(c, c->wgraph[which][slot][parity][gi], &q, nblocks, allowed,
-                             [&]() { return block_enqueue(c, &q, bb, c->h_blk[slot], nthreads, bcap, capacity, &shift); });
-        if (rc) return rc;
-        HIPCHK(hipEventRecord(c->ev_blk[slot], c->stream));
-        if (win_in) HIPCHK(hipEventRecord(c->ev_wfree[which], c->stream));
-    } else {
-        // part 1 on the handle's stream, part 2 behind it on the second stream: the NEXT batch's part 1 is enqueued behind this
-        // one's part 1 only, and runs beside this batch's part 2
-        if ((rc = second_stream(c, slot))) return rc;
-        rc = graph_or_launch(c, c->wgraph[which][slot][parity][gi], &q, nblocks, allowed,
-                             [&]() { return block_enqueue_p1(c, &q, bb, nthreads, bcap); });
-        if (rc) return rc;
-        HIPCHK(hipEventRecord(c->ev_p1[slot], c->stream));
-        hipStream_t s1 = c->stream;
-        c->stream = c->s2;            // every launch helper enqueues on c->stream
-        c->use_z2 = true;
-        c->s2_busy = true;
-        hipError_t e = hipStreamWaitEvent(c->s2, c->ev_p1[slot], 0);
-        rc = e != hipSuccess ? MFB_ERR_HIP
-                             : graph_or_launch(c, c->wgraph2[which][slot][parity][gi], &q, nblocks, allowed,
-                                               [&]() { return block_enqueue_p2(c, &q, bb, c->h_blk[slot], nthreads, bcap, capacity, &shift); });
-        if (!rc) {
-            e = hipEventRecord(c->ev_blk[slot], c->s2);
-            if (e == hipSuccess && win_in) e = hipEventRecord(c->ev_wfree[which], c->s2);
-            if (e != hipSuccess) rc = MFB_ERR_HIP;
-        }
-        c->stream = s1;
-        c->use_z2 = false;
-        if (rc) return rc;
-    }
+    const bool split = batch_split(c);
+    if (split && (rc = second_stream(c, slot))) return rc;
+    rc = flight_launch(c, c->wgraph[which][slot][parity][gi], c->wgraph2[which][slot][parity][gi], bb, &q, geo, nblocks, allowed, split, slot,
+                       win_in ? c->ev_wfree[which] : nullptr);
+    if (rc) return rc;
     if (stages) c->carry_cur = 1 - parity;        // this batch's tail and ring are the next batch's start
-    const size_t sym_off = BLK_HEAD + align16((size_t)2 * bcap * sizeof(cf)), arr = align16((size_t)nthreads * sizeof(int));
-    f.off[0] = 0;
-    f.off[4] = BLK_HEAD;
-    f.off[1] = sym_off;
-    f.off[2] = sym_off + arr;
-    f.off[3] = sym_off + 2 * arr;
-    f.active = true;
-    f.mode = p->mode;
-    f.nthreads = nthreads;
-    f.bcap = bcap;
-    f.shift = shift;
-    f.seq = ++c->blk_seq;
-    f.op = p->op;
-    f.nb = nblocks;
-    f.rec = rec;
-    f.ext = stages ? core : 0;
-    f.clip = clip;
+    flight_fill(c, f, p, geo, lay, nblocks, clip);
     c->last_batch_blocks = p->mode == MFB_BLOCK_SEARCH ? nblocks : 0;
     // the handle's one-block buffers (spectrum, matched-filter outputs) hold nothing of this batch
     c->have_xc = false;
@@ -2911,9 +2871,9 @@ extern "C" int mfb_receive_blocks_end(mfb_ctx *c, int slot, mfb_block_result *re
     f.active = false;
     int rc = MFB_OK;
     for (int b = 0; b < f.nb; ++b) {
-        const uint8_t *h = c->h_blk[slot] + (size_t)b * f.rec;
+        const uint8_t *h = c->h_blk[slot] + (size_t)b * f.lay.bytes;
         BlockScalars hs;
-        memcpy(&hs, h + f.off[0], sizeof(hs));
+        memcpy(&hs, h + f.lay.scalars, sizeof(hs));
         int n = hs.count;
         // (the rate fallback k* == 0 -> spSym = 10 could ask for more symbols than the rate window admits; it cannot occur while
         // the window starts above bin 0, and a batch has no second pass to fetch them: the record's symbols are delivered)
@@ -2922,20 +2882,41 @@ extern "C" int mfb_receive_blocks_end(mfb_ctx *c, int slot, mfb_block_result *re
             rc = MFB_ERR_UNSUPPORTED;
         }
         if (n > symbol_stride) return MFB_ERR_ARG;
-        memcpy(sym + (size_t)b * symbol_stride, h + f.off[1], (size_t)n * sizeof(int));
-        memcpy(cen + (size_t)b * symbol_stride, h + f.off[2], (size_t)n * sizeof(int));
-        memcpy(mag + (size_t)b * symbol_stride, h + f.off[3], (size_t)n * sizeof(float));
-        if (f.mode == MFB_BLOCK_SEARCH && f.bcap > 0) {
-            const int l0 = hs.band_len[0] < f.bcap ? hs.band_len[0] : f.bcap, l1 = hs.band_len[1] < f.bcap ? hs.band_len[1] : f.bcap;
-            float *dst = bands_c64 + (size_t)b * 4 * f.bcap;
-            memcpy(dst, h + f.off[4], (size_t)l0 * sizeof(cf));
-            memcpy(dst + (size_t)2 * f.bcap, h + f.off[4] + (size_t)f.bcap * sizeof(cf), (size_t)l1 * sizeof(cf));
-        }
-        fill_result(&results[b], hs, f.mode, f.shift);
+        const size_t at = (size_t)b * symbol_stride;
+        record_unpack(f, h, hs, n, &results[b], sym + at, cen + at, mag + at, bands_c64 + (size_t)b * 4 * f.bcap);
     }
     return rc;
 }
 
+// What the callers of mfb_receive_blocks_end_record and mfb_debug_stream_stages learn about the records they were handed
+static void fill_layout(mfb_record_layout *lay, const mfb_ctx *c, const RecordLayout &l, int nb, int symbols, int bcap, int mode, int shift) {
+    memset(lay, 0, sizeof(*lay));
+    lay->nblocks = nb;
+    lay->record_bytes = (int64_t)l.bytes;
+    lay->scalars_bytes = (int32_t)sizeof(BlockScalars);
+    lay->symbols = symbols;
+    lay->band_capacity = bcap;
+    lay->mode = mode;
+    lay->fixed_shift = shift;
+    lay->off_bands = (int64_t)l.bands;
+    lay->off_sym = (int64_t)l.sym;
+    lay->off_cen = (int64_t)l.cen;
+    lay->off_mag = (int64_t)l.mag;
+    if (l.stages) {
+        lay->stream_stages = 1;
+        lay->off_bits = (int64_t)l.bits;
+        lay->off_centres_u8 = (int64_t)l.cenw;
+        lay->off_trust = (int64_t)l.trust;
+        lay->off_post = (int64_t)l.post;
+        lay->off_end = (int64_t)l.end;
+        lay->off_hits = (int64_t)l.hits;
+        lay->off_edges = (int64_t)l.edges;
+        lay->edge_candidates = STREAM_EDGE_CANDS;
+        lay->edge_hits = STREAM_EDGE_HITS;
+        lay->max_hits = STREAM_MAX_HITS;
+        lay->templates = c->st.K;
+    }
+}
 // The whole batch as it came off the device: nb records of `rec` bytes copied into the caller's buffer, and where things are
 // inside a record.  The caller (the Python host) reads scalars and arrays in place -- one copy per batch instead of a dozen
 // small ones per block.
@@ -2943,44 +2924,19 @@ extern "C" int mfb_receive_blocks_end_record(mfb_ctx *c, int slot, void *dst, si
     if (!c || slot < 0 || slot > 1 || !dst || !lay) return MFB_ERR_ARG;
     BlockFlight &f = c->flight[slot];
     if (!f.active || !f.nb) return MFB_ERR_STATE;
-    if (capacity < f.rec * (size_t)f.nb) {
+    const size_t rec = f.lay.bytes;
+    if (capacity < rec * (size_t)f.nb) {
         // too small: say what the batch needs (nblocks * record_bytes) and leave it in flight for the caller's second attempt
         memset(lay, 0, sizeof(*lay));
         lay->nblocks = f.nb;
-        lay->record_bytes = (int64_t)f.rec;
+        lay->record_bytes = (int64_t)rec;
         return MFB_ERR_ARG;
     }
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipEventSynchronize(c->ev_blk[slot]));
     f.active = false;
-    memcpy(dst, c->h_blk[slot], f.rec * (size_t)f.nb);
-    memset(lay, 0, sizeof(*lay));
-    lay->nblocks = f.nb;
-    lay->record_bytes = (int64_t)f.rec;
-    lay->scalars_bytes = (int32_t)sizeof(BlockScalars);
-    lay->symbols = f.nthreads;
-    lay->band_capacity = f.bcap;
-    lay->mode = f.mode;
-    lay->fixed_shift = f.shift;
-    lay->off_bands = (int64_t)f.off[4];
-    lay->off_sym = (int64_t)f.off[1];
-    lay->off_cen = (int64_t)f.off[2];
-    lay->off_mag = (int64_t)f.off[3];
-    if (f.ext) {
-        const size_t a1 = align16((size_t)f.nthreads);
-        lay->stream_stages = 1;
-        lay->off_bits = (int64_t)f.ext;
-        lay->off_centres_u8 = (int64_t)(f.ext + a1);
-        lay->off_trust = (int64_t)(f.ext + 2 * a1);
-        lay->off_post = (int64_t)(f.ext + 3 * a1);
-        lay->off_end = lay->off_post + STREAM_POST_MAX;
-        lay->off_hits = lay->off_end + STREAM_END_MAX;
-        lay->off_edges = lay->off_hits + (int64_t)STREAM_MAX_TMPL * 2 * STREAM_MAX_HITS * (int64_t)sizeof(int32_t);
-        lay->edge_candidates = STREAM_EDGE_CANDS;
-        lay->edge_hits = STREAM_EDGE_HITS;
-        lay->max_hits = STREAM_MAX_HITS;
-        lay->templates = c->st.K;
-    }
+    memcpy(dst, c->h_blk[slot], rec * (size_t)f.nb);
+    fill_layout(lay, c, f.lay, f.nb, f.nthreads, f.bcap, f.mode, f.shift);
     return MFB_OK;
 }
 
@@ -3092,41 +3048,27 @@ extern "C" int mfb_debug_stream_stages(mfb_ctx *c, int nb, int symbols, const in
     for (int s = 0; s < 2; ++s)
         if (c->flight[s].active) return MFB_ERR_STATE;
     HIPCHK(hipSetDevice(c->device));
-    const size_t core = blkout_bytes(0, symbols), a1 = align16((size_t)symbols);
-    const size_t ext_bytes = 3 * a1 + STREAM_POST_MAX + STREAM_END_MAX + (size_t)STREAM_MAX_TMPL * 2 * STREAM_MAX_HITS * sizeof(int32_t) +
-                             align16(STREAM_EDGE_CANDS * sizeof(StreamEdge));
-    const size_t rec = core + ext_bytes;
+    const RecordLayout l = rec_layout(0, symbols, true);
+    const size_t rec = l.bytes;
     if (capacity < rec * (size_t)nb) return MFB_ERR_ARG;
     int rc = batch_reserve(c, nb > c->bat_cap ? nb : (c->bat_cap > 0 ? c->bat_cap : nb), rec);
     if (rc) return rc;
     if (rec * nb > c->batout_cap) return MFB_ERR_ALLOC;
     std::vector<uint8_t> h(rec * (size_t)nb, 0);
-    const size_t off_sym = BLK_HEAD, arr = align16((size_t)symbols * sizeof(int));
     for (int b = 0; b < nb; ++b) {
         if (counts[b] < 0 || counts[b] > symbols) return MFB_ERR_ARG;
         uint8_t *r = h.data() + (size_t)b * rec;
         BlockScalars sc;
         memset(&sc, 0, sizeof(sc));
         sc.count = counts[b];
-        memcpy(r, &sc, sizeof(sc));
-        memcpy(r + off_sym, sym + (size_t)b * symbols, (size_t)symbols * sizeof(int));
-        memcpy(r + off_sym + arr, cen + (size_t)b * symbols, (size_t)symbols * sizeof(int));
-        memcpy(r + off_sym + 2 * arr, mag + (size_t)b * symbols, (size_t)symbols * sizeof(float));
+        memcpy(r + l.scalars, &sc, sizeof(sc));
+        memcpy(r + l.sym, sym + (size_t)b * symbols, (size_t)symbols * sizeof(int));
+        memcpy(r + l.cen, cen + (size_t)b * symbols, (size_t)symbols * sizeof(int));
+        memcpy(r + l.mag, mag + (size_t)b * symbols, (size_t)symbols * sizeof(float));
     }
     HIPCHK(hipMemcpyAsync(c->d_batout, h.data(), h.size(), hipMemcpyHostToDevice, c->stream));
     StreamArgs sa = c->st;
-    sa.rec0 = c->d_batout;
-    sa.rec = rec;
-    sa.off_sym = off_sym;
-    sa.off_cen = off_sym + arr;
-    sa.off_mag = off_sym + 2 * arr;
-    sa.off_bits = core;
-    sa.off_cenw = core + a1;
-    sa.off_trust = core + 2 * a1;
-    sa.off_post = core + 3 * a1;
-    sa.off_end = sa.off_post + STREAM_POST_MAX;
-    sa.off_hits = sa.off_end + STREAM_END_MAX;
-    sa.off_edges = sa.off_hits + (size_t)STREAM_MAX_TMPL * 2 * STREAM_MAX_HITS * sizeof(int32_t);
+    stream_records(sa, c->d_batout, l);
     sa.nb = nb;
     sa.nsym = symbols;
     sa.carry_in = c->d_carry[c->carry_cur];
@@ -3141,28 +3083,7 @@ extern "C" int mfb_debug_stream_stages(mfb_ctx *c, int nb, int symbols, const in
     c->carry_cur = 1 - c->carry_cur;
     HIPCHK(hipMemcpyAsync(dst, c->d_batout, rec * (size_t)nb, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(sync_streams(c));
-    memset(lay, 0, sizeof(*lay));
-    lay->nblocks = nb;
-    lay->record_bytes = (int64_t)rec;
-    lay->scalars_bytes = (int32_t)sizeof(BlockScalars);
-    lay->symbols = symbols;
-    lay->mode = MFB_BLOCK_SEARCH;
-    lay->off_bands = BLK_HEAD;
-    lay->off_sym = (int64_t)sa.off_sym;
-    lay->off_cen = (int64_t)sa.off_cen;
-    lay->off_mag = (int64_t)sa.off_mag;
-    lay->stream_stages = 1;
-    lay->off_bits = (int64_t)sa.off_bits;
-    lay->off_centres_u8 = (int64_t)sa.off_cenw;
-    lay->off_trust = (int64_t)sa.off_trust;
-    lay->off_post = (int64_t)sa.off_post;
-    lay->off_end = (int64_t)sa.off_end;
-    lay->off_hits = (int64_t)sa.off_hits;
-    lay->off_edges = (int64_t)sa.off_edges;
-    lay->edge_candidates = STREAM_EDGE_CANDS;
-    lay->edge_hits = STREAM_EDGE_HITS;
-    lay->max_hits = STREAM_MAX_HITS;
-    lay->templates = c->st.K;
+    fill_layout(lay, c, l, nb, symbols, 0, MFB_BLOCK_SEARCH, 0);
     return MFB_OK;
 }
 
