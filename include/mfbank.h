@@ -53,7 +53,9 @@ int mfb_abi_version(void);   /* 2: search paths, mfb_xcorr; 3: mfb_set_search_mo
                               * mfb_export_rows_async, mfb_sync_find_packed; 5: mfb_debug_block_scalars; 6: mfb_receive_blocks_*,
                               * mfb_window_buffer, mfb_block_params.block_stride; 7: mfb_set_stream_stages, mfb_stream_seed,
                               * mfb_receive_blocks_end_record; 8: mfb_hostcopy_*; 9: mfb_set_batch_overlap, mfb_get_batch_scores, mfb_get_search_info, mfb_set_cu_share, mfb_receive_blocks_end_record
-                              * reports the size it needs */
+                              * reports the size it needs.  Calls added without a change to an existing prototype do not bump it: a caller
+                              * finds them by symbol (dlsym) -- mfb_set_sample_format, mfb_get_sample_format, mfb_input_buffer_raw,
+                              * mfb_window_buffer_raw, mfb_debug_unpack */
 
 /* Create a handle on HIP device `device` for blocks of N = 2^log2N samples, `num_dopplers`
  * Doppler bins plus `doppler_offset` leading noise-reference bins (DB:150-159), M matched
@@ -288,7 +290,8 @@ int mfb_receive_blocks_begin(mfb_ctx *ctx, const mfb_block_params *params, int n
  * evenly -- workgroups of the long-filter kernel (76 KiB of LDS) find no room beside the short-filter kernel's (52 KiB): 16 % / 85 % of
  * their stand-alone rates at BASELINE C5 --; with (0, 2) and (1, 2) each runs on its own half, whatever the other does
  * (bench.py: c5_*_shared).  The handle's own stream is re-created with a CU mask (a stream set with mfb_set_stream is the caller's
- * business); nothing may be in flight. */
+ * business); nothing may be in flight.  Known limit: the stream of the host-to-device copies carries no CU mask, so the conversion
+ * of integer samples behind such a copy (mfb_set_sample_format: a few microseconds) runs outside the handle's share. */
 int mfb_set_cu_share(mfb_ctx *ctx, int part, int parts);
 /* How the segment search of the next block will run (no reference counterpart; bench.py's flop count reads it): filter_side = 1 when
  * the Doppler shift sits on the FILTERS' side -- the segment of samples is transformed once for `bins_per_forward` neighbouring bins
@@ -508,6 +511,41 @@ int mfb_profile_enable(mfb_ctx *ctx, int on);
 int mfb_profile_read(mfb_ctx *ctx, int counts[2], float total_ms[2]);
 /* Block until all work enqueued on the handle's stream has finished (the reference: cuda.Context.synchronize(), DB:651). */
 int mfb_sync(mfb_ctx *ctx);
+
+#define MFB_SAMPLES_CF32 0   /* interleaved float pairs */
+#define MFB_SAMPLES_SC16 1   /* interleaved int16 I, Q, native endianness */
+#define MFB_SAMPLES_SC8  2   /* interleaved int8 I, Q */
+/* Integer IQ samples as the radio delivers them, converted on the device.  The reference's demodulator takes complex64 only
+ * (integers off a socket appear in its tree only as decoded bits: np.frombuffer(..., np.int8), examples/benchmark/bench_modem.py:134):
+ * whoever feeds it converts on the host first and copies 8 bytes per sample into the page-locked buffer (DB:456-457, DP:256,287,337).
+ * mfb_set_sample_format sets the element type of the handle's page-locked inputs -- the two one-block input buffers and the two
+ * batch windows: the caller fills them with interleaved int16 or int8 I, Q pairs, 4 or 2 bytes per sample cross the host link, and a
+ * kernel behind the copy (csrc/unpack_kernels.hpp) writes complex64 = integer * scale into the device copy that everything else
+ * reads.  Blocks in device memory (MFB_INPUT_DEVICE) and mfb_upload_device stay complex64 always.
+ *   scale      the value of one integer step.  0: full scale 1.0 (2^-15 for sc16, 2^-7 for sc8); else a positive, finite power of
+ *              two (frexpf mantissa exactly 0.5) for which every sample stays a normal float: MFB_ERR_ARG otherwise.  An int16 /
+ *              int8 converts to float32 without rounding and a multiplication by a power of two is exact, so every sample is bit for
+ *              bit what raw.astype(float32) * scale gives on the host -- and so is everything computed from it.  Other gains are
+ *              refused for that reason.
+ * Unknown format: MFB_ERR_ARG; anything in flight: MFB_ERR_STATE; after a refusal the previous format stays in force.  A change
+ * synchronises, drops the recorded graphs, restarts the peak-clip chain (as mfb_restart_peak_clip) and zero-fills the page-locked
+ * inputs.  While the format is not CF32: mfb_input_buffer, mfb_input_buffer2 and mfb_window_buffer return MFB_ERR_STATE (use the
+ * _raw calls below), mfb_upload_from (complex64 host data) returns MFB_ERR_UNSUPPORTED; mfb_upload, the pinned buffer, honours
+ * the format. */
+int mfb_set_sample_format(mfb_ctx *ctx, int format, float scale);
+/* What is in force (any pointer may be NULL): 8, 4 or 2 bytes per sample.  No reference counterpart (complex64 only, DB:456-457). */
+int mfb_get_sample_format(mfb_ctx *ctx, int *format, float *scale, int *bytes_per_sample);
+/* The page-locked input buffer of mfb_input_buffer (which = 0) / mfb_input_buffer2 (which = 1) typed by the format in force:
+ * N samples of it, *bytes = N * bytes_per_sample (the allocation keeps its complex64 size; only those bytes are used).  Replaces
+ * pagelocked_empty(...) DB:456-457 / get_signalBufferHostPointer DB:1055-1060 for integer samples. */
+int mfb_input_buffer_raw(mfb_ctx *ctx, int which, void **host, size_t *bytes);
+/* mfb_window_buffer likewise: the window of max_blocks * block_stride + (N - block_stride) samples of the format in force -- the
+ * destination of the loop's copies (DP:256,287,337). */
+int mfb_window_buffer_raw(mfb_ctx *ctx, int which, int max_blocks, int block_stride, void **host, size_t *bytes);
+/* Test seam of the conversion: the kernel behind the copies on nsamples host samples of `format` (SC16 / SC8; scale as for
+ * mfb_set_sample_format), out_c64 = nsamples complex64.  The product paths do not use it.  No reference counterpart (its
+ * callers convert with numpy on the host). */
+int mfb_debug_unpack(int device, int format, float scale, const void *raw, size_t nsamples, float *out_c64);
 
 /* A host copy worker for the receive loop: the reference's loop copies every chunk of samples twice on its one thread, into the
  * ring buffer (sigFIFO.py:62-84) and from there into the page-locked input buffer (`raw[ov:] = sigIn.getBlock()`, DP:287,337).

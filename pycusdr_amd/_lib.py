@@ -138,6 +138,11 @@ PROTOTYPES = {
     'mfb_profile_enable': (_i, [_vp, _i]),
     'mfb_profile_read': (_i, [_vp, C.POINTER(_i), _fp]),
     'mfb_sync': (_i, [_vp]),
+    'mfb_set_sample_format': (_i, [_vp, _i, C.c_float]),
+    'mfb_get_sample_format': (_i, [_vp, C.POINTER(_i), _fp, C.POINTER(_i)]),
+    'mfb_input_buffer_raw': (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
+    'mfb_window_buffer_raw': (_i, [_vp, _i, _i, _i, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
+    'mfb_debug_unpack': (_i, [_i, _i, C.c_float, _vp, C.c_size_t, _vp]),
     'mfb_hostcopy_create': (_i, [C.POINTER(_vp)]),
     'mfb_hostcopy_submit': (_i, [_vp, _vp, _vp, C.c_size_t]),
     'mfb_hostcopy_drain': (_i, [_vp]),

@@ -55,6 +55,7 @@
 #include "energy_kernels.hpp"
 #include "stream_kernels.hpp"
 #include "clip_kernels.hpp"
+#include "unpack_kernels.hpp"
 #include "hostcopy.hpp"
 #include "record_layout.hpp"
 
@@ -214,6 +215,12 @@ struct mfb_ctx {
     int *d_clipw = nullptr;              // per-wave counts and tail flags [2][clip_ws_cap][N / 1024]
     ClipTail *d_ctail = nullptr;         // the last clipped block's tail (stable address: captured graphs hold it)
     int ctail_cap = 0;
+    // integer IQ samples in the page-locked inputs (unpack_kernels.hpp, mfb_set_sample_format): the raw bytes land in a staging
+    // buffer of the input's own and k_unpack writes complex64 into the device copy everything else reads
+    int fmt = MFB_SAMPLES_CF32;
+    float fmt_scale = 1.f;
+    void *d_raw[4] = {};                 // [input buffer 0 / 1, window 0 / 1]: allocated at the first copy that needs it
+    size_t raw_cap[4] = {};
 };
 
 #define HIPCHK(x)                                                                            \
@@ -654,6 +661,7 @@ extern "C" int mfb_destroy(mfb_ctx *c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->s2) (void)hipStreamSynchronize(c->s2);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
+    if (c->in_stream) (void)hipStreamSynchronize(c->in_stream);
     void *bufs[] = {c->d_uniq, c->d_rep, c->d_x,  c->d_X,    c->d_masks, c->d_Z,   c->d_xc,  c->d_P,   c->d_env, c->d_shifts, c->d_tw1,
                     c->d_tw2, c->d_twLo, c->d_twHi,  c->d_part, c->d_sum, c->d_res, c->d_cr,  c->d_sym,    c->d_cen, c->d_mag,
                     c->d_G, c->d_twL, c->d_Gb, c->d_pow, c->d_W, c->d_blkout, c->d_blkout2, c->d_x2,
@@ -708,6 +716,8 @@ extern "C" int mfb_destroy(mfb_ctx *c) {
     if (c->d_clips) (void)hipFree(c->d_clips);
     if (c->d_clipw) (void)hipFree(c->d_clipw);
     if (c->d_ctail) (void)hipFree(c->d_ctail);
+    for (void *p : c->d_raw)
+        if (p) (void)hipFree(p);
     delete c->bank;
     delete c;
     return MFB_OK;
@@ -1105,6 +1115,7 @@ extern "C" int mfb_set_shifts(mfb_ctx *c, const int32_t *shifts, int count) {
 
 extern "C" int mfb_input_buffer(mfb_ctx *c, float **p) {
     if (!c || !p) return MFB_ERR_ARG;
+    if (c->fmt != MFB_SAMPLES_CF32) return MFB_ERR_STATE;      // the buffer holds integers: mfb_input_buffer_raw
     *p = (float *)c->h_in;
     return MFB_OK;
 }
@@ -1433,10 +1444,53 @@ static int enable_mirror(mfb_ctx *c) {
     return MFB_OK;
 }
 
+// ---- integer IQ samples (unpack_kernels.hpp) ---------------------------------------------------------------------------------
+static int fmt_bytes(int fmt) { return fmt == MFB_SAMPLES_SC16 ? 4 : fmt == MFB_SAMPLES_SC8 ? 2 : (int)sizeof(cf); }
+// The value of one integer step: 0 = full scale 1.0 (2^-15 / 2^-7), else a positive power of two that keeps every product a normal
+// float -- the whole reason the conversion is exact (include/mfbank.h).  Returns 0 for anything else.
+static float fmt_scale_checked(int fmt, float scale) {
+    if (scale == 0.f) return fmt == MFB_SAMPLES_SC16 ? 0x1p-15f : 0x1p-7f;
+    int e = 0;
+    if (!(scale > 0.f) || isinf(scale) || frexpf(scale, &e) != 0.5f) return 0.f;
+    const float top = scale * (fmt == MFB_SAMPLES_SC16 ? 32768.f : 128.f);
+    if (scale < 0x1p-126f || isinf(top)) return 0.f;
+    return scale;
+}
+static int launch_unpack(int fmt, const void *raw, cf *dst, size_t samples, float scale, hipStream_t s) {
+    const dim3 grid((unsigned)unpack_blocks(fmt, samples)), block(UNPACK_THREADS);
+    if (fmt == MFB_SAMPLES_SC16) hipLaunchKernelGGL(k_unpack<UNPACK_SC16>, grid, block, 0, s, raw, (float2 *)dst, samples, scale);
+    else hipLaunchKernelGGL(k_unpack<UNPACK_SC8>, grid, block, 0, s, raw, (float2 *)dst, samples, scale);
+    HIPCHK(hipGetLastError());
+    return MFB_OK;
+}
+// `samples` raw samples of a page-locked input to its staging buffer `rawslot` and, right behind the copy on the same stream,
+// as complex64 into dst.  The staging buffer is made (or grown: everything that may read the old one is waited for) here.
+static int raw_copy_unpack(mfb_ctx *c, const void *src, cf *dst, size_t samples, int rawslot, hipStream_t s) {
+    const size_t bytes = samples * (size_t)fmt_bytes(c->fmt), need = (bytes + 15) & ~(size_t)15;
+    if (c->raw_cap[rawslot] < need) {
+        if (c->d_raw[rawslot]) {
+            HIPCHK(sync_streams(c));
+            if (c->in_stream) HIPCHK(hipStreamSynchronize(c->in_stream));
+            HIPCHK(hipFree(c->d_raw[rawslot]));
+            c->d_raw[rawslot] = nullptr;
+            c->raw_cap[rawslot] = 0;
+        }
+        HIPCHK(dev_alloc(&c->d_raw[rawslot], need));
+        c->raw_cap[rawslot] = need;
+    }
+    HIPCHK(hipMemcpyAsync(c->d_raw[rawslot], src, bytes, hipMemcpyHostToDevice, s));
+    return launch_unpack(c->fmt, c->d_raw[rawslot], dst, samples, c->fmt_scale, s);
+}
+
 extern "C" int mfb_upload(mfb_ctx *c) {
     if (!c) return MFB_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpyAsync(c->d_x, c->h_in, (size_t)c->N * sizeof(cf), hipMemcpyHostToDevice, c->stream));
+    if (c->fmt != MFB_SAMPLES_CF32) {
+        const int rc = raw_copy_unpack(c, c->h_in, c->d_x, (size_t)c->N, 0, c->stream);
+        if (rc) return rc;
+    } else {
+        HIPCHK(hipMemcpyAsync(c->d_x, c->h_in, (size_t)c->N * sizeof(cf), hipMemcpyHostToDevice, c->stream));
+    }
     c->d_in = c->d_x;
     int rc = before_fft(c);
     if (rc) return rc;
@@ -1450,6 +1504,7 @@ extern "C" int mfb_upload(mfb_ctx *c) {
 
 extern "C" int mfb_upload_from(mfb_ctx *c, const float *host, int N) {
     if (!c || !host || N != c->N) return MFB_ERR_ARG;
+    if (c->fmt != MFB_SAMPLES_CF32) return MFB_ERR_UNSUPPORTED;      // complex64 host data; the pinned buffer holds integers
     if ((const void *)host != (const void *)c->h_in) {
         HIPCHK(hipSetDevice(c->device));
         HIPCHK(sync_streams(c));  // pinned buffer may still be in flight
@@ -2381,7 +2436,10 @@ static int block_enqueue(mfb_ctx *c, const mfb_block_params *p, const BlkBufs &b
 // last block that read that device copy is done -- i.e. while the block before this one is still being searched -- and the
 // handle's stream picks it up with an event.  (With one device buffer and one stream the copy of an 8 MiB block, 0.15 ms,
 // sat between two searches.)
-static int input_copy(mfb_ctx *c, const cf *src, cf *dst, size_t samples, hipEvent_t *ev_h2d, hipEvent_t *ev_free, int which) {
+// Under an integer sample format (mfb_set_sample_format) the raw bytes go to the input's staging buffer `rawslot` and k_unpack
+// writes the complex64 device copy right behind the copy, on the input stream too: whatever waits for the event reads what it
+// always read.  (Copy and unpack stay outside the recorded graphs, which begin behind that event.)
+static int input_copy(mfb_ctx *c, const cf *src, cf *dst, size_t samples, hipEvent_t *ev_h2d, hipEvent_t *ev_free, int which, int rawslot) {
     if (!src || !dst) return MFB_ERR_STATE;
     if (!c->in_stream) HIPCHK(hipStreamCreateWithFlags(&c->in_stream, hipStreamNonBlocking));
     for (int i = 0; i < 2; ++i) {
@@ -2392,13 +2450,18 @@ static int input_copy(mfb_ctx *c, const cf *src, cf *dst, size_t samples, hipEve
         }
     }
     HIPCHK(hipStreamWaitEvent(c->in_stream, ev_free[which], 0));
-    HIPCHK(hipMemcpyAsync(dst, src, samples * sizeof(cf), hipMemcpyHostToDevice, c->in_stream));
+    if (c->fmt != MFB_SAMPLES_CF32) {
+        const int rc = raw_copy_unpack(c, src, dst, samples, rawslot, c->in_stream);
+        if (rc) return rc;
+    } else {
+        HIPCHK(hipMemcpyAsync(dst, src, samples * sizeof(cf), hipMemcpyHostToDevice, c->in_stream));
+    }
     HIPCHK(hipEventRecord(ev_h2d[which], c->in_stream));
     HIPCHK(hipStreamWaitEvent(c->stream, ev_h2d[which], 0));
     return MFB_OK;
 }
 static int block_input_copy(mfb_ctx *c, int which) {
-    return input_copy(c, which ? c->h_in2 : c->h_in, which ? c->d_x2 : c->d_x, (size_t)c->N, c->ev_h2d, c->ev_xfree, which);
+    return input_copy(c, which ? c->h_in2 : c->h_in, which ? c->d_x2 : c->d_x, (size_t)c->N, c->ev_h2d, c->ev_xfree, which, which);
 }
 
 // A block whose input is one of the handle's two page-locked buffers is the same sequence of launches with the same
@@ -2769,7 +2832,7 @@ static int batch_reserve(mfb_ctx *c, int nb, size_t rec) {
     return MFB_OK;
 }
 
-extern "C" int mfb_window_buffer(mfb_ctx *c, int which, int max_blocks, int block_stride, float **host_c64) {
+static int window_buffer(mfb_ctx *c, int which, int max_blocks, int block_stride, void **host_c64) {
     if (!c || !host_c64 || which < 0 || which > 1 || max_blocks < 1 || max_blocks > 1024 || block_stride < 1 || block_stride > c->N)
         return MFB_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
@@ -2782,8 +2845,11 @@ extern "C" int mfb_window_buffer(mfb_ctx *c, int which, int max_blocks, int bloc
         for (int i = 0; i < 2; ++i) {
             if (c->h_win[i]) HIPCHK(hipHostFree(c->h_win[i]));
             if (c->d_win[i]) HIPCHK(hipFree(c->d_win[i]));
+            if (c->d_raw[2 + i]) HIPCHK(hipFree(c->d_raw[2 + i]));
             c->h_win[i] = nullptr;
             c->d_win[i] = nullptr;
+            c->d_raw[2 + i] = nullptr;
+            c->raw_cap[2 + i] = 0;
         }
         c->win_blocks = max_blocks;
         c->win_stride = block_stride;
@@ -2794,8 +2860,21 @@ extern "C" int mfb_window_buffer(mfb_ctx *c, int which, int max_blocks, int bloc
         memset(c->h_win[which], 0, bytes);
         HIPCHK(dev_alloc((void **)&c->d_win[which], bytes));
     }
-    *host_c64 = (float *)c->h_win[which];
+    *host_c64 = c->h_win[which];
     return MFB_OK;
+}
+extern "C" int mfb_window_buffer(mfb_ctx *c, int which, int max_blocks, int block_stride, float **host_c64) {
+    if (c && c->fmt != MFB_SAMPLES_CF32) return MFB_ERR_STATE;      // the windows hold integers: mfb_window_buffer_raw
+    void *p = nullptr;
+    const int rc = window_buffer(c, which, max_blocks, block_stride, host_c64 ? &p : nullptr);
+    if (!rc) *host_c64 = (float *)p;
+    return rc;
+}
+extern "C" int mfb_window_buffer_raw(mfb_ctx *c, int which, int max_blocks, int block_stride, void **host, size_t *bytes) {
+    if (!bytes) return MFB_ERR_ARG;
+    const int rc = window_buffer(c, which, max_blocks, block_stride, host);
+    if (!rc) *bytes = (size_t)window_samples(c, c->win_blocks) * (size_t)fmt_bytes(c->fmt);
+    return rc;
 }
 
 extern "C" int mfb_receive_blocks_begin(mfb_ctx *c, const mfb_block_params *p, int nblocks, int slot) {
@@ -2826,7 +2905,7 @@ extern "C" int mfb_receive_blocks_begin(mfb_ctx *c, const mfb_block_params *p, i
     if ((rc = batch_reserve(c, nblocks > c->win_blocks ? nblocks : (c->win_blocks > 0 ? c->win_blocks : nblocks), rec))) return rc;
     if ((rc = staging_reserve(c, slot, rec * nblocks))) return rc;
     if (!c->ev_blk[slot]) HIPCHK(hipEventCreateWithFlags(&c->ev_blk[slot], hipEventDisableTiming));
-    if (win_in && (rc = input_copy(c, c->h_win[which], c->d_win[which], (size_t)(nblocks * stride + (c->N - stride)), c->ev_wh2d, c->ev_wfree, which)))
+    if (win_in && (rc = input_copy(c, c->h_win[which], c->d_win[which], (size_t)(nblocks * stride + (c->N - stride)), c->ev_wh2d, c->ev_wfree, which, 2 + which)))
         return rc;
     const int parity = c->carry_cur;
     // (the two flights' records live in buffers of their own: the next batch's pick writes into its records while this batch's
@@ -3143,16 +3222,91 @@ extern "C" int mfb_debug_block_scalars(mfb_ctx *c, int n, const float *picks, co
     return MFB_OK;
 }
 
-extern "C" int mfb_input_buffer2(mfb_ctx *c, float **p) {
-    if (!c || !p) return MFB_ERR_ARG;
+static int input_buffer2(mfb_ctx *c) {
     if (!c->h_in2) {
         HIPCHK(hipSetDevice(c->device));
         HIPCHK(hipHostMalloc((void **)&c->h_in2, (size_t)c->N * sizeof(cf), hipHostMallocDefault));
         memset(c->h_in2, 0, (size_t)c->N * sizeof(cf));
         if (!c->d_x2) HIPCHK(dev_alloc((void **)&c->d_x2, (size_t)c->N * sizeof(cf)));
     }
+    return MFB_OK;
+}
+extern "C" int mfb_input_buffer2(mfb_ctx *c, float **p) {
+    if (!c || !p) return MFB_ERR_ARG;
+    if (c->fmt != MFB_SAMPLES_CF32) return MFB_ERR_STATE;      // the buffer holds integers: mfb_input_buffer_raw
+    const int rc = input_buffer2(c);
+    if (rc) return rc;
     *p = (float *)c->h_in2;
     return MFB_OK;
+}
+extern "C" int mfb_input_buffer_raw(mfb_ctx *c, int which, void **host, size_t *bytes) {
+    if (!c || !host || !bytes || which < 0 || which > 1) return MFB_ERR_ARG;
+    if (which) {
+        const int rc = input_buffer2(c);
+        if (rc) return rc;
+    }
+    *host = which ? c->h_in2 : c->h_in;
+    *bytes = (size_t)c->N * (size_t)fmt_bytes(c->fmt);
+    return MFB_OK;
+}
+
+extern "C" int mfb_set_sample_format(mfb_ctx *c, int format, float scale) {
+    if (!c || (format != MFB_SAMPLES_CF32 && format != MFB_SAMPLES_SC16 && format != MFB_SAMPLES_SC8)) return MFB_ERR_ARG;
+    float sc = 1.f;
+    if (format == MFB_SAMPLES_CF32) {
+        if (scale != 0.f && scale != 1.f) return MFB_ERR_ARG;      // complex64 is taken as it is
+    } else if ((sc = fmt_scale_checked(format, scale)) == 0.f) {
+        return MFB_ERR_ARG;
+    }
+    if (c->flight[0].active || c->flight[1].active) return MFB_ERR_STATE;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(sync_streams(c));
+    if (c->in_stream) HIPCHK(hipStreamSynchronize(c->in_stream));
+    ++c->epoch;                  // no recorded graph outlives the element type of its input
+    c->fmt = format;
+    c->fmt_scale = sc;
+    c->clip_restart = true;      // the chain's tail belongs to samples of the other type's stream
+    // what the buffers held means nothing as the new type
+    if (c->h_in) memset(c->h_in, 0, (size_t)c->N * sizeof(cf));
+    if (c->h_in2) memset(c->h_in2, 0, (size_t)c->N * sizeof(cf));
+    for (int i = 0; i < 2; ++i)
+        if (c->h_win[i]) memset(c->h_win[i], 0, (size_t)window_samples(c, c->win_blocks) * sizeof(cf));
+    return MFB_OK;
+}
+extern "C" int mfb_get_sample_format(mfb_ctx *c, int *format, float *scale, int *bytes_per_sample) {
+    if (!c) return MFB_ERR_ARG;
+    if (format) *format = c->fmt;
+    if (scale) *scale = c->fmt_scale;
+    if (bytes_per_sample) *bytes_per_sample = fmt_bytes(c->fmt);
+    return MFB_OK;
+}
+// Test seam: k_unpack on nsamples host samples, the complex64 result back to the host.  The product paths do not come here.
+extern "C" int mfb_debug_unpack(int device, int format, float scale, const void *raw, size_t nsamples, float *out_c64) {
+    if (!raw || !out_c64 || nsamples < 1 || nsamples > ((size_t)1 << 28) || (format != MFB_SAMPLES_SC16 && format != MFB_SAMPLES_SC8))
+        return MFB_ERR_ARG;
+    const float sc = fmt_scale_checked(format, scale);
+    if (sc == 0.f) return MFB_ERR_ARG;
+    int ndev = 0;
+    HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return MFB_ERR_ARG;
+    HIPCHK(hipSetDevice(device));
+    const size_t bytes = nsamples * (size_t)fmt_bytes(format);
+    void *d_in = nullptr;
+    cf *d_out = nullptr;
+    int rc = MFB_OK;
+    auto body = [&]() -> int {
+        HIPCHK(hipMalloc(&d_in, (bytes + 15) & ~(size_t)15));
+        HIPCHK(hipMalloc((void **)&d_out, nsamples * sizeof(cf)));
+        HIPCHK(hipMemcpy(d_in, raw, bytes, hipMemcpyHostToDevice));
+        const int r = launch_unpack(format, d_in, d_out, nsamples, sc, nullptr);
+        if (r) return r;
+        HIPCHK(hipMemcpy(out_c64, d_out, nsamples * sizeof(cf), hipMemcpyDeviceToHost));
+        return MFB_OK;
+    };
+    rc = body();
+    if (d_in) (void)hipFree(d_in);
+    if (d_out) (void)hipFree(d_out);
+    return rc;
 }
 
 extern "C" int mfb_find_centres(mfb_ctx *c, float spSym, float offset, int op, int count, int32_t *sym, int32_t *cen,

@@ -14,6 +14,7 @@ class Demodulator(_HostDriver):
         """Clip interference peaks in place (their indices are kept for the trust tagging), then
         forward-FFT the block.  The first, second and fourth results are the constants the
         reference returns in place of a Doppler estimate."""
+        self._refuse_host_clip()       # (integer sample formats: the device clips, beginBlock / beginBlocks)
         if self._device_clip:
             # clipped here: the device takes the block as it is (after device-clipped blocks, the overlap is their clipped tail)
             self._armDeviceClip(False, samples)

@@ -15,7 +15,9 @@ from enum import Enum
 
 import numpy as np
 
-from ..mfbank import MFBank
+import math
+
+from ..mfbank import MFBank, SAMPLE_FORMATS
 
 log = logging.getLogger('pycusdr_amd.demodulator')
 
@@ -70,6 +72,54 @@ def fill_peak_gaps(hot, Nfft, min_gap):
             marks[hot[gi]:hot[gi] + gaps[gi]] = 1
         return np.where(marks == 1)[0]
     return hot.copy()
+
+
+def sample_format_config(hip_cfg, backend, shard=None):
+    """``"HIP": {"sample_format": "cf32" | "sc16" | "sc8", "sample_scale": <power of two>}`` of a radio's GPU settings ->
+    (MFB_SAMPLES_* code, numpy dtype of the samples, value of one integer step).  Pure: needs no device.  ValueError for an unknown
+    name; a scale that is not a positive, finite power of two inside float32's normal range (the device's conversion is exact for
+    those and no others: include/mfbank.h); an integer format together with sharding (dist.py moves complex64 tensors); an integer
+    format on a back end that clips on the host (every back end but UHF, unless ``"device_clip": true`` on the one-call path): the
+    host's clip writes clipped floats back into the samples, and integers cannot hold them."""
+    name = hip_cfg.get('sample_format', 'cf32')
+    if not isinstance(name, str) or name not in SAMPLE_FORMATS:
+        raise ValueError('"sample_format": %r is none of %s' % (name, sorted(SAMPLE_FORMATS)))
+    code, dtype, step = SAMPLE_FORMATS[name]
+    scale = hip_cfg.get('sample_scale', None)
+    if name == 'cf32':
+        if scale not in (None, 1, 1.0):
+            raise ValueError('"sample_scale" applies to the integer sample formats, not to cf32')
+        return code, dtype, 1.0
+    if scale is not None:
+        try:
+            step = float(scale)
+        except (TypeError, ValueError):
+            raise ValueError('"sample_scale": %r is not a number' % (scale,)) from None
+        top = step * (32768.0 if name == 'sc16' else 128.0)
+        if not (math.isfinite(step) and step > 0 and math.frexp(step)[0] == 0.5 and step >= 2.0 ** -126 and top < 2.0 ** 128):
+            raise ValueError('"sample_scale": %r is not a power of two (within float32\'s normal range): the conversion on the '
+                             'device is exact for powers of two only' % (scale,))
+    if shard is not None:
+        raise ValueError('"sample_format": %r is not supported together with sharding (the ranks exchange complex64)' % name)
+    if backend != 'UHF' and not (bool(hip_cfg.get('device_clip', False)) and bool(hip_cfg.get('one_call', True))):
+        raise ValueError('"sample_format": %r on the %s back end needs "device_clip": true: the host\'s peak clip writes clipped '
+                         'floats back into the samples' % (name, backend))
+    return code, dtype, step
+
+
+def as_samples(chunk, dtype):
+    """A chunk of samples of an integer format as an (n, 2) array of (I, Q) rows: shape (n, 2) or flat 2n, reshaped as a view and
+    never copied or converted -- TypeError for any other dtype (the point of the integer formats is that no conversion runs on
+    the receive loop's thread)."""
+    a = chunk if isinstance(chunk, np.ndarray) else np.asarray(chunk)
+    if a.dtype != dtype:
+        raise TypeError('chunk of %s handed to a receiver of %s samples: convert at the source or configure "sample_format"'
+                        % (a.dtype, np.dtype(dtype)))
+    if a.ndim == 2 and a.shape[1] == 2:
+        return a
+    if a.ndim == 1 and a.size % 2 == 0:
+        return a.reshape(-1, 2)
+    raise ValueError('integer samples come as (n, 2) or flat 2n, got shape %s' % (a.shape,))
 
 
 def _first_true(mask):
@@ -136,6 +186,9 @@ class Demodulator:
             raise ValueError('[{}]: the size of the input signal has to be divisible by {}'.format(
                 radioName, self.numThreadsS))
         device = cuda_cfg.get('device', 0)
+        # integer IQ samples in the page-locked inputs, converted on the device: "HIP": {"sample_format": ..., "sample_scale": ...}
+        self.sample_format = confGPU.get('HIP', {}).get('sample_format', 'cf32')
+        _, self.sample_dtype, self.sample_scale = sample_format_config(confGPU.get('HIP', {}), self.backend, shard)
 
         # filters and LUTs from the protocol plugin
         try:
@@ -180,6 +233,8 @@ class Demodulator:
         # optional search settings next to the reference's "CUDA" block (where it keeps batchSize / streams, DB:171-178):
         #   "HIP": {"search_path": "auto|segment|twopass", "search_basis": "filters|span", "search_mode": "transforms|energy"}
         hip_cfg = confGPU.get('HIP', {})
+        if self.sample_format != 'cf32':
+            self.bank.set_sample_format(self.sample_format, self.sample_scale)
         if 'search_path' in hip_cfg:
             self.bank.set_search_path(hip_cfg['search_path'])
         if 'search_basis' in hip_cfg:
@@ -243,7 +298,8 @@ class Demodulator:
             pass
 
     def get_signalBufferHostPointer(self):
-        """Writable page-locked complex64[N] the caller fills in place (reference DB:1055-1060)."""
+        """Writable page-locked complex64[N] the caller fills in place (reference DB:1055-1060) -- int16 / int8 [N][2] under an
+        integer sample format."""
         return self.bank.input
 
     # ---- input ---------------------------------------------------------------------------------
@@ -257,6 +313,9 @@ class Demodulator:
             self.bank.upload_device(device_ptr)
             return
         if self.shard is None:
+            if self.sample_format != 'cf32':
+                self._fill_input(samples)
+                samples = None
             self.bank.upload(samples)
             return
         sh = self.shard
@@ -272,7 +331,24 @@ class Demodulator:
         else:
             sh.broadcast_block(self.bank)
 
+    def _fill_input(self, samples):
+        """Integer sample formats: ``samples`` -- the page-locked input buffer itself, or samples of its dtype -- into that buffer."""
+        raw = self.bank.input
+        if samples is None or samples is raw:
+            return
+        samples = as_samples(samples, self.sample_dtype)
+        if not (samples.ctypes.data == raw.ctypes.data and samples.size == raw.size):
+            if samples.shape != raw.shape:
+                raise ValueError('a block is %d samples, got %d' % (len(raw), len(samples)))
+            np.copyto(raw, samples)
+
+    def _refuse_host_clip(self):
+        if self.sample_format != 'cf32':
+            raise TypeError('[%s]: the host\'s peak clip needs complex64 samples; with "sample_format": "%s" blocks are clipped on '
+                            'the device (beginBlock / beginBlocks)' % (self.radioName, self.sample_format))
+
     def thresholdInput(self, samples):
+        self._refuse_host_clip()
         self._thresholdInput(samples)
 
     def _thresholdInput(self, samples):
@@ -299,6 +375,8 @@ class Demodulator:
             if on:
                 self.bank.set_peak_clip(self.peakThresholdScale, self.sigOverlap)
             else:
+                if samples is not None:
+                    self._refuse_host_clip()        # (the clipped tail is complex64: an integer block cannot take it)
                 tail = self.bank.peak_clip_tail(self.sigOverlap) if samples is not None else None
                 if tail is not None:
                     samples[:self.sigOverlap] = tail
@@ -306,6 +384,7 @@ class Demodulator:
             self._clip_armed = on
 
     def uploadAndFindUHF(self, samples):
+        self._refuse_host_clip()
         self._thresholdInput(samples)
         self.uploadToGPU(samples)
         return self._findUHF(samples)
@@ -316,6 +395,9 @@ class Demodulator:
         ``demodulateDevice``."""
         if device_ptr is not None:
             source = 'device'
+        elif self.sample_format != 'cf32':
+            self._fill_input(samples)
+            source = 'pinned'
         else:
             raw = self.bank.input
             if samples is not raw and not (isinstance(samples, np.ndarray) and samples.ctypes.data == raw.ctypes.data

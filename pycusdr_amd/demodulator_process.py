@@ -13,6 +13,7 @@ import time
 import numpy as np
 
 from . import demodulator as demod_backends
+from .demodulator.demodulator_base import as_samples
 
 log = logging.getLogger('pycusdr_amd.demodulator_process')
 
@@ -52,7 +53,13 @@ class MarkedSource:
 
 class DemodulatorRunner:
     """One receive channel, in-process.  ``feed(new_samples)`` takes exactly
-    ``blockSize - overlap`` new complex64 samples and returns the result dict of that block."""
+    ``blockSize - overlap`` new complex64 samples and returns the result dict of that block.
+
+    With ``"HIP": {"sample_format": "sc16" | "sc8"}`` the samples are the radio's integers -- int16 / int8 (I, Q) pairs, converted on
+    the device: ``self.raw`` and every chunk have that dtype, shape (n, 2) or flat 2n (taken as a view); a chunk of another dtype
+    raises TypeError, it is never converted here.  Device-resident blocks (``feed_resident*``) stay complex64."""
+
+    dtype, _integer = np.dtype(np.complex64), False       # the samples' element type (set from the demodulator's sample format)
 
     def __init__(self, conf, protocol, radio, shard=None):
         self.conf, self.protocol, self.radioName = conf, protocol, radio
@@ -81,6 +88,17 @@ class DemodulatorRunner:
         self.demod = self.demodulator.Demodulator(conf, protocol, radio, shard=shard)
         self.raw = self.demod.get_signalBufferHostPointer()
         self.raw[:] = 0
+        self.dtype = np.dtype(getattr(self.demod, 'sample_dtype', np.complex64))       # of self.raw and of every chunk
+        self._integer = self.dtype != np.complex64
+
+    def _chunk(self, chunk):
+        """A chunk of a stream on its way into a block buffer or window: as it is (complex64 receivers: the assignment converts,
+        as ever), or the integer format's (n, 2) view."""
+        return as_samples(chunk, self.dtype) if self._integer else chunk
+
+    def _slice(self, chunk):
+        """A slice of new samples as ``run`` takes it: complex64 (converted, as ever), or the integer format's (n, 2) view."""
+        return as_samples(chunk, self.dtype) if self._integer else np.asarray(chunk, dtype=np.complex64)
 
     def close(self):
         hc = getattr(self, '_copier', None)
@@ -136,6 +154,8 @@ class DemodulatorRunner:
         raw = self.raw
         in_place = new_samples is None
         if not in_place:
+            if self._integer:
+                new_samples = as_samples(new_samples, self.dtype)
             if len(new_samples) != self.samplesPerSlice:
                 raise ValueError(f'expected {self.samplesPerSlice} new samples per block, got {len(new_samples)}')
             raw[self.overlap:] = new_samples
@@ -179,6 +199,8 @@ class DemodulatorRunner:
         """``feed_device`` in two halves: enqueue the block's device work and return at once (``feed_device_end`` collects it).
         One block in flight per runner.  Falls back to the synchronous call where the one-call block path is not in use (STX,
         Doppler-sharded handles, ``"one_call": false``)."""
+        if self._integer:
+            new_samples = as_samples(new_samples, self.dtype)
         if len(new_samples) != self.samplesPerSlice:
             raise ValueError(f'expected {self.samplesPerSlice} new samples per block, got {len(new_samples)}')
         if not self._one_block_path():
@@ -208,6 +230,8 @@ class DemodulatorRunner:
 
     def skip_block(self, new_samples):
         """A block another rank processes: keep the overlap carry and the block counter in step."""
+        if self._integer:
+            new_samples = as_samples(new_samples, self.dtype)
         if len(new_samples) != self.samplesPerSlice:
             raise ValueError(f'expected {self.samplesPerSlice} new samples per block, got {len(new_samples)}')
         ov, sps = self.overlap, self.samplesPerSlice
@@ -273,7 +297,11 @@ class DemodulatorRunner:
         Pipelined form: the stages run in threads, so blocks travel as copies through a SigFIFO."""
         if pipelined:
             from .sigFIFO import SigFIFO
-            fifo = SigFIFO((c for c in chunk_source if c is not None), self.samplesPerSlice)
+            if self._integer:
+                fifo = SigFIFO((as_samples(c, self.dtype) for c in chunk_source if c is not None), self.samplesPerSlice,
+                               dtype=self.dtype, row=(2,))
+            else:
+                fifo = SigFIFO((c for c in chunk_source if c is not None), self.samplesPerSlice)
 
             def blocks():
                 while True:
@@ -285,7 +313,8 @@ class DemodulatorRunner:
         from .sigFIFO import BlockAssembler
         if not (overlapped and self._one_block_path()):
             asm = BlockAssembler(self.raw, self.overlap)
-            return self.run((None for chunk in chunk_source if chunk is not None for _ in asm.push(chunk)), sink=sink, decoder=decoder)
+            return self.run((None for chunk in chunk_source if chunk is not None for _ in asm.push(self._chunk(chunk))), sink=sink,
+                            decoder=decoder)
         # how many blocks per device call: the caller's word, else the configuration's, else ("auto") whatever the source has ready.
         # A source that marks where it would block (MarkedSource) says so itself; a plain iterator cannot be asked, so the loop
         # watches how long each chunk takes to come (``_run_stream_batched``, adaptive): chunks that are there at once (a
@@ -371,7 +400,7 @@ class DemodulatorRunner:
                         collect(fl)
                     finish_search()
                     continue
-                for _ in asm.push(chunk):
+                for _ in asm.push(self._chunk(chunk)):
                     self.demod.beginBlock(cur, source=names[cur])
                     started = (cur, self.count, time.time())
                     self.count += 1
@@ -579,7 +608,7 @@ class DemodulatorRunner:
                             return 'end'
                         if chunk is None:
                             return 'dry'
-                        rest[0] = chunk if isinstance(chunk, np.ndarray) else np.asarray(chunk)
+                        rest[0] = self._chunk(chunk if isinstance(chunk, np.ndarray) else np.asarray(chunk))
                         live = adaptive and since_wait[0] * len(rest[0]) < self.samplesPerSlice
                     n = asm.take(rest[0])
                     rest[0] = rest[0][n:] if n < len(rest[0]) else None
@@ -683,7 +712,7 @@ class DemodulatorRunner:
 
         if not pipelined:
             for chunk in sample_source:       # None: the block sits in self.raw already (run_stream)
-                d = self.feed(None if chunk is None else np.asarray(chunk, dtype=np.complex64))
+                d = self.feed(None if chunk is None else self._slice(chunk))
                 decode(d)
                 report(d)
             return results, packets
@@ -717,7 +746,7 @@ class DemodulatorRunner:
             for chunk in sample_source:
                 if failure:
                     return
-                q_in.put(np.array(chunk, dtype=np.complex64))      # own copy: the ring buffer reuses its storage
+                q_in.put(np.array(self._slice(chunk)))      # own copy: the ring buffer reuses its storage
 
         def decoder_body():
             while True:

@@ -26,10 +26,33 @@ BLOCK_SCALARS = np.dtype({
     'itemsize': 168})
 
 
+# sample formats of the page-locked inputs (mfb_set_sample_format): name -> (MFB_SAMPLES_*, numpy dtype, default value of one step)
+SAMPLE_FORMATS = {'cf32': (0, np.dtype(np.complex64), 1.0), 'sc16': (1, np.dtype(np.int16), 2.0 ** -15), 'sc8': (2, np.dtype(np.int8), 2.0 ** -7)}
+
+
+def debug_unpack(raw, fmt, scale=None, device=0, out=None):
+    """Test seam (mfb_debug_unpack): the device's integer -> complex64 conversion of ``raw`` -- int16 ('sc16') or int8 ('sc8') of
+    shape (n, 2).  ``out``: a complex64 array of at least n elements to write into (the first n are written)."""
+    lib = _lib.load()
+    code, dt, _ = SAMPLE_FORMATS[fmt]
+    raw = np.ascontiguousarray(raw)
+    if raw.dtype != dt or raw.ndim != 2 or raw.shape[1] != 2:
+        raise TypeError(f'{fmt} samples are {dt} of shape (n, 2), got {raw.dtype} {raw.shape}')
+    n = len(raw)
+    if out is None:
+        out = np.empty(n, np.complex64)
+    if out.dtype != np.complex64 or not out.flags.c_contiguous or out.size < n:
+        raise ValueError('out: contiguous complex64 of at least n elements')
+    _lib.check(lib.mfb_debug_unpack(int(device), code, C.c_float(0.0 if scale is None else float(scale)), _ptr(raw), n, _ptr(out)),
+               'mfb_debug_unpack')
+    return out
+
+
 class HostCopy:
     """The library's host copy worker (mfb_hostcopy_*): ``submit(dst, dst_off, src)`` queues ``dst[dst_off:dst_off + len(src)] = src``
     for a thread of its own and returns at once; ``drain()`` returns when every queued copy has been made.  Arrays handed to
-    ``submit`` are kept alive until then.  Plain host memory: no GPU involved."""
+    ``submit`` are kept alive until then.  Plain host memory: no GPU involved.  Offsets and lengths count ROWS of ``dst`` (one
+    complex64 sample, or one (I, Q) pair of an integer window of shape (samples, 2))."""
 
     def __init__(self):
         self._lib = _lib.load()
@@ -37,7 +60,7 @@ class HostCopy:
         _lib.check(self._lib.mfb_hostcopy_create(C.byref(h)), 'mfb_hostcopy_create')
         self._h = h
         self._held = []
-        self._base = {}              # id(dst) -> (address, itemsize): asking numpy for it costs as much as a small copy
+        self._base = {}              # id(dst) -> (address, bytes per row, dst): asking numpy for it costs as much as a small copy
 
     def submit(self, dst, dst_off, src):
         n = len(src)
@@ -48,7 +71,9 @@ class HostCopy:
         if base is None or base[2] is not dst:
             if not dst.flags.c_contiguous or not dst.flags.writeable:
                 raise ValueError('destination must be a writable contiguous array')
-            base = self._base[key] = (dst.ctypes.data, dst.itemsize, dst)
+            base = self._base[key] = (dst.ctypes.data, dst.itemsize * int(np.prod(dst.shape[1:], dtype=np.int64)), dst)
+        if src.shape[1:] != base[2].shape[1:]:
+            raise ValueError('source rows of shape %s into a destination of rows %s' % (src.shape[1:], base[2].shape[1:]))
         if src.dtype != dst.dtype or not src.flags.c_contiguous:
             src = np.ascontiguousarray(src, dtype=dst.dtype)
         if dst_off < 0 or dst_off + n > len(dst):
@@ -165,10 +190,44 @@ class MFBank:
         _lib.check(self._lib.mfb_create(C.byref(self._h), self.device, int(log2N), self.D, self.Doff, self.M,
                                         int(window_width), int(bool(sum_all_masks)), int(code_search_mask_offset)),
                    'mfb_create')
-        buf = C.POINTER(C.c_float)()
-        _lib.check(self._lib.mfb_input_buffer(self._h, C.byref(buf)), 'mfb_input_buffer')
+        self._fmt = 'cf32'
         # writable complex64 view of the page-locked input buffer owned by the library
-        self.input = np.ctypeslib.as_array(buf, shape=(2 * self.N,)).view(np.complex64)
+        self.input = self._input_view(0)
+
+    def _typed(self, address, samples):
+        """``samples`` samples at ``address`` as the format in force types them: complex64 (samples,), or int16 / int8 (samples, 2)."""
+        dt = SAMPLE_FORMATS[self._fmt][1]
+        n = samples * (1 if self._fmt == 'cf32' else 2)
+        a = np.ctypeslib.as_array(C.cast(C.c_void_p(address), C.POINTER(C.c_uint8)), shape=(n * dt.itemsize,)).view(dt)
+        return a if self._fmt == 'cf32' else a.reshape(samples, 2)
+
+    def _input_view(self, which):
+        p, nbytes = C.c_void_p(), C.c_size_t()
+        _lib.check(self._lib.mfb_input_buffer_raw(self._h, which, C.byref(p), C.byref(nbytes)), 'mfb_input_buffer_raw')
+        return self._typed(p.value, self.N)
+
+    # -- integer IQ samples (mfb_set_sample_format) ------------------------------------------------
+    def set_sample_format(self, fmt, scale=None):
+        """Element type of the page-locked inputs -- ``input``, ``input2``, ``windows()``: 'cf32' (complex64, the default), 'sc16'
+        (int16 I, Q pairs) or 'sc8' (int8); the device converts behind the copy, sample = integer * ``scale`` (None: full scale
+        1.0; else a power of two -- the conversion is then exact).  The buffers are handed out again as arrays of the new type
+        (integer formats: shape (samples, 2)); views taken before the call must not be used any more.  Nothing may be in flight."""
+        if fmt not in SAMPLE_FORMATS:
+            raise ValueError(f'unknown sample format {fmt!r}: one of {sorted(SAMPLE_FORMATS)}')
+        _lib.check(self._lib.mfb_set_sample_format(self._h, SAMPLE_FORMATS[fmt][0], C.c_float(0.0 if scale is None else float(scale))),
+                   'mfb_set_sample_format')
+        self._fmt = fmt
+        self.input = self._input_view(0)
+        self._input2 = None
+        self._wins, self._win_key = None, None
+
+    @property
+    def sample_format(self):
+        """(name, numpy dtype, scale, bytes per sample) in force (mfb_get_sample_format)."""
+        f, sc, b = C.c_int(), C.c_float(), C.c_int()
+        _lib.check(self._lib.mfb_get_sample_format(self._h, C.byref(f), C.byref(sc), C.byref(b)), 'mfb_get_sample_format')
+        name = {v[0]: k for k, v in SAMPLE_FORMATS.items()}[f.value]
+        return name, SAMPLE_FORMATS[name][1], float(sc.value), int(b.value)
 
     # -- lifetime --------------------------------------------------------------------------------
     def close(self):
@@ -476,9 +535,7 @@ class MFBank:
         """The second page-locked input buffer: while the device works on the block in one buffer, the caller assembles
         the next block in the other (``begin_block(..., source='pinned2')``)."""
         if getattr(self, '_input2', None) is None:
-            buf = C.POINTER(C.c_float)()
-            _lib.check(self._lib.mfb_input_buffer2(self._h, C.byref(buf)), 'mfb_input_buffer2')
-            self._input2 = np.ctypeslib.as_array(buf, shape=(2 * self.N,)).view(np.complex64)
+            self._input2 = self._input_view(1)
         return self._input2
 
     def begin_block(self, slot, k_offset, k_len, spsym_min, op=0, snr_window=5, fixed_shift=None, source='pinned', device_ptr=None):
@@ -510,17 +567,18 @@ class MFBank:
     # -- B consecutive blocks per call -----------------------------------------------------------
     def windows(self, max_blocks, block_stride):
         """The two page-locked sample windows of the batched block path (mfb_window_buffer): each holds ``max_blocks``
-        consecutive blocks of the stream as ``max_blocks * block_stride + (N - block_stride)`` complex64 samples -- block b
-        starts at ``b * block_stride``, neighbours share their overlap.  Returns (window 0, window 1) as writable numpy
-        views; asking for another geometry re-allocates them."""
+        consecutive blocks of the stream as ``max_blocks * block_stride + (N - block_stride)`` samples (complex64, or (I, Q) rows of
+        the integer format in force) -- block b starts at ``b * block_stride``, neighbours share their overlap.  Returns (window 0,
+        window 1) as writable numpy views; asking for another geometry re-allocates them."""
         key = (int(max_blocks), int(block_stride))
         if getattr(self, '_win_key', None) != key:
             n = key[0] * key[1] + (self.N - key[1])
             wins = []
             for which in (0, 1):
-                buf = C.POINTER(C.c_float)()
-                _lib.check(self._lib.mfb_window_buffer(self._h, which, key[0], key[1], C.byref(buf)), 'mfb_window_buffer')
-                wins.append(np.ctypeslib.as_array(buf, shape=(2 * n,)).view(np.complex64))
+                p, nbytes = C.c_void_p(), C.c_size_t()
+                _lib.check(self._lib.mfb_window_buffer_raw(self._h, which, key[0], key[1], C.byref(p), C.byref(nbytes)),
+                           'mfb_window_buffer_raw')
+                wins.append(self._typed(p.value, n))
             self._wins, self._win_key = tuple(wins), key
         return self._wins
 

@@ -144,7 +144,7 @@ class WindowAssembler:
 
 
 class RingBuffer:
-    def __init__(self, outLen, bufLen=None, dtype=np.complex64):
+    def __init__(self, outLen, bufLen=None, dtype=np.complex64, row=()):
         self.outLen = outLen
         if bufLen is None:
             bufLen = 10 * outLen
@@ -152,7 +152,8 @@ class RingBuffer:
             raise IndexError('bufLen < outLen', 'Buffer size too small for expected output size')
         self.bufLen = bufLen
         self.dtype = dtype
-        self.buf = np.empty(self.bufLen, dtype=self.dtype)
+        # row: the shape of one sample -- () for complex64, (2,) for the (I, Q) rows of the integer sample formats
+        self.buf = np.empty((self.bufLen,) + tuple(row), dtype=self.dtype)
         self._written = 0          # samples stored / consumed since the last flush
         self._read = 0
 
@@ -214,11 +215,11 @@ class RingBuffer:
 class SigFIFO:
     """``getBlock()`` -> exactly ``reqDataSize`` samples, assembled from the chunks ``source`` yields."""
 
-    def __init__(self, source, reqDataSize, dtype=np.complex64):
+    def __init__(self, source, reqDataSize, dtype=np.complex64, row=()):
         self.blockSize = reqDataSize
         self.dtype = dtype
         self.source = iter(source)
-        self.buf = RingBuffer(self.blockSize, bufLen=self.blockSize * 2, dtype=dtype)     # sigFIFO.py:141
+        self.buf = RingBuffer(self.blockSize, bufLen=self.blockSize * 2, dtype=dtype, row=row)     # sigFIFO.py:141
         self._rest = None          # the part of an oversized chunk that has not gone in yet
 
     def getBlock(self):

@@ -2,11 +2,26 @@
 collected one batch behind, no host stages, no decoder -- what mfb_receive_blocks_begin/_end sustain when the host is not the
 bound (the receive loop in Python is: ~20 us of host work per block).  The A/B of the batch's two streams
 (MFB_BATCH_SPLIT=0/1, profiles/r06_chain.md).
-usage: python3 tools/batch_device_rate.py [log2N] [bins] [B] [batches] [stages 0|1] [overlap 0|1]"""
+usage: python3 tools/batch_device_rate.py [log2N] [bins] [B] [batches] [stages 0|1] [overlap 0|1] [--sample-format cf32|sc16|sc8] [--reps R]
+--sample-format: the windows hold the radio's integers (mfb_set_sample_format; the stream quantised with one step = 2^-11 / 2^-5),
+converted on the device behind the copy; --reps: timed repeats (default 3), the median is printed last."""
 import sys
 import time
 import numpy as np
 sys.path.insert(0, '.')
+
+
+def _option(name, default):
+    if name in sys.argv:
+        i = sys.argv.index(name)
+        value = sys.argv[i + 1]
+        del sys.argv[i:i + 2]
+        return value
+    return default
+
+
+fmt = _option('--sample-format', 'cf32')
+reps = int(_option('--reps', 3))
 from pycusdr_amd.hostcpu import quiet_blas  # noqa: E402
 quiet_blas()
 from pycusdr_amd import config as cfg, signals as sg  # noqa: E402
@@ -23,10 +38,16 @@ overlap = bool(int(sys.argv[6])) if len(sys.argv) > 6 else False
 N, ov = 1 << log2N, 1 << 10
 step = N - ov
 conf = cfg.bench_config('bench_GMSK', blockSize=log2N, doppCarrierSteps=D)
+bits = {'cf32': None, 'sc16': 11, 'sc8': 5}[fmt]
+if bits is not None:
+    conf['GPU']['UHF'].setdefault('HIP', {}).update(sample_format=fmt, sample_scale=2.0 ** -bits)
 p = loadProtocol('bench_GMSK')(conf=conf)
 run = DemodulatorRunner(conf, p, 'UHF-H')
 dec = Decoder(conf, p)
 sig = sg.s1_stream(2 * B, N, ov, 'GMSK', snr_db=12.0, seed=3)
+if bits is not None:
+    info = np.iinfo(run.dtype)
+    sig = np.clip(np.round(np.stack((sig.real, sig.imag), axis=1) * 2.0 ** bits), info.min, info.max).astype(run.dtype)
 run.demod.bank.set_batch_overlap(overlap)          # (MFB_BATCH_SPLIT in the environment overrides it)
 wins = run.demod.blockWindows(B)
 wins[0][:] = sig[:B * step + ov]
@@ -45,12 +66,13 @@ def loop(n):
 
 
 loop(8)              # graphs recorded, clock settled
-best = None
-for rep in range(3):
+rates = []
+for rep in range(reps):
     t0 = time.perf_counter()
     loop(nbat)
     dt = (time.perf_counter() - t0) / nbat
-    best = dt if best is None else min(best, dt)
-    print(f'N=2^{log2N} D={D} B={B} stages={int(stages)} overlap={int(overlap)}: {dt * 1e6:8.1f} us per batch, {dt / B * 1e6:6.2f} us per block, '
-          f'{B * step / dt / 1e6:8.1f} Msamples/s', flush=True)
+    rates.append(B * step / dt / 1e6)
+    print(f'N=2^{log2N} D={D} B={B} stages={int(stages)} overlap={int(overlap)} {fmt}: {dt * 1e6:8.1f} us per batch, {dt / B * 1e6:6.2f} us per block, '
+          f'{rates[-1]:8.1f} Msamples/s', flush=True)
+print(f'N=2^{log2N} D={D} B={B} stages={int(stages)} overlap={int(overlap)} {fmt}: median of {reps}: {float(np.median(rates)):8.1f} Msamples/s', flush=True)
 run.close()
