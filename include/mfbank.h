@@ -498,6 +498,76 @@ int mfb_sync_pinned_buffer(int device, size_t bytes, void **host);
  * of the handle are invalidated. */
 int mfb_xcorr(mfb_ctx *ctx, const float *a, int Na, const float *b, int Nb, float *out_c64);
 
+/* The soft combiner's deterministic core on the device: softCombiner.py:665-798 (correlate), softCombiner.py:570-618 (_doVoteN),
+ * softCombiner.py:623-662 (_doVote2).  The master's new bits bM[Lm] (uint8 0/1) and trust tM[Lm] (int8) are aligned against every
+ * slave's whole buffer bT_i[n_i], tT_i[n_i], in the caller's order.  The current master length Lc starts at Lm; per slave, with
+ * N = 2^ceil(log2 n):
+ *   x[k] = sum_{j < min(Lc, n)} bT[(j + k) mod N] * bM[j],  k in [0, N), bT zero beyond n
+ *          -- abs(customXCorr(bitsX, bitsM[:n])) of softCombiner.py:706 as exact integers (popcounts of packed words);
+ *   val[0..14], idx0: the fifteen largest x by repeated arg-max with zeroing, ties to the lowest index (softCombiner.py:713-716);
+ *   cond = mean(val[2:]) + variance_multiplier * std(val[2:]) in float64; the slave is matched when val[0] > cond;
+ *   a matched slave contributes bT[idx0 : idx0 + Lc]; avail = max(0, min(Lc, n - idx0)) is what that slice holds.  avail <
+ *   min_length: the whole call yields nothing (the reference's `return None`, softCombiner.py:733-737); avail < Lc: Lc = avail for
+ *   the master and every slave accepted before (softCombiner.py:738-747), and the next slave is correlated with the shortened master.
+ * K matched slaves: K >= 2 vote with _doVoteN, K = 1 with _doVote2 -- both through the tables of mfb_combiner_set_vote --, K = 0
+ * passes the master's bits and trust through.  Deviation: a slave of n < 16 bits is not evaluated and not matched (the reference
+ * would raise or match noise on such a buffer).  The counter / length rule by which the reference holds back an unmatched master
+ * (softCombiner.py:779-786) is bookkeeping of the caller, not part of this core.
+ * Limits: at most MFB_COMBINE_MAX_SLAVES slaves (four voters) and streams of at most 2^20 bits; MFB_ERR_UNSUPPORTED beyond, and the
+ * caller takes its host path. */
+#define MFB_COMBINE_MAX_SLAVES 3
+#define MFB_COMBINE_NOTHING     0   /* a matched slave overlaps by less than min_length: no output */
+#define MFB_COMBINE_COMBINED    1   /* voted with matched_count >= 1 slaves */
+#define MFB_COMBINE_MASTER_ONLY 2   /* no slave matched: the master's bits and trust, unchanged */
+typedef struct mfb_combine_params {
+    double variance_multiplier;                 /* conf['SoftCombiner']['varianceMultiplier'] */
+    int32_t min_length;                         /* conf['SoftCombiner']['minProcessingLength'] */
+    int32_t master_len;                         /* Lm */
+    int32_t num_slaves;
+    int32_t slave_len[MFB_COMBINE_MAX_SLAVES];  /* n_i */
+} mfb_combine_params;
+typedef struct mfb_combine_slave {
+    int32_t evaluated;      /* 0: n < 16, or the call had already ended in MFB_COMBINE_NOTHING; everything else is 0 then */
+    int32_t matched;
+    int32_t idx0;           /* lag of val[0] */
+    int32_t avail;          /* matched slaves only */
+    int32_t lc_after;       /* Lc after this slave */
+    int32_t reserved;
+    int32_t val[15];
+    int32_t reserved2;
+    double cond;
+} mfb_combine_slave;
+typedef struct mfb_combine_result {
+    int32_t status;         /* MFB_COMBINE_* */
+    int32_t out_len;        /* bits and trust bytes handed out; 0 for MFB_COMBINE_NOTHING */
+    int32_t matched_count;
+    int32_t num_slaves;
+    int32_t matched_slaves[MFB_COMBINE_MAX_SLAVES];   /* indices into the call's slave list, in the caller's order */
+    int32_t reserved;
+    mfb_combine_slave slave[MFB_COMBINE_MAX_SLAVES];
+} mfb_combine_result;
+/* A combiner owns a stream, page-locked staging and device buffers for streams of up to max_bits bits and max_slaves slaves
+ * (shaped like mfb_syncfinder_*).  The reference keeps these arrays in numpy (Worker.data, softCombiner.py:137-147). */
+typedef struct mfb_combiner mfb_combiner;
+int mfb_combiner_create(mfb_combiner **out, int device, int max_bits, int max_slaves);
+int mfb_combiner_destroy(mfb_combiner *c);
+/* The vote tables for `voters` = 2, 3 or 4 (master + matched slaves): entries = 8^voters; entry sum_v code_v * 8^v with
+ * code_v = 4 * bit_v + trust class {< -1: 0, -1: 1, 0: 2, > 0: 3}, v = 0 the master, holds the output bit and trust byte of
+ * _doVote2 (voters = 2, softCombiner.py:623-662) resp. _doVoteN (softCombiner.py:570-618) for that column.  Both are functions of
+ * the column alone and look at trust only through these classes; the host evaluates them once per masterVoteWeight. */
+int mfb_combiner_set_vote(mfb_combiner *c, int voters, const uint8_t *lut_bits, const int8_t *lut_trust, int entries);
+/* _begin copies the streams in, enqueues everything -- pack, per slave correlation / top-15 / decision, vote -- and returns; no
+ * host synchronisation between slaves.  _end waits and hands out the record and out_len bits / trust bytes (room for master_len
+ * each).  One call in flight per combiner.  MFB_ERR_ARG: lengths <= 0 or beyond max_bits, more slaves than max_slaves;
+ * MFB_ERR_UNSUPPORTED: more than MFB_COMBINE_MAX_SLAVES slaves; MFB_ERR_STATE: a call in flight, _end without _begin, or a vote
+ * table that the call may need is not set.  Replaces SoftCombiner.correlate's numpy loop, softCombiner.py:697-774. */
+int mfb_combiner_begin(mfb_combiner *c, const mfb_combine_params *p, const uint8_t *master_bits, const int8_t *master_trust,
+                       const uint8_t *const *slave_bits, const int8_t *const *slave_trust);
+int mfb_combiner_end(mfb_combiner *c, mfb_combine_result *result, uint8_t *bits, int8_t *trust);
+/* Test seam of the correlation: all N = 2^ceil(log2 n) lags of slave a_bits[n] against master b_bits[m] (the first min(m, n) bits
+ * of it), int32 out[N]: abs(customXCorr(bitsX, bitsM[:n])), softCombiner.py:703-706.  1 <= n, m <= 2^20. */
+int mfb_debug_bit_xcorr(int device, const uint8_t *a_bits, int n, const uint8_t *b_bits, int m, int32_t *out);
+
 /* HIP-event stopwatch on the handle's stream (bench.py's live kernel timing).  The reference times blocks with time.time()
  * around the whole call (DP:324-333). */
 int mfb_timer_start(mfb_ctx *ctx);

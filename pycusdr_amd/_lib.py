@@ -65,6 +65,24 @@ class RecordLayout(C.Structure):
                                          'off_trust', 'off_post', 'off_end', 'off_hits', 'off_edges')]
 
 
+class CombineParams(C.Structure):
+    """mfb_combine_params of include/mfbank.h."""
+    _fields_ = [('variance_multiplier', C.c_double), ('min_length', C.c_int32), ('master_len', C.c_int32), ('num_slaves', C.c_int32),
+                ('slave_len', C.c_int32 * 3)]
+
+
+class CombineSlave(C.Structure):
+    """mfb_combine_slave of include/mfbank.h."""
+    _fields_ = [('evaluated', C.c_int32), ('matched', C.c_int32), ('idx0', C.c_int32), ('avail', C.c_int32), ('lc_after', C.c_int32),
+                ('reserved', C.c_int32), ('val', C.c_int32 * 15), ('reserved2', C.c_int32), ('cond', C.c_double)]
+
+
+class CombineResult(C.Structure):
+    """mfb_combine_result of include/mfbank.h."""
+    _fields_ = [('status', C.c_int32), ('out_len', C.c_int32), ('matched_count', C.c_int32), ('num_slaves', C.c_int32),
+                ('matched_slaves', C.c_int32 * 3), ('reserved', C.c_int32), ('slave', CombineSlave * 3)]
+
+
 # name -> (restype, argtypes); exactly the prototypes of include/mfbank.h
 PROTOTYPES = {
     'mfb_strerror': (C.c_char_p, [_i]),
@@ -133,6 +151,12 @@ PROTOTYPES = {
     'mfb_sync_find_packed': (_i, [_i, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     'mfb_sync_pinned_buffer': (_i, [_i, C.c_size_t, C.POINTER(_vp)]),
     'mfb_xcorr': (_i, [_vp, _vp, _i, _vp, _i, _vp]),
+    'mfb_combiner_create': (_i, [C.POINTER(_vp), _i, _i, _i]),
+    'mfb_combiner_destroy': (_i, [_vp]),
+    'mfb_combiner_set_vote': (_i, [_vp, _i, _vp, _vp, _i]),
+    'mfb_combiner_begin': (_i, [_vp, C.POINTER(CombineParams), _vp, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    'mfb_combiner_end': (_i, [_vp, C.POINTER(CombineResult), _vp, _vp]),
+    'mfb_debug_bit_xcorr': (_i, [_i, _vp, _i, _vp, _i, _vp]),
     'mfb_timer_start': (_i, [_vp]),
     'mfb_timer_stop': (_i, [_vp, _fp]),
     'mfb_profile_enable': (_i, [_vp, _i]),

@@ -981,3 +981,108 @@ def sync_correlate(bits, template, device=0):
     out = np.empty((B, L + ti.size - 1), dtype=np.int32)
     _lib.check(lib.mfb_sync_correlate(int(device), _ptr(b2), B, L, _ptr(ti), ti.size, _ptr(out)), 'mfb_sync_correlate')
     return out[0] if single else out
+
+
+def bit_xcorr(slave_bits, master_bits, device=0):
+    """Test seam (mfb_debug_bit_xcorr): every lag of the soft combiner's alignment correlation as exact integers,
+    ``abs(customXCorr(bitsX, bitsM[:n]))`` of softCombiner.py:703-706: int32 [2^ceil(log2 n)]."""
+    lib = _lib.load()
+    a = np.ascontiguousarray(slave_bits).astype(np.uint8, copy=False)
+    b = np.ascontiguousarray(master_bits).astype(np.uint8, copy=False)
+    N = 1
+    while N < a.size:
+        N *= 2
+    out = np.empty(N, np.int32)
+    _lib.check(lib.mfb_debug_bit_xcorr(int(device), _ptr(a), a.size, _ptr(b), b.size, _ptr(out)), 'mfb_debug_bit_xcorr')
+    return out
+
+
+COMBINE_NOTHING, COMBINE_COMBINED, COMBINE_MASTER_ONLY = 0, 1, 2
+COMBINE_MAX_SLAVES = 3
+COMBINE_MAX_BITS = 1 << 20
+
+
+class Combiner:
+    """The soft combiner's core as an object (mfb_combiner_*): ``begin`` copies the master's new bits / trust and every
+    slave's buffer in, enqueues alignment, decisions and the vote and returns at once; ``end`` waits and returns the
+    result; ``combine`` does both.  ``set_vote(voters, bits, trust)`` hands over the vote table for 2, 3 or 4 voters
+    (softCombiner.vote_table builds them).  Buffers grow on demand."""
+
+    def __init__(self, max_bits=1 << 16, max_slaves=COMBINE_MAX_SLAVES, device=0):
+        self._lib = _lib.load()
+        self.device, self.max_slaves = int(device), int(max_slaves)
+        self._h = C.c_void_p()
+        self._tables = {}
+        self._pending = None
+        self._create(int(max_bits))
+
+    def _create(self, max_bits):
+        self.close()
+        self.max_bits = max_bits
+        _lib.check(self._lib.mfb_combiner_create(C.byref(self._h), self.device, max_bits, self.max_slaves), 'mfb_combiner_create')
+        for v, (b, t) in self._tables.items():
+            _lib.check(self._lib.mfb_combiner_set_vote(self._h, v, _ptr(b), _ptr(t), b.size), 'mfb_combiner_set_vote')
+
+    def close(self):
+        if getattr(self, '_h', None) is not None and self._h:
+            self._lib.mfb_combiner_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_vote(self, voters, lut_bits, lut_trust):
+        b = np.ascontiguousarray(lut_bits, dtype=np.uint8)
+        t = np.ascontiguousarray(lut_trust, dtype=np.int8)
+        _lib.check(self._lib.mfb_combiner_set_vote(self._h, int(voters), _ptr(b), _ptr(t), b.size), 'mfb_combiner_set_vote')
+        self._tables[int(voters)] = (b, t)
+
+    @staticmethod
+    def _u8(a):
+        a = np.ascontiguousarray(a)
+        return a.view(np.uint8) if a.dtype == np.int8 else a.astype(np.uint8, copy=False)
+
+    @staticmethod
+    def _i8(a):
+        return np.ascontiguousarray(a, dtype=np.int8)
+
+    def begin(self, master_bits, master_trust, slaves, variance_multiplier, min_length):
+        """``slaves``: a list of (bits, trust) pairs, the whole buffer of each, in voting order."""
+        mb, mt = self._u8(master_bits), self._i8(master_trust)
+        sl = [(self._u8(b), self._i8(t)) for b, t in slaves]
+        if mb.size != mt.size or any(b.size != t.size for b, t in sl):
+            raise ValueError('bits and trust of a stream have the same length')
+        need = max([mb.size] + [b.size for b, _ in sl])
+        if need > self.max_bits and need <= COMBINE_MAX_BITS and len(sl) <= self.max_slaves:
+            self._create(min(COMBINE_MAX_BITS, need + need // 2))
+        p = _lib.CombineParams(float(variance_multiplier), int(min_length), mb.size, len(sl))
+        for i, (b, _) in enumerate(sl[:COMBINE_MAX_SLAVES]):
+            p.slave_len[i] = b.size
+        n = max(len(sl), 1)
+        pb = (C.c_void_p * n)(*[b.ctypes.data for b, _ in sl])
+        pt = (C.c_void_p * n)(*[t.ctypes.data for _, t in sl])
+        _lib.check(self._lib.mfb_combiner_begin(self._h, C.byref(p), _ptr(mb), _ptr(mt), pb, pt), 'mfb_combiner_begin')
+        self._pending = (mb.size, len(sl))
+
+    def end(self):
+        """A dict: status (COMBINE_*), bits (uint8) and trust (int8) of out_len elements, matched (slave indices) and one
+        record per slave {evaluated, matched, idx0, avail, lc_after, val (int32 [15]), cond}."""
+        Lm, ns = self._pending if self._pending else (1, 0)
+        R = _lib.CombineResult()
+        bits, trust = np.empty(Lm, np.uint8), np.empty(Lm, np.int8)
+        _lib.check(self._lib.mfb_combiner_end(self._h, C.byref(R), _ptr(bits), _ptr(trust)), 'mfb_combiner_end')
+        self._pending = None
+        recs = []
+        for i in range(ns):
+            s = R.slave[i]
+            recs.append({'evaluated': int(s.evaluated), 'matched': int(s.matched), 'idx0': int(s.idx0), 'avail': int(s.avail),
+                         'lc_after': int(s.lc_after), 'val': np.array(s.val[:], np.int32), 'cond': float(s.cond)})
+        return {'status': int(R.status), 'bits': bits[:R.out_len], 'trust': trust[:R.out_len],
+                'matched': [int(R.matched_slaves[i]) for i in range(R.matched_count)], 'slaves': recs}
+
+    def combine(self, master_bits, master_trust, slaves, variance_multiplier, min_length):
+        self.begin(master_bits, master_trust, slaves, variance_multiplier, min_length)
+        return self.end()
