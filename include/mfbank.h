@@ -567,6 +567,13 @@ int mfb_combiner_end(mfb_combiner *c, mfb_combine_result *result, uint8_t *bits,
 /* Test seam of the correlation: all N = 2^ceil(log2 n) lags of slave a_bits[n] against master b_bits[m] (the first min(m, n) bits
  * of it), int32 out[N]: abs(customXCorr(bitsX, bitsM[:n])), softCombiner.py:703-706.  1 <= n, m <= 2^20. */
 int mfb_debug_bit_xcorr(int device, const uint8_t *a_bits, int n, const uint8_t *b_bits, int m, int32_t *out);
+/* Test seam of the peak stages (softCombiner.py:709-747): what a call runs for slave 0 after its correlation -- the record's
+ * initialisation with Lc = master_len, the fifteen peaks of every 4096 lags, their merge and the decision, the final status: the
+ * production kernels on the production grids -- on a correlation x[nlags] of the caller's choice instead of one of bit streams; n is
+ * the slave's length (avail = max(0, min(Lc, n - idx0))).  No vote: *out is the record alone.  1 <= nlags, n, master_len <= 2^20
+ * (MFB_ERR_UNSUPPORTED beyond), every x[k] >= 0 (MFB_ERR_ARG). */
+int mfb_debug_combine_peaks(int device, const int32_t *x, int nlags, int n, int master_len, double variance_multiplier,
+                            int min_length, mfb_combine_result *out);
 
 /* HIP-event stopwatch on the handle's stream (bench.py's live kernel timing).  The reference times blocks with time.time()
  * around the whole call (DP:324-333). */

@@ -157,6 +157,7 @@ PROTOTYPES = {
     'mfb_combiner_begin': (_i, [_vp, C.POINTER(CombineParams), _vp, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
     'mfb_combiner_end': (_i, [_vp, C.POINTER(CombineResult), _vp, _vp]),
     'mfb_debug_bit_xcorr': (_i, [_i, _vp, _i, _vp, _i, _vp]),
+    'mfb_debug_combine_peaks': (_i, [_i, _vp, _i, _i, _i, C.c_double, _i, C.POINTER(CombineResult)]),
     'mfb_timer_start': (_i, [_vp]),
     'mfb_timer_stop': (_i, [_vp, _fp]),
     'mfb_profile_enable': (_i, [_vp, _i]),

@@ -164,11 +164,31 @@ __global__ __launch_bounds__(256) void k_cmb_top_seg(const int32_t *__restrict__
     if (threadIdx.x < CMB_TOPK) cand[blockIdx.x * CMB_TOPK + threadIdx.x] = top[threadIdx.x];
 }
 
-// numpy's float64 sum of 13 values (pairwise routine, n < 128: eight partial sums, then the rest in order) without contraction
+// numpy's float64 sum of 13 values (pairwise routine, n < 128: eight partial sums, then the rest in order).  Contraction is switched
+// off by pragma in the two functions that make cond: HIP's __dadd_rn / __dmul_rn are plain `x + y` / `x * y` in the headers, and
+// under the compiler's default -ffp-contract=fast-honor-pragmas they fuse with their neighbours after inlining (t * t + u * u and
+// mean + vm * sd became v_fma_f64, one rounding fewer than numpy: cond differed in the last bit).  The operators below carry no
+// contract flag, so neither a product made here nor one handed in can be fused into these sums.
 __device__ inline double cmb_sum13(const double *a) {
-    double r = __dadd_rn(__dadd_rn(__dadd_rn(a[0], a[1]), __dadd_rn(a[2], a[3])), __dadd_rn(__dadd_rn(a[4], a[5]), __dadd_rn(a[6], a[7])));
-    for (int i = 8; i < 13; ++i) r = __dadd_rn(r, a[i]);
+#pragma clang fp contract(off)
+    double r = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+    for (int i = 8; i < 13; ++i) r = r + a[i];
     return r;
+}
+
+// cond = mean(val[2:]) + vm * std(val[2:]) as numpy computes it in float64 (softCombiner.py:720): every line one correctly rounded
+// operation (the division and the square root expand to IEEE-exact sequences of their own), none fused with the next
+__device__ inline double cmb_cond(const double *v, double vm) {
+#pragma clang fp contract(off)
+    const double mean = cmb_sum13(v + 2) / 13.0;
+    double d[13];
+    for (int i = 0; i < 13; ++i) {
+        const double t = v[i + 2] - mean;
+        d[i] = t * t;
+    }
+    const double sd = __dsqrt_rn(cmb_sum13(d) / 13.0);
+    const double scaled = vm * sd;
+    return mean + scaled;
 }
 
 // Stage 2 and the decision: one workgroup merges ncand <= 4096 candidates; thread 0 computes
@@ -194,14 +214,7 @@ __global__ __launch_bounds__(256) void k_cmb_decide(const cmb_key *__restrict__ 
         v[i] = (double)r->val[i];
     }
     const int idx0 = (int)(0xFFFFFFFFu - (uint32_t)top[0]);
-    const double mean = __ddiv_rn(cmb_sum13(v + 2), 13.0);
-    double d[13];
-    for (int i = 0; i < 13; ++i) {
-        const double t = __dadd_rn(v[i + 2], -mean);
-        d[i] = __dmul_rn(t, t);
-    }
-    const double sd = __dsqrt_rn(__ddiv_rn(cmb_sum13(d), 13.0));
-    const double cond = __dadd_rn(mean, __dmul_rn(vm, sd));
+    const double cond = cmb_cond(v, vm);
     int Lc = res->out_len;
     r->evaluated = 1;
     r->cond = cond;

@@ -3939,6 +3939,41 @@ extern "C" int mfb_debug_bit_xcorr(int device, const uint8_t *a_bits, int n, con
     return rc;
 }
 
+// Test seam of the peak stages: what a call runs for slave 0 after its correlation -- init, top-15 per segment, merge and decision,
+// finish: the same kernels, the same grids -- on a correlation x[nlags] of the caller's choice.  No streams, so no vote.
+extern "C" int mfb_debug_combine_peaks(int device, const int32_t *x, int nlags, int n, int master_len, double variance_multiplier,
+                                       int min_length, mfb_combine_result *out) {
+    if (!x || !out || nlags < 1 || n < 1 || master_len < 1) return MFB_ERR_ARG;
+    if (nlags > CMB_MAX_BITS || n > CMB_MAX_BITS || master_len > CMB_MAX_BITS) return MFB_ERR_UNSUPPORTED;
+    for (int i = 0; i < nlags; ++i)
+        if (x[i] < 0) return MFB_ERR_ARG;
+    int rc = sync_device_ok(device);
+    if (rc) return rc;
+    const int g = (nlags + CMB_SEG - 1) / CMB_SEG;
+    int32_t *d_x = nullptr;
+    cmb_key *d_cand = nullptr;
+    mfb_combine_result *d_res = nullptr;
+    auto run = [&]() -> int {
+        HIPCHK(hipMalloc((void **)&d_x, (size_t)nlags * sizeof(int32_t)));
+        HIPCHK(hipMalloc((void **)&d_cand, (size_t)g * CMB_TOPK * sizeof(cmb_key)));
+        HIPCHK(hipMalloc((void **)&d_res, sizeof(mfb_combine_result)));
+        HIPCHK(hipMemcpy(d_x, x, (size_t)nlags * sizeof(int32_t), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_cmb_init, dim3(1), dim3(64), 0, nullptr, d_res, master_len, 1);
+        hipLaunchKernelGGL(k_cmb_top_seg, dim3(g), dim3(256), 0, nullptr, (const int32_t *)d_x, nlags, (const mfb_combine_result *)d_res, d_cand);
+        hipLaunchKernelGGL(k_cmb_decide, dim3(1), dim3(256), 0, nullptr, (const cmb_key *)d_cand, g * CMB_TOPK, d_res, 0, n, variance_multiplier,
+                           min_length);
+        hipLaunchKernelGGL(k_cmb_finish, dim3(1), dim3(1), 0, nullptr, d_res);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpy(out, d_res, sizeof(mfb_combine_result), hipMemcpyDeviceToHost));
+        return MFB_OK;
+    };
+    rc = run();
+    if (d_x) (void)hipFree(d_x);
+    if (d_cand) (void)hipFree(d_cand);
+    if (d_res) (void)hipFree(d_res);
+    return rc;
+}
+
 // ---- packed sync correlation (sync_kernels.hpp, second half) -------------------------------------------------------------
 // One page-locked buffer per device, grown on demand: callers that produce their packed bit streams straight into it
 // (mfb_sync_pinned_buffer) get a true asynchronous host-to-device copy; any other host pointer works too (the runtime stages it).

@@ -1002,6 +1002,31 @@ COMBINE_MAX_SLAVES = 3
 COMBINE_MAX_BITS = 1 << 20
 
 
+def _combine_dict(R, ns, bits, trust):
+    """A CombineResult as the dict of ``Combiner.end``."""
+    recs = []
+    for i in range(ns):
+        s = R.slave[i]
+        recs.append({'evaluated': int(s.evaluated), 'matched': int(s.matched), 'idx0': int(s.idx0), 'avail': int(s.avail),
+                     'lc_after': int(s.lc_after), 'val': np.array(s.val[:], np.int32), 'cond': float(s.cond)})
+    return {'status': int(R.status), 'bits': bits, 'trust': trust,
+            'matched': [int(R.matched_slaves[i]) for i in range(R.matched_count)], 'slaves': recs}
+
+
+def combine_peaks(x, n, master_len, variance_multiplier, min_length, device=0):
+    """Test seam (mfb_debug_combine_peaks): the soft combiner's peak stages and decision for one slave of ``n`` bits on a
+    correlation ``x`` (non-negative integers, at most 2^20 lags) of the caller's choice, the master ``master_len`` bits long.
+    The dict of ``Combiner.end`` -- no streams go in, so ``bits`` and ``trust`` are empty -- and ``out_len``, the record's."""
+    lib = _lib.load()
+    xi = np.ascontiguousarray(x, dtype=np.int32)
+    if xi.ndim != 1 or not np.array_equal(xi, x):
+        raise ValueError('x is one row of int32 values')
+    R = _lib.CombineResult()
+    _lib.check(lib.mfb_debug_combine_peaks(int(device), _ptr(xi), xi.size, int(n), int(master_len), float(variance_multiplier),
+                                           int(min_length), C.byref(R)), 'mfb_debug_combine_peaks')
+    return {**_combine_dict(R, 1, np.empty(0, np.uint8), np.empty(0, np.int8)), 'out_len': int(R.out_len)}
+
+
 class Combiner:
     """The soft combiner's core as an object (mfb_combiner_*): ``begin`` copies the master's new bits / trust and every
     slave's buffer in, enqueues alignment, decisions and the vote and returns at once; ``end`` waits and returns the
@@ -1075,13 +1100,7 @@ class Combiner:
         bits, trust = np.empty(Lm, np.uint8), np.empty(Lm, np.int8)
         _lib.check(self._lib.mfb_combiner_end(self._h, C.byref(R), _ptr(bits), _ptr(trust)), 'mfb_combiner_end')
         self._pending = None
-        recs = []
-        for i in range(ns):
-            s = R.slave[i]
-            recs.append({'evaluated': int(s.evaluated), 'matched': int(s.matched), 'idx0': int(s.idx0), 'avail': int(s.avail),
-                         'lc_after': int(s.lc_after), 'val': np.array(s.val[:], np.int32), 'cond': float(s.cond)})
-        return {'status': int(R.status), 'bits': bits[:R.out_len], 'trust': trust[:R.out_len],
-                'matched': [int(R.matched_slaves[i]) for i in range(R.matched_count)], 'slaves': recs}
+        return _combine_dict(R, ns, bits[:R.out_len], trust[:R.out_len])
 
     def combine(self, master_bits, master_trust, slaves, variance_multiplier, min_length):
         self.begin(master_bits, master_trust, slaves, variance_multiplier, min_length)

@@ -140,7 +140,7 @@ def test_compare_workers_takes_every_worker_as_master():
 def test_binding_carries_the_new_symbols():
     from pycusdr_amd import _lib
     for name in ('mfb_combiner_create', 'mfb_combiner_destroy', 'mfb_combiner_set_vote', 'mfb_combiner_begin', 'mfb_combiner_end',
-                 'mfb_debug_bit_xcorr'):
+                 'mfb_debug_bit_xcorr', 'mfb_debug_combine_peaks'):
         assert name in _lib.PROTOTYPES
     import ctypes
     assert ctypes.sizeof(_lib.CombineSlave) == 96 and ctypes.sizeof(_lib.CombineResult) == 320 and ctypes.sizeof(_lib.CombineParams) == 32

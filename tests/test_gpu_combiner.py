@@ -55,12 +55,12 @@ def test_bit_xcorr_equals_the_exact_integer_correlation():
 @pytest.mark.parametrize('name', cc.SCENARIOS)
 def test_scenario_hip_equals_host_and_the_reference(name):
     """Every recorded scenario on the hip back end: the reference's result and indices byte for byte, and the core's record
-    equal to the host's -- val[15], idx0, avail exactly, cond within 1e-9 relative -- without the host path being taken."""
+    equal to the host's -- val[15], idx0, avail and cond, the float64 bit for bit -- without the host path being taken."""
     from pycusdr_amd import softCombiner as sc
     res, ws, comb = cc.run_scenario(name, 'hip')
     cc.check_against_reference(name, res, ws)
     args = cc.core_inputs(name)
-    cc.same_core(comb.combine(*args), sc.combine_host(*args, VM, WEIGHT, MINLEN), cond_rel=1e-9)
+    cc.same_core(comb.combine(*args), sc.combine_host(*args, VM, WEIGHT, MINLEN), cond_rel=0.0)
     assert comb.host_fallbacks == 0
     comb.close()
 
@@ -92,8 +92,8 @@ def test_begin_end_overlap_with_a_second_handle():
     b.begin(*ib, VM, MINLEN)
     rb = b.end()
     ra = a.end()
-    cc.same_core(ra, sc.combine_host(*ia, VM, WEIGHT, MINLEN), cond_rel=1e-9)
-    cc.same_core(rb, sc.combine_host(*ib, VM, WEIGHT, MINLEN), cond_rel=1e-9)
+    cc.same_core(ra, sc.combine_host(*ia, VM, WEIGHT, MINLEN), cond_rel=0.0)
+    cc.same_core(rb, sc.combine_host(*ib, VM, WEIGHT, MINLEN), cond_rel=0.0)
     a.close()
     b.close()
 
@@ -167,7 +167,7 @@ def test_four_slaves_take_the_host_path():
     cc.same_core(got, sc.combine_host(m, t, slaves, VM, WEIGHT, MINLEN))
     got3 = hip.combine(m, t, slaves[:3])                    # three slaves: the device again
     assert hip.host_fallbacks == 1 and hip._combiner is not None
-    cc.same_core(got3, sc.combine_host(m, t, slaves[:3], VM, WEIGHT, MINLEN), cond_rel=1e-9)
+    cc.same_core(got3, sc.combine_host(m, t, slaves[:3], VM, WEIGHT, MINLEN), cond_rel=0.0)
     hip.close()
 
 
@@ -195,7 +195,7 @@ def test_handle_reuse_equals_fresh_handles():
         fresh.close()
         cc.same_core(got, want)
         if call % 10 == 0:
-            cc.same_core(got, sc.combine_host(m, t, slaves, VM, WEIGHT, MINLEN), cond_rel=1e-9)
+            cc.same_core(got, sc.combine_host(m, t, slaves, VM, WEIGHT, MINLEN), cond_rel=0.0)
         statuses.add(got['status'])
     assert statuses == {sc.NOTHING, sc.COMBINED, sc.MASTER_ONLY}
     one.close()
