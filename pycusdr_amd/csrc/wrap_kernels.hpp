@@ -51,6 +51,13 @@ struct SegWCfg {
     }
 };
 
+// a bin's tables in registers: the B fragments (hi, lo) and its Parseval weights
+template <int KT>
+struct SegWBin {
+    seg_h8 hi[KT], lo[KT];
+    cf q[8];
+};
+
 template <int PV, int KT>
 DEVI void segw_body(const SegWArgs &w, const int blk) {
     static_assert(MFB_FFT_FUSED, "the fused 256-point transform");
@@ -109,6 +116,11 @@ DEVI void segw_body(const SegWArgs &w, const int blk) {
     const bool im_half = q >= 2;
     const int qo = 8 * (q & 1);
 
+    // the bins' powers of two of the wrap energy, lane j holding bin jb0 + j's: fetched once (the samples' loads wait for it), so that
+    // no bin waits for a load at the head of its products
+    const bool one_chunk = jb1 - jb0 <= 64;
+    int wexl = jb0 + lane < jb1 ? w.Wexp[jb0 + lane] : 0;
+
     for (int slot = s0; slot < s1; ++slot) {
         cf v[PPL];
         {
@@ -160,15 +172,12 @@ DEVI void segw_body(const SegWArgs &w, const int blk) {
             auto keep = [&](int, cf val, auto, auto nu) { A[decltype(nu)::value / NT] = val; };
             fft256_fused<0, PPL>(v, mylds, g, f256, keep);
         }
-        cf pp[PPL / 2], qq[PPL / 2];
+        cf pp[PPL / 2];
 #pragma unroll
         for (int j = 0; j < PPL / 2; ++j) {
             const cf p0 = A[2 * j] * A[2 * j], p1 = A[2 * j + 1] * A[2 * j + 1];
             pp[j] = mkc(p0.x + p0.y, p1.x + p1.y);
         }
-        load_q(qq, jb0);
-        seg_h8 bhi[KT], blo[KT];
-        load_b(bhi, blo, jb0);
         // ---- the A fragments of the CT segments: ND Toeplitz blocks each, scaled by 2^ea of the segment and split into hi / lo ----
         seg_h8 ahi[CT][ND], alo[CT][ND];
         int eseg[CT];
@@ -191,58 +200,114 @@ DEVI void segw_body(const SegWArgs &w, const int blk) {
         }
         xsync<1>();       // the windows are rewritten by the next slot
 
-        for (int jb = jb0; jb < jb1; ++jb) {
+        // ---- the bins: bin jb + 1's products issue with bin jb's squares, reduction and store between them (two sets of accumulators
+        // and of bin tables, taking turns), so that the matrix pipe does not idle while the vector ALUs finish a bin.  A bin's arithmetic
+        // is what it was: the same operations on the same operands in the same order.
+        for (int jc = jb0; jc < jb1; jc += 64) {
+            if (!one_chunk) {       // a rectangle of more than 64 bins: fetched per chunk, and waited for here, not at the head of a bin
+                wexl = jc + lane < jb1 ? w.Wexp[jc + lane] : 0;
+                __builtin_amdgcn_s_waitcnt(0x0F70);         // vmcnt(0)
+            }
+            const int jc1 = min(jb1, jc + 64);
+            SegWBin<KT> b0, b1;
+            seg_f4 acc0[CT][RT], acc1[CT][RT];
             // the Parseval total of the bin's filters (segf_body)
-            cf t2[2] = {mkc(0.f, 0.f), mkc(0.f, 0.f)};
+            auto parseval = [&](const SegWBin<KT> &b) {
+                cf t2[2] = {mkc(0.f, 0.f), mkc(0.f, 0.f)};
 #pragma unroll
-            for (int j = 0; j < PPL / 2; ++j) t2[j & 1] = __builtin_elementwise_fma(pp[j], qq[j], t2[j & 1]);
-            const float tot = (t2[0].x + t2[0].y) + (t2[1].x + t2[1].y);
-            if (jb + 1 < jb1) load_q(qq, jb + 1);
-            const int wexp = w.Wexp[jb];
-            seg_h8 nhi[KT], nlo[KT];            // the next bin's B fragments land while this bin's products run
-            if (jb + 1 < jb1) load_b(nhi, nlo, jb + 1);
-            // the wrap energy: per segment, RT row tiles x KT K-steps x (lo.hi, hi.lo, hi.hi), squared and summed in a fixed order
-            float wacc = 0.f;
+                for (int j = 0; j < PPL / 2; ++j) t2[j & 1] = __builtin_elementwise_fma(pp[j], b.q[j], t2[j & 1]);
+                return (t2[0].x + t2[0].y) + (t2[1].x + t2[1].y);
+            };
+            auto fetch = [&](SegWBin<KT> &b, int bin) {
+                load_q(b.q, bin);
+                load_b(b.hi, b.lo, bin);
+            };
+            // the wrap products: per segment, RT row tiles x KT K-steps x (lo.hi, hi.lo, hi.hi)
+            auto products = [&](seg_f4 (&acc)[CT][RT], const SegWBin<KT> &b) {
 #pragma unroll
-            for (int c = 0; c < CT; ++c) {
-                float sq[RT];
+                for (int c = 0; c < CT; ++c) {
 #pragma unroll
-                for (int rt = 0; rt < RT; ++rt) {
-                    seg_f4 acc = {0.f, 0.f, 0.f, 0.f};
+                    for (int rt = 0; rt < RT; ++rt) {
+                        seg_f4 t = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                    for (int kk = 0; kk < KT; ++kk) {
-                        const int di = rt - kk + KT - 1;
-                        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo[c][di], bhi[kk], acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi[c][di], blo[kk], acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi[c][di], bhi[kk], acc, 0, 0, 0);
+                        for (int kk = 0; kk < KT; ++kk) {
+                            const int di = rt - kk + KT - 1;
+                            t = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo[c][di], b.hi[kk], t, 0, 0, 0);
+                            t = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi[c][di], b.lo[kk], t, 0, 0, 0);
+                            t = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi[c][di], b.hi[kk], t, 0, 0, 0);
+                        }
+                        acc[c][rt] = t;
                     }
-                    sq[rt] = __builtin_fmaf(acc.x, acc.x, acc.y * acc.y) + __builtin_fmaf(acc.z, acc.z, acc.w * acc.w);
                 }
-                float s = sq[0];
+            };
+            // the wrap energy, squared and summed in a fixed order, off the Parseval total; then the wave's 64 values in segf_body's
+            // fixed order: quads, the four quads of a row, the four rows
+            auto finish = [&](const seg_f4 (&acc)[CT][RT], float tot, int jb) {
+                const int wexp = __builtin_amdgcn_readlane(wexl, jb - jc);
+                float wacc = 0.f;
 #pragma unroll
-                for (int rt = 1; rt < RT; ++rt) s += sq[rt];
-                wacc += __builtin_ldexpf(s, wexp - 2 * eseg[c]);
-            }
-            if (jb + 1 < jb1) {
+                for (int c = 0; c < CT; ++c) {
+                    float sq[RT];
 #pragma unroll
-                for (int kk = 0; kk < KT; ++kk) {
-                    bhi[kk] = nhi[kk];
-                    blo[kk] = nlo[kk];
+                    for (int rt = 0; rt < RT; ++rt) {
+                        const seg_f4 t = acc[c][rt];
+                        sq[rt] = __builtin_fmaf(t.x, t.x, t.y * t.y) + __builtin_fmaf(t.z, t.z, t.w * t.w);
+                    }
+                    float s = sq[0];
+#pragma unroll
+                    for (int rt = 1; rt < RT; ++rt) s += sq[rt];
+                    wacc += __builtin_ldexpf(s, wexp - 2 * eseg[c]);
                 }
+                float sv = __builtin_fmaf((float)L, tot, -wacc);
+                sv += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(sv), 0xB1, 0xF, 0xF, true));       // quad_perm [1,0,3,2]
+                sv += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(sv), 0x4E, 0xF, 0xF, true));       // quad_perm [2,3,0,1]
+                sv += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(sv), 0x124, 0xF, 0xF, true));      // row_ror:4
+                sv += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(sv), 0x128, 0xF, 0xF, true));      // row_ror:8
+                const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sv), 0));
+                const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sv), 16));
+                const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sv), 32));
+                const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sv), 48));
+                return (r0 + r1) + (r2 + r3);
+            };
+            auto store = [&](float total, int jb) {
+                if (lane < a.MU)
+                    a.partials[((size_t)(a.part_row0 + bk * a.dper + jb) * a.MU + lane) * a.parts + slot] = lane == 0 ? total * a.scale : 0.f;
+            };
+            // one bin's products with the bin before's finish between them, two vector instructions to a product (16 cycles of the
+            // matrix pipe, four issue slots); the tables of the bin after (clamped to the chunk: the last one is fetched twice, into
+            // the set nobody reads) are requested first
+            auto step = [&](seg_f4 (&accn)[CT][RT], SegWBin<KT> &bn, const seg_f4 (&accp)[CT][RT], SegWBin<KT> &bp, float totp, int jb) {
+                const float totn = parseval(bn);
+                fetch(bp, min(jb + 2, jc1 - 1));
+                products(accn, bn);
+                const float total = finish(accp, totp, jb);
+#pragma unroll
+                for (int i = 0; i < CT * RT * KT * 3; ++i) {
+                    __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);        // one MFMA
+                    __builtin_amdgcn_sched_group_barrier(0x2, 2, 0);        // two VALU
+                }
+                store(total, jb);
+                return totn;
+            };
+            fetch(b0, jc);
+            fetch(b1, min(jc + 1, jc1 - 1));
+            float tot0 = parseval(b0), tot1 = 0.f;
+            products(acc0, b0);
+            int jb = jc;
+            while (true) {
+                if (jb + 1 >= jc1) {
+                    store(finish(acc0, tot0, jb), jb);
+                    break;
+                }
+                tot1 = step(acc1, b1, acc0, b0, tot0, jb);
+                ++jb;
+                if (jb + 1 >= jc1) {
+                    store(finish(acc1, tot1, jb), jb);
+                    break;
+                }
+                tot0 = step(acc0, b0, acc1, b1, tot1, jb);
+                ++jb;
             }
-            // the wave's 64 values in segf_body's fixed order: quads, the four quads of a row, the four rows
-            float sv = __builtin_fmaf((float)L, tot, -wacc);
-            sv += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(sv), 0xB1, 0xF, 0xF, true));       // quad_perm [1,0,3,2]
-            sv += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(sv), 0x4E, 0xF, 0xF, true));       // quad_perm [2,3,0,1]
-            sv += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(sv), 0x124, 0xF, 0xF, true));      // row_ror:4
-            sv += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(sv), 0x128, 0xF, 0xF, true));      // row_ror:8
-            const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sv), 0));
-            const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sv), 16));
-            const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sv), 32));
-            const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sv), 48));
-            const float total = (r0 + r1) + (r2 + r3);
-            if (lane < a.MU)
-                a.partials[((size_t)(a.part_row0 + bk * a.dper + jb) * a.MU + lane) * a.parts + slot] = lane == 0 ? total * a.scale : 0.f;
         }
     }
 }
