@@ -1616,10 +1616,23 @@ static int fsm_prepare(mfb_ctx *c, bool span, int rows) {
 // of the 8-filter banks, 8 of the BPSK bank's 16 --, 64 of 2048 points.  Groups (blockIdx % 8 = XCD): an eighth of the BINS when
 // there are enough of them -- every XCD then keeps its share of the per-bin spectra in its L2 (C3: +4.5 %; the 2048-point kernel,
 // 32 MiB of spectra at 256 bins: 2.09 against 2.49 ms) and the samples stream through all of them --, else an eighth of the slots.
+//
+// The matrix-core form (k_segw) plans for itself.  A wave of it pays a slot's prologue -- samples, window, forward transform and the
+// 160 fragment registers, the matrix pipe idle and nothing else on the SIMD -- once per rectangle, so its rectangle is the group's
+// whole share of bins, in equal chunks of at most SEGW_FB (C2: 32 bins, one chunk; C3: four chunks of 32), and SEGW_FS slots
+// (measured, profiles/r12_wrap_slots.md: C2 2055 Msamples/s at 16 x 1, 2295 at 32 x 1, 2316 at 32 x 2, 2310 ... 2323 at 32 x 5, 2273
+// at 32 x 10, one launch round with nothing to even out).  It holds one wave per SIMD, not three: its small-launch bound is a wave for
+// every SIMD, reached by giving up slots per wave first, which cost nothing, and bins only then.  What a group is does not depend on
+// the form, and which form runs does not depend on the rectangle (wrap_kt).
 struct FsmPlan {
-    bool ok;
+    bool ok, segw;
     int nsg, gbins, fb, fs, nbc, nsc;
 };
+constexpr int SEGW_FB = 32, SEGW_FS = 5;
+// whether launch_fsm takes k_segw<13, 3>: the bank, the basis and the block length decide (wrap_kt), nothing else
+static bool fsm_segw(const mfb_ctx *c, int MU) {
+    return wrap_kt(c, c->basis == MFB_BASIS_SPAN, MU) == 3;
+}
 static FsmPlan fsm_plan(const mfb_ctx *c, int MU, int nfull, int nb = 1) {
     static int env_fb = 0, env_fs = 0;
     static const bool env_read = [] {
@@ -1632,10 +1645,12 @@ static FsmPlan fsm_plan(const mfb_ctx *c, int MU, int nfull, int nb = 1) {
     FsmPlan p;
     memset(&p, 0, sizeof(p));
     const bool w32 = c->segl == 11;
+    p.segw = fsm_segw(c, MU);
     p.nsg = nfull >= 64 ? 8 : 1;
     const int per_fwd = w32 ? 64 : 128;
+    const bool fb_set = c->fsm_fb > 0 || env_fb > 0, fs_set = c->fsm_fs > 0 || env_fs > 0;
     int fb = c->fsm_fb > 0 ? c->fsm_fb : (env_fb > 0 ? env_fb : (per_fwd / MU > 2 ? per_fwd / MU : 2));
-    int fs = c->fsm_fs > 0 ? c->fsm_fs : (env_fs > 0 ? env_fs : 1);
+    int fs = c->fsm_fs > 0 ? c->fsm_fs : (env_fs > 0 ? env_fs : (p.segw ? SEGW_FS : 1));
     if (fb > c->Dtot) fb = c->Dtot;
     p.gbins = env_gb >= 0 ? (env_gb != 0) : (p.nsg > 1 && c->Dtot >= p.nsg * fb ? 1 : 0);
     if (p.gbins && c->Dtot < p.nsg) p.gbins = 0;
@@ -1647,6 +1662,10 @@ static FsmPlan fsm_plan(const mfb_ctx *c, int MU, int nfull, int nb = 1) {
     }
     const int glen = p.gbins ? nfull : (nfull + p.nsg - 1) / p.nsg;
     const int gblen = p.gbins ? (c->Dtot + p.nsg - 1) / p.nsg : c->Dtot;
+    if (p.segw && !fb_set) {
+        const int chunks = (gblen + SEGW_FB - 1) / SEGW_FB;
+        fb = (gblen + chunks - 1) / chunks;
+    }
     if (fs > glen) fs = glen;
     if (fb > gblen) fb = gblen;
     if (fb < 1 || fs < 1) return p;
@@ -1654,9 +1673,14 @@ static FsmPlan fsm_plan(const mfb_ctx *c, int MU, int nfull, int nb = 1) {
     // rectangle shrinks until the launch has twice the waves the device holds at once -- at one bin per rectangle the forward
     // transform is no longer shared, and what is left of the gain is the mixing multiply (measured: bench.py's one-block loop at
     // 2^15 x 64 fell from 250 to 155 Msamples/s with 16-bin rectangles: 156 waves on 1024 SIMDs)
-    if (c->fsm_fb <= 0 && env_fb <= 0) {
+    auto waves = [&] { return (long long)nb * p.nsg * ((gblen + fb - 1) / fb) * ((glen + fs - 1) / fs); };
+    if (p.segw) {
+        const long long want = 4LL * c->num_cus;
+        while (!fs_set && fs > 1 && waves() < want) fs = (fs + 1) >> 1;
+        while (!fb_set && fb > 1 && waves() < want) fb = (fb + 1) >> 1;
+    } else if (!fb_set) {
         const long long want = 2LL * c->num_cus * 4 * (w32 ? 2 : 3);
-        while (fb > 1 && (long long)nb * p.nsg * ((gblen + fb - 1) / fb) * ((glen + fs - 1) / fs) < want) fb >>= 1;
+        while (fb > 1 && waves() < want) fb >>= 1;
     }
     p.fb = fb;
     p.fs = fs;
@@ -1730,7 +1754,11 @@ static int launch_fsm(mfb_ctx *c, int nb, const cf *x, int xstride, int MU, int 
         return launch_segf_pv<2048, 16, 32>(c, a, grid, lds, pv);
     }
     // the wrap-around energy on the matrix cores (wrap_kernels.hpp)
-    if (a.Qs && a.presum && c->d_Wb && c->wb_kt == 3 && pv == 13 && MU <= 8 && wrap_kt(c, c->gs_span == 1, MU) == 3) {
+    if (fp.segw) {
+        // fsm_prepare built the bin tables from the same answer of wrap_kt; tables that do not match it are an error, not a reason
+        // to run the other form
+        const bool tables = a.Qs && a.presum && c->d_Wb && c->wb_kt == 3 && c->gs_span == (c->basis == MFB_BASIS_SPAN ? 1 : 0);
+        if (!tables || pv != 13) return MFB_ERR_STATE;
         SegWArgs w;
         w.f = a;
         w.Wb = c->d_Wb;

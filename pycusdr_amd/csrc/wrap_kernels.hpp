@@ -18,10 +18,15 @@
 // lo.hi + hi.lo + hi.hi accumulate in fp32 (lo.lo, ~2^-22 relative, is dropped).  Because both scales are powers of two taken from the
 // data, scaling the input by 2^k leaves the fp16 operands and the accumulators bit for bit the same and the score scales exactly.
 //
-// Everything else is segf_body's: the XCD-aware rectangle of bins x slots, the unmixed forward transform (via the inverse one on swapped
+// Everything else is segf_body's: the XCD-aware groups of the grid, the unmixed forward transform (via the inverse one on swapped
 // samples), the Parseval total from pp = |A|^2 and Q, and the PRESUM store (row 0 carries the (bin, slot) sum, the other rows zero).
 // A bin's number depends on its own tables and the slot's samples only, summed in one fixed order: the same bits whichever bins share
 // the rectangle, whatever the grid or the batch.
+//
+// The rectangle of bins x slots is this form's own (mfbank.hip, fsm_plan): a slot's prologue -- samples, window, forward transform and
+// the 160 fragment registers -- runs with the matrix pipe idle and nothing else on the SIMD, so a wave takes its group's whole share
+// of bins, up to 32 a chunk, and pays the prologue once for them (profiles/r12_wrap_slots.md: C2 1.13x over 16 bins).  The loads
+// of a slot are not carried into the next: 32 registers of samples across the bin loop cost more than their latency (same write-up).
 #pragma once
 #include "seg_kernels.hpp"
 
