@@ -27,6 +27,19 @@
 // the 160 fragment registers -- runs with the matrix pipe idle and nothing else on the SIMD, so a wave takes its group's whole share
 // of bins, up to 32 a chunk, and pays the prologue once for them (profiles/r12_wrap_slots.md: C2 1.13x over 16 bins).  The loads
 // of a slot are not carried into the next: 32 registers of samples across the bin loop cost more than their latency (same write-up).
+//
+// Where the values live and how a step of the bin loop issues (profiles/r13_wrap_issue.md).  With one wave on the SIMD a 16x16x32 MFMA
+// holds the vector issue for 8 of its 16 cycles and every other instruction costs about 4, so a gap between two MFMAs hides two
+// instructions and pays for every further one.  The library is compiled with -mllvm -amdgpu-mfma-vgpr-form (k_segw is its only kernel
+// with an MFMA): the products accumulate in arch VGPRs, where the vector ALUs of `finish` read them with no copy, and what only the
+// MFMA reads -- the 160 fragment registers and both sets of B fragments -- is pinned to the accumulation registers by empty asm
+// statements with an "a" constraint (the fragments are written there once, as they are built; the B tables are loaded there).  A
+// step's 108 gaps are then filled by sched_group_barrier: scalar address arithmetic and the row of the bin before (carried as a
+// value and stored ahead of the table fetches, so that no wait at the head of a step covers a store just issued) in the first four,
+// the ten table fetches of the bin after next one to a gap, and the squares, the reduction, the lane sums and the Parseval total of
+// the bins at hand one or two to a gap through all the others.  The row store is a buffer store with the lanes >= MU out of range,
+// in place of a branch; packed fp32 instructions, which cost a gap more than the two they replace, are kept apart by "v" constraints.
+// No operation on a score changed: the same operands in the same order.
 #pragma once
 #include "seg_kernels.hpp"
 
@@ -48,8 +61,8 @@ struct SegWCfg {
     static constexpr int OFF = 16 * KT - 1;           // window index of sample offset 0: t = n' - r in [-(16 KT - 1), 16 RT - 1]
     static constexpr int WSTR = 16 * (RT + KT);       // window elements per segment (one spare)
     static_assert(RT >= 1 && RT + KT <= PPL, "the window is the first RT and the last KT register slots of a lane");
-    // one wave per SIMD: the four segments' fragments (160 registers) and two sets of B fragments stay in the register file (with the
-    // accumulation registers); two waves spill 61 registers.  The matrix loop is 27 k cycles per slot, the forward transform ~1 k.
+    // one wave per SIMD: the four segments' fragments (160 registers) and two sets of B fragments stay in the accumulation registers,
+    // two sets of accumulators (96) in the arch VGPRs; two waves spill.  The matrix loop is 27 k cycles per slot, the forward transform ~1 k.
     static constexpr int WAVES = 1;
     static constexpr size_t lds_bytes() {
         return (size_t)SegCfg<256>::LDS_ELEMS * sizeof(cf) + (size_t)(SegCfg<256>::BLOCK / 64) * CT * WSTR * sizeof(cf);
@@ -102,16 +115,16 @@ DEVI void segw_body(const SegWArgs &w, const int blk) {
     const auto xr = mk_rsrc(a.x + (size_t)bk * (size_t)a.xstride, (unsigned)a.N * sizeof(cf));
     const auto qr = mk_rsrc(a.Qs, (unsigned)a.dper * (unsigned)(L * sizeof(float)));
     const auto br = mk_rsrc(w.Wb, (unsigned)a.dper * (unsigned)(KT * 2 * 64 * 16));
-    auto load_q = [&](cf (&dst)[PPL / 2], int bin) {
+    auto load_q = [&](cf (&dst)[PPL / 2], int so) {
 #pragma unroll
         for (int jj = 0; jj < PPL / 4; ++jj)
-            buf_load_cf2(qr, g * 4 * (int)sizeof(float), bin * (L * (int)sizeof(float)) + jj * NT * 4 * (int)sizeof(float), dst[2 * jj], dst[2 * jj + 1]);
+            buf_load_cf2(qr, g * 4 * (int)sizeof(float) + jj * NT * 4 * (int)sizeof(float), so, dst[2 * jj], dst[2 * jj + 1]);
     };
-    auto load_b = [&](seg_h8 (&hi)[KT], seg_h8 (&lo)[KT], int bin) {
+    auto load_b = [&](seg_h8 (&hi)[KT], seg_h8 (&lo)[KT], int so) {
 #pragma unroll
         for (int kk = 0; kk < KT; ++kk) {
-            hi[kk] = __builtin_bit_cast(seg_h8, __builtin_amdgcn_raw_buffer_load_b128(br, lane * 16, (bin * KT + kk) * 2 * 1024, 0));
-            lo[kk] = __builtin_bit_cast(seg_h8, __builtin_amdgcn_raw_buffer_load_b128(br, lane * 16, ((bin * KT + kk) * 2 + 1) * 1024, 0));
+            hi[kk] = __builtin_bit_cast(seg_h8, __builtin_amdgcn_raw_buffer_load_b128(br, lane * 16 + kk * 2 * 1024, so, 0));
+            lo[kk] = __builtin_bit_cast(seg_h8, __builtin_amdgcn_raw_buffer_load_b128(br, lane * 16 + (kk * 2 + 1) * 1024, so, 0));
         }
     };
     constexpr int so_x = NT * (int)sizeof(cf);
@@ -125,6 +138,10 @@ DEVI void segw_body(const SegWArgs &w, const int blk) {
     // no bin waits for a load at the head of its products
     const bool one_chunk = jb1 - jb0 <= 64;
     int wexl = jb0 + lane < jb1 ? w.Wexp[jb0 + lane] : 0;
+    // the row store (PRESUM: lane 0 the sum, lanes < MU zeros) as a buffer store: bytes from bin to bin, and each lane's offset in a
+    // bin's rows -- lanes >= MU beyond any buffer size, so that the hardware drops them
+    const int pstep = __builtin_amdgcn_readfirstlane(a.MU * a.parts * (int)sizeof(float));
+    const int pvo = lane < a.MU ? lane * a.parts * (int)sizeof(float) : 0x7FFFFFFF;
 
     for (int slot = s0; slot < s1; ++slot) {
         cf v[PPL];
@@ -201,6 +218,8 @@ DEVI void segw_body(const SegWArgs &w, const int blk) {
                     ahi[c][di][j] = h;
                     alo[c][di][j] = (_Float16)(sv - (float)h);
                 }
+                asm("" : "+a"(ahi[c][di]));
+                asm("" : "+a"(alo[c][di]));
             }
         }
         xsync<1>();       // the windows are rewritten by the next slot
@@ -214,21 +233,34 @@ DEVI void segw_body(const SegWArgs &w, const int blk) {
                 __builtin_amdgcn_s_waitcnt(0x0F70);         // vmcnt(0)
             }
             const int jc1 = min(jb1, jc + 64);
+            const auto pr = mk_rsrc(a.partials + ((size_t)(a.part_row0 + bk * a.dper + jc) * a.MU) * a.parts + slot, 64u * (unsigned)pstep);
             SegWBin<KT> b0, b1;
             seg_f4 acc0[CT][RT], acc1[CT][RT];
+            // carried from step to step: the row of the bin before, stored ahead of the next step's table fetches (nothing yet: every lane
+            // out of range)
+            unsigned pend = 0u;
+            int pendvo = 0x7FFFFFFF;
             // the Parseval total of the bin's filters (segf_body)
             auto parseval = [&](const SegWBin<KT> &b) {
-                cf t2[2] = {mkc(0.f, 0.f), mkc(0.f, 0.f)};
+                float tx[2] = {0.f, 0.f}, ty[2] = {0.f, 0.f};
 #pragma unroll
-                for (int j = 0; j < PPL / 2; ++j) t2[j & 1] = __builtin_elementwise_fma(pp[j], b.q[j], t2[j & 1]);
-                return (t2[0].x + t2[0].y) + (t2[1].x + t2[1].y);
+                for (int j = 0; j < PPL / 2; ++j) {
+                    tx[j & 1] = __builtin_fmaf(pp[j].x, b.q[j].x, tx[j & 1]);
+                    ty[j & 1] = __builtin_fmaf(pp[j].y, b.q[j].y, ty[j & 1]);
+                    asm("" : "+v"(tx[j & 1]), "+v"(ty[j & 1]));
+                }
+                float s0 = tx[0] + ty[0];
+                asm("" : "+v"(s0));
+                return s0 + (tx[1] + ty[1]);
             };
             auto fetch = [&](SegWBin<KT> &b, int bin) {
-                load_q(b.q, bin);
-                load_b(b.hi, b.lo, bin);
+                load_b(b.hi, b.lo, bin * (KT * 2 * 1024));
+                load_q(b.q, bin * (L * (int)sizeof(float)));
             };
             // the wrap products: per segment, RT row tiles x KT K-steps x (lo.hi, hi.lo, hi.hi)
-            auto products = [&](seg_f4 (&acc)[CT][RT], const SegWBin<KT> &b) {
+            auto products = [&](seg_f4 (&acc)[CT][RT], SegWBin<KT> &b) {
+#pragma unroll
+                for (int kk = 0; kk < KT; ++kk) asm("" : "+a"(b.hi[kk]), "+a"(b.lo[kk]));
 #pragma unroll
                 for (int c = 0; c < CT; ++c) {
 #pragma unroll
@@ -257,6 +289,7 @@ DEVI void segw_body(const SegWArgs &w, const int blk) {
                     for (int rt = 0; rt < RT; ++rt) {
                         const seg_f4 t = acc[c][rt];
                         sq[rt] = __builtin_fmaf(t.x, t.x, t.y * t.y) + __builtin_fmaf(t.z, t.z, t.w * t.w);
+                        asm("" : "+v"(sq[rt]));
                     }
                     float s = sq[0];
 #pragma unroll
@@ -272,26 +305,44 @@ DEVI void segw_body(const SegWArgs &w, const int blk) {
                 const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sv), 16));
                 const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sv), 32));
                 const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sv), 48));
-                return (r0 + r1) + (r2 + r3);
+                float r01 = r0 + r1;
+                asm("" : "+v"(r01));
+                return r01 + (r2 + r3);
             };
-            auto store = [&](float total, int jb) {
-                if (lane < a.MU)
-                    a.partials[((size_t)(a.part_row0 + bk * a.dper + jb) * a.MU + lane) * a.parts + slot] = lane == 0 ? total * a.scale : 0.f;
-            };
-            // one bin's products with the bin before's finish between them, two vector instructions to a product (16 cycles of the
-            // matrix pipe, four issue slots); the tables of the bin after (clamped to the chunk: the last one is fetched twice, into
-            // the set nobody reads) are requested first
+            auto row = [&](float total) { return lane == 0 ? __float_as_uint(total * a.scale) : 0u; };
+            auto store = [&](unsigned val, int vo, int so) { __builtin_amdgcn_raw_buffer_store_b32(val, pr, vo, so, 0); };
+            auto row_off = [&](int jb) { return __builtin_amdgcn_readfirstlane(max(jb - jc, 0)) * pstep; };      // (jb = jc - 1: nothing carried yet)
+            // one bin's products with the bin before's finish between them, at most two other instructions to a product (16 cycles of the
+            // matrix pipe, of which the MFMA holds the issue for 8); the row carried from the step before is stored and the tables of
+            // the bin after (clamped to the chunk: the last one is fetched twice, into the set nobody reads) are requested first, all
+            // memory instructions of a step within its first 14 gaps
             auto step = [&](seg_f4 (&accn)[CT][RT], SegWBin<KT> &bn, const seg_f4 (&accp)[CT][RT], SegWBin<KT> &bp, float totp, int jb) {
-                const float totn = parseval(bn);
+                store(pend, pendvo, row_off(jb - 1));
                 fetch(bp, min(jb + 2, jc1 - 1));
                 products(accn, bn);
                 const float total = finish(accp, totp, jb);
+                const float totn = parseval(bn);
+                pend = row(total);
+                pendvo = pvo;
 #pragma unroll
                 for (int i = 0; i < CT * RT * KT * 3; ++i) {
                     __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);        // one MFMA
-                    __builtin_amdgcn_sched_group_barrier(0x2, 2, 0);        // two VALU
+                    if (i < 4) {
+                        if (i == 2) {
+                            __builtin_amdgcn_sched_group_barrier(0x40, 1, 0);
+                            __builtin_amdgcn_sched_group_barrier(0x4, 1, 0);
+                        } else {
+                            __builtin_amdgcn_sched_group_barrier(0x4, 2, 0);
+                        }
+                    } else if (i < 14) {
+                        __builtin_amdgcn_sched_group_barrier(0x20, 1, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x6, 1, 0);
+                    } else if ((i & 3) && i < 96) {
+                        __builtin_amdgcn_sched_group_barrier(0x6, 1, 0);
+                    } else {
+                        __builtin_amdgcn_sched_group_barrier(0x6, 2, 0);
+                    }
                 }
-                store(total, jb);
                 return totn;
             };
             fetch(b0, jc);
@@ -301,13 +352,15 @@ DEVI void segw_body(const SegWArgs &w, const int blk) {
             int jb = jc;
             while (true) {
                 if (jb + 1 >= jc1) {
-                    store(finish(acc0, tot0, jb), jb);
+                    store(pend, pendvo, row_off(jb - 1));
+                    store(row(finish(acc0, tot0, jb)), pvo, row_off(jb));
                     break;
                 }
                 tot1 = step(acc1, b1, acc0, b0, tot0, jb);
                 ++jb;
                 if (jb + 1 >= jc1) {
-                    store(finish(acc1, tot1, jb), jb);
+                    store(pend, pendvo, row_off(jb - 1));
+                    store(row(finish(acc1, tot1, jb)), pvo, row_off(jb));
                     break;
                 }
                 tot0 = step(acc0, b0, acc1, b1, tot1, jb);

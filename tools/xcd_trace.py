@@ -1,6 +1,6 @@
 """How evenly does the search grid drain?  Needs a variant build with -DMFB_SEG_TRACE (start / end time and XCC of every
 workgroup of the branch-free search kernel):
-    hipcc --offload-arch=gfx950 -O3 -std=c++17 -shared -fPIC -pthread -DMFB_SEG_TRACE -o build_var/libmfbank_trace.so pycusdr_amd/csrc/mfbank.hip
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -amdgpu-mfma-vgpr-form -shared -fPIC -pthread -DMFB_SEG_TRACE -o build_var/libmfbank_trace.so pycusdr_amd/csrc/mfbank.hip
     MFBANK_LIB=build_var/libmfbank_trace.so python tools/xcd_trace.py [wg_per_cu] [D]
 Prints, per XCC, the workgroups it ran, when its last one ended and its summed busy time, relative to the kernel."""
 import ctypes as C
