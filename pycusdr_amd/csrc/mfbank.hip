@@ -98,6 +98,9 @@ struct mfb_ctx {
     // copy into pageable memory is staged by the runtime with a round trip of its own per copy
     uint8_t *h_back;
     size_t back_cap;
+    // the pick's own page-locked slot: k_pick stores its two floats there itself (h_pick_dev: the slot as the device addresses it),
+    // so that no copy -- a blit kernel and its dispatch gap for 8 bytes -- stands between the kernel and the host's read
+    float *h_pick, *h_pick_dev;
     // Host mirror of the spectrum for small blocks.  The reference keeps the spectrum in host-mapped memory and reads
     // its SNR windows straight from there (DB:456-457, 651-661); here the first mfb_get_spectrum on a handle turns on
     // an asynchronous copy of every new spectrum (own stream, beside the search), so that later window reads cost no
@@ -525,6 +528,8 @@ static int create_impl(mfb_ctx *c) {
     c->back_cap = (size_t)3 * (c->N / 2) * sizeof(int) + ((size_t)256 << 10);
     if (c->back_cap < ((size_t)64 << 10)) c->back_cap = (size_t)64 << 10;
     HIPCHK(hipHostMalloc((void **)&c->h_back, c->back_cap, hipHostMallocDefault));
+    HIPCHK(hipHostMalloc((void **)&c->h_pick, 2 * sizeof(float), hipHostMallocDefault));
+    HIPCHK(hipHostGetDevicePointer((void **)&c->h_pick_dev, c->h_pick, 0));
     HIPCHK(dev_alloc((void **)&c->d_x, nb));
     HIPCHK(dev_alloc((void **)&c->d_X, nb));
     HIPCHK(dev_alloc((void **)&c->d_masks, nb * M));
@@ -685,6 +690,7 @@ extern "C" int mfb_destroy(mfb_ctx *c) {
     }
     if (c->s2) (void)hipStreamDestroy(c->s2);
     if (c->h_back) (void)hipHostFree(c->h_back);
+    if (c->h_pick) (void)hipHostFree(c->h_pick);
     if (c->h_seed) (void)hipHostFree(c->h_seed);
     if (c->h_X) (void)hipHostFree(c->h_X);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
@@ -1619,16 +1625,28 @@ static int fsm_prepare(mfb_ctx *c, bool span, int rows) {
 //
 // The matrix-core form (k_segw) plans for itself.  A wave of it pays a slot's prologue -- samples, window, forward transform and the
 // 160 fragment registers, the matrix pipe idle and nothing else on the SIMD -- once per rectangle, so its rectangle is the group's
-// whole share of bins, in equal chunks of at most SEGW_FB (C2: 32 bins, one chunk; C3: four chunks of 32), and SEGW_FS slots
+// whole share of bins, in equal chunks of at most SEGW_FB (256 bins: 32, one chunk; 1024: four chunks of 32), and SEGW_FS slots
 // (measured, profiles/r12_wrap_slots.md: C2 2055 Msamples/s at 16 x 1, 2295 at 32 x 1, 2316 at 32 x 2, 2310 ... 2323 at 32 x 5, 2273
 // at 32 x 10, one launch round with nothing to even out).  It holds one wave per SIMD, not three: its small-launch bound is a wave for
-// every SIMD, reached by giving up slots per wave first, which cost nothing, and bins only then.  What a group is does not depend on
-// the form, and which form runs does not depend on the rectangle (wrap_kt).
+// every SIMD, reached by giving up slots per wave first, which cost nothing, and bins only then.
+//
+// The wide plan of k_segw (profiles/r14_wrap_wide.md): chunks of at most SEGW_WIDE_FB = 64 bins, so that a slot's fragments are built
+// by half as many waves (C3 1.068x, 384 bins 1.07x, C2 1.03x on top of the pick's copy).  Its groups are always groups of BINS, with
+// the four waves of a workgroup on four slots of the same bins: they fetch the same 7 KiB of tables a bin (Wb 6 KiB, Qs 1 KiB) at
+// about the same time, so three of four fetches end in the CU's vector cache.  Over groups of slots the four waves are the four
+// chunks of one slot, every fetch goes to the L2 (measured at C2: 20.7 M L2 hits a launch against 7.0 M) and 64 bins gain 1 %
+// instead of 4.  So where an eighth of the bins does not fill a chunk and a quarter does (Dtot <= 256), the grid has FOUR groups,
+// each on a pair of XCDs (blockIdx % 4); from there on eight.  Under 128 bins the plan above stands.  A rectangle twice as long needs
+// twice the rounds to even out CUs that finish at different times, so the wide plan applies only where a launch of one-slot
+// rectangles has four waves for every SIMD, and it takes the most slots a wave (5 ... 1) that keep those four rounds (C2: 5040 waves
+// of 64 x 1; C3: 5040 of 64 x 4).  Anything smaller gets the plan above, unchanged.  Which form runs does not depend on the
+// rectangle or the groups (wrap_kt).
 struct FsmPlan {
     bool ok, segw;
     int nsg, gbins, fb, fs, nbc, nsc;
 };
 constexpr int SEGW_FB = 32, SEGW_FS = 5;
+constexpr int SEGW_WIDE_FB = 64, SEGW_WIDE_ROUNDS = 4;
 // whether launch_fsm takes k_segw<13, 3>: the bank, the basis and the block length decide (wrap_kt), nothing else
 static bool fsm_segw(const mfb_ctx *c, int MU) {
     return wrap_kt(c, c->basis == MFB_BASIS_SPAN, MU) == 3;
@@ -1651,6 +1669,26 @@ static FsmPlan fsm_plan(const mfb_ctx *c, int MU, int nfull, int nb = 1) {
     const bool fb_set = c->fsm_fb > 0 || env_fb > 0, fs_set = c->fsm_fs > 0 || env_fs > 0;
     int fb = c->fsm_fb > 0 ? c->fsm_fb : (env_fb > 0 ? env_fb : (per_fwd / MU > 2 ? per_fwd / MU : 2));
     int fs = c->fsm_fs > 0 ? c->fsm_fs : (env_fs > 0 ? env_fs : (p.segw ? SEGW_FS : 1));
+    if (p.segw && !fb_set && env_gb < 0 && p.nsg > 1 && c->Dtot >= 4 * SEGW_FB) {
+        // the wide plan, where the launch is long enough for it
+        const int wnsg = c->Dtot <= 4 * SEGW_WIDE_FB ? 4 : 8;
+        const int share = (c->Dtot + wnsg - 1) / wnsg;
+        const int chunks = (share + SEGW_WIDE_FB - 1) / SEGW_WIDE_FB;
+        const long long want = (long long)SEGW_WIDE_ROUNDS * 4 * c->num_cus;
+        auto wwaves = [&](int s) { return (long long)nb * wnsg * chunks * ((nfull + s - 1) / s); };
+        if (wwaves(1) >= want) {
+            if (fs > nfull) fs = nfull;
+            while (!fs_set && fs > 1 && wwaves(fs) < want) --fs;
+            p.nsg = wnsg;
+            p.gbins = 1;
+            p.fb = (share + chunks - 1) / chunks;
+            p.fs = fs;
+            p.nbc = (share + p.fb - 1) / p.fb;
+            p.nsc = (nfull + fs - 1) / fs;
+            p.ok = true;
+            return p;
+        }
+    }
     if (fb > c->Dtot) fb = c->Dtot;
     p.gbins = env_gb >= 0 ? (env_gb != 0) : (p.nsg > 1 && c->Dtot >= p.nsg * fb ? 1 : 0);
     if (p.gbins && c->Dtot < p.nsg) p.gbins = 0;
@@ -1991,14 +2029,22 @@ extern "C" int mfb_export_rows_async(mfb_ctx *c, void *dst, int dst_row, int fir
     return MFB_OK;
 }
 
+// the pick k_pick has just been asked for, from the handle's page-locked slot: the kernel stored it there itself, and a kernel's
+// stores to page-locked host memory are the host's to read once its stream has been synchronised (as read_back synchronises)
+static int read_pick(mfb_ctx *c, float res[2]) {
+    HIPCHK(sync_streams(c));
+    res[0] = c->h_pick[0];
+    res[1] = c->h_pick[1];
+    return MFB_OK;
+}
+
 extern "C" int mfb_pick_column(mfb_ctx *c, const void *column, int num, int offset, float res[2]) {
     if (!c || !column || !res || num < 1 || offset < 0) return MFB_ERR_ARG;
     if (!c->sum_all) return MFB_ERR_STATE;   // a single column is the whole table only under SUM_ALL_MASKS
     HIPCHK(hipSetDevice(c->device));
-    hipLaunchKernelGGL(k_pick, dim3(1), dim3(64), 0, c->stream, (const float *)column, c->d_res, num, offset, 1, 1);
+    hipLaunchKernelGGL(k_pick, dim3(1), dim3(64), 0, c->stream, (const float *)column, c->d_res, c->h_pick_dev, num, offset, 1, 1);
     HIPCHK(hipGetLastError());
-    const BackPiece bp = {res, c->d_res, 2 * sizeof(float)};
-    return read_back(c, &bp, 1);
+    return read_pick(c, res);
 }
 
 extern "C" int mfb_pick(mfb_ctx *c, const void *scores, int num, int offset, float res[2]) {
@@ -2006,10 +2052,9 @@ extern "C" int mfb_pick(mfb_ctx *c, const void *scores, int num, int offset, flo
     if (!scores && (num != c->D || offset != c->Doff)) return MFB_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
     const float *in = scores ? (const float *)scores : c->d_sum;
-    hipLaunchKernelGGL(k_pick, dim3(1), dim3(64), 0, c->stream, in, c->d_res, num, offset, c->M, c->sum_all);
+    hipLaunchKernelGGL(k_pick, dim3(1), dim3(64), 0, c->stream, in, c->d_res, c->h_pick_dev, num, offset, c->M, c->sum_all);
     HIPCHK(hipGetLastError());
-    const BackPiece bp = {res, c->d_res, 2 * sizeof(float)};
-    return read_back(c, &bp, 1);
+    return read_pick(c, res);
 }
 
 extern "C" int mfb_find_carrier(mfb_ctx *c, float res[2]) {

@@ -227,10 +227,16 @@ DEVI void pick_body(const float *in, float *res, int num, int offset, int M, int
         res[1] = 10.f * log10f(__fdiv_rn(sVal[0], (float)M));
     }
 }
-__global__ void __launch_bounds__(64) k_pick(const float *in, float *res, int num, int offset, int M, int sum_all) {
+// res: the pick on the device, for the kernels behind it; hres: the same two floats in page-locked host memory (the device's address
+// of it), for the host, which reads them after synchronising the stream -- no copy behind the kernel
+__global__ void __launch_bounds__(64) k_pick(const float *in, float *res, float *hres, int num, int offset, int M, int sum_all) {
     __shared__ float sIdx[64], sVal[64];
     __shared__ float scol[PICK_LDS];
     pick_body(in, res, num, offset, M, sum_all, sIdx, sVal, scol);
+    if (threadIdx.x == 0) {         // lane 0 wrote res[0..1]: its own stores, read back in program order
+        hres[0] = res[0];
+        hres[1] = res[1];
+    }
 }
 
 // |z|^2 the way nvcc contracts in.x*in.x+in.y*in.y (cuda_kernels.cu:1022-1026): fma(x,x,y*y)

@@ -25,8 +25,11 @@
 //
 // The rectangle of bins x slots is this form's own (mfbank.hip, fsm_plan): a slot's prologue -- samples, window, forward transform and
 // the 160 fragment registers -- runs with the matrix pipe idle and nothing else on the SIMD, so a wave takes its group's whole share
-// of bins, up to 32 a chunk, and pays the prologue once for them (profiles/r12_wrap_slots.md: C2 1.13x over 16 bins).  The loads
-// of a slot are not carried into the next: 32 registers of samples across the bin loop cost more than their latency (same write-up).
+// of bins, up to 32 a chunk, and pays the prologue once for them (profiles/r12_wrap_slots.md: C2 1.13x over 16 bins) -- up to 64 a
+// chunk where the launch is long enough to keep four rounds of waves (profiles/r14_wrap_wide.md: the fixed part of a slot is 9.4 k
+// cycles beside 2.13 k a bin).  The groups of that plan are groups of bins, four of them up to 256 bins: the four waves of a workgroup
+// then walk the same bins on four slots and share the table fetches in the CU's vector cache, which four chunks of one slot do not.  The loads
+// of a slot are not carried into the next: 32 registers of samples across the bin loop cost more than their latency (r12).
 //
 // Where the values live and how a step of the bin loop issues (profiles/r13_wrap_issue.md).  With one wave on the SIMD a 16x16x32 MFMA
 // holds the vector issue for 8 of its 16 cycles and every other instruction costs about 4, so a gap between two MFMAs hides two
