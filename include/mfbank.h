@@ -55,7 +55,7 @@ int mfb_abi_version(void);   /* 2: search paths, mfb_xcorr; 3: mfb_set_search_mo
                               * mfb_receive_blocks_end_record; 8: mfb_hostcopy_*; 9: mfb_set_batch_overlap, mfb_get_batch_scores, mfb_get_search_info, mfb_set_cu_share, mfb_receive_blocks_end_record
                               * reports the size it needs.  Calls added without a change to an existing prototype do not bump it: a caller
                               * finds them by symbol (dlsym) -- mfb_set_sample_format, mfb_get_sample_format, mfb_input_buffer_raw,
-                              * mfb_window_buffer_raw, mfb_debug_unpack */
+                              * mfb_window_buffer_raw, mfb_debug_unpack, mfb_debug_envelope, mfb_debug_code_rate, mfb_debug_centres */
 
 /* Create a handle on HIP device `device` for blocks of N = 2^log2N samples, `num_dopplers`
  * Doppler bins plus `doppler_offset` leading noise-reference bins (DB:150-159), M matched
@@ -623,6 +623,28 @@ int mfb_window_buffer_raw(mfb_ctx *ctx, int which, int max_blocks, int block_str
  * mfb_set_sample_format), out_c64 = nsamples complex64.  The product paths do not use it.  No reference counterpart (its
  * callers convert with numpy on the host). */
 int mfb_debug_unpack(int device, int format, float scale, const void *raw, size_t nsamples, float *out_c64);
+
+/* Test seams of the demodulation tail: the three kernels between the matched filters and the bit stream, launched as the product
+ * launches them, on INJECTED inputs (tests/test_gpu_demod_tail.py).  Handle-less: device buffers of their own, a synchronous copy
+ * back; the product paths do not use them.  MFB_ERR_UNSUPPORTED: more than 2^26 complex64 input elements.
+ *   mfb_debug_envelope   sumXCorrBuffMasks (CU:191-205) on xc complex64 [nb][M][N]: env float32 [nb][N], env[b][n] = sum over
+ *                        filters off <= m < M - off of |xc[b][m][n]|^2, on the grid mfb_demodulate uses (1024 x nb workgroups of 256).
+ *                        Any N >= 1; off as mfb_create's code_search_mask_offset (0 <= 2 * off < M).
+ *   mfb_debug_code_rate  findCodeRateAndPhase (CU:236-320) over [offset, offset + len) of each of the nb windows P complex64 [nb][n],
+ *                        twice: the kernel of mfb_demodulate once per window -> triples float32 [nb][3] = {k*, arg P[k*], |P[k*]|^2};
+ *                        the one-launch form of mfb_receive_block(s) over all nb windows (block length n, records 256 bytes apart)
+ *                        -> block_triples [nb][3], and what it derives per window (DB:733-752, 994-999): rate double [nb][2] =
+ *                        {spSym, codeOffset}, launch_args float32 [nb][2] = the two arguments of findCentres, counts int32 [nb][2] =
+ *                        {symbol count, rate_fallback}.  0 <= offset, 0 <= len, offset + len <= n as mfb_demodulate demands.
+ *   mfb_debug_centres    findCentres (CU:78-146) on sig complex64 [M][lenSig] with nthreads threads in workgroups of 256.  The three
+ *                        outputs hold ceil(nthreads / 256) * 256 entries each, every byte 0x5a before the launch: what the kernel
+ *                        does not write (entries from `capacity` on) comes back as 0x5a5a5a5a.  spSym >= 2 as mfb_find_centres
+ *                        demands, offset >= 0, op 0..2, nthreads <= 2^20, lenSig <= 2^22. */
+int mfb_debug_envelope(int device, const float *xc_c64, int nb, int M, int N, int off, float *env);
+int mfb_debug_code_rate(int device, const float *P_c64, int nb, int n, int offset, int len, int spsym_min, int capacity, float *triples,
+                        float *block_triples, double *rate, float *launch_args, int32_t *counts);
+int mfb_debug_centres(int device, const float *sig_c64, int M, int lenSig, int W, int op, float spSym, float offset, int capacity,
+                      int nthreads, int32_t *sym, int32_t *centres, float *magnitude);
 
 /* A host copy worker for the receive loop: the reference's loop copies every chunk of samples twice on its one thread, into the
  * ring buffer (sigFIFO.py:62-84) and from there into the page-locked input buffer (`raw[ov:] = sigIn.getBlock()`, DP:287,337).

@@ -168,6 +168,9 @@ PROTOTYPES = {
     'mfb_input_buffer_raw': (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     'mfb_window_buffer_raw': (_i, [_vp, _i, _i, _i, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     'mfb_debug_unpack': (_i, [_i, _i, C.c_float, _vp, C.c_size_t, _vp]),
+    'mfb_debug_envelope': (_i, [_i, _vp, _i, _i, _i, _i, _vp]),
+    'mfb_debug_code_rate': (_i, [_i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'mfb_debug_centres': (_i, [_i, _vp, _i, _i, _i, _i, C.c_float, C.c_float, _i, _i, _vp, _vp, _vp]),
     'mfb_hostcopy_create': (_i, [C.POINTER(_vp)]),
     'mfb_hostcopy_submit': (_i, [_vp, _vp, _vp, C.c_size_t]),
     'mfb_hostcopy_drain': (_i, [_vp]),

@@ -3383,6 +3383,121 @@ extern "C" int mfb_debug_unpack(int device, int format, float scale, const void 
     return rc;
 }
 
+// Test seams of the demodulation tail: k_envelope, k_code_rate / k_code_rate_block and k_centres, launched as the product launches
+// them, on INJECTED inputs.  Handle-less: buffers of their own on the null stream, a synchronous copy back.
+#define DBG_TAIL_MAX_ELEMS ((size_t)1 << 26)      // complex64 elements a seam takes (512 MiB)
+static int debug_device_ok(int device) {
+    int ndev = 0;
+    HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return MFB_ERR_ARG;
+    HIPCHK(hipSetDevice(device));
+    return MFB_OK;
+}
+extern "C" int mfb_debug_envelope(int device, const float *xc_c64, int nb, int M, int N, int off, float *env) {
+    if (!xc_c64 || !env || nb < 1 || M < 1 || N < 1 || off < 0 || 2 * off >= M) return MFB_ERR_ARG;
+    if (nb > 65535 || (size_t)nb * (size_t)M * (size_t)N > DBG_TAIL_MAX_ELEMS) return MFB_ERR_UNSUPPORTED;
+    int rc = debug_device_ok(device);
+    if (rc) return rc;
+    const size_t nin = (size_t)nb * M * N, nout = (size_t)nb * N;
+    cf *d_xc = nullptr;
+    float *d_env = nullptr;
+    auto run = [&]() -> int {
+        HIPCHK(hipMalloc((void **)&d_xc, nin * sizeof(cf)));
+        HIPCHK(hipMalloc((void **)&d_env, nout * sizeof(float)));
+        HIPCHK(hipMemcpy(d_xc, xc_c64, nin * sizeof(cf), hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(d_env, 0x5a, nout * sizeof(float)));
+        hipLaunchKernelGGL(k_envelope, dim3(1024, nb), dim3(256), 0, nullptr, (const cf *)d_xc, d_env, N, M, off);     // as demod_enqueue
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpy(env, d_env, nout * sizeof(float), hipMemcpyDeviceToHost));
+        return MFB_OK;
+    };
+    rc = run();
+    if (d_xc) (void)hipFree(d_xc);
+    if (d_env) (void)hipFree(d_env);
+    return rc;
+}
+
+#define DBG_REC_STRIDE 256       // bytes from one window's BlockScalars to the next (static_assert: sizeof(BlockScalars) <= 256)
+extern "C" int mfb_debug_code_rate(int device, const float *P_c64, int nb, int n, int offset, int len, int spsym_min, int capacity,
+                                   float *triples, float *block_triples, double *rate, float *launch_args, int32_t *counts) {
+    if (!P_c64 || !triples || !block_triples || !rate || !launch_args || !counts || nb < 1 || n < 1) return MFB_ERR_ARG;
+    if (offset < 0 || len < 0 || (long long)offset + len > n) return MFB_ERR_ARG;          // as mfb_demodulate
+    if (nb > 65535 || (size_t)nb * (size_t)n > DBG_TAIL_MAX_ELEMS) return MFB_ERR_UNSUPPORTED;
+    int rc = debug_device_ok(device);
+    if (rc) return rc;
+    const size_t nin = (size_t)nb * n;
+    cf *d_P = nullptr;
+    float *d_cr = nullptr;           // [2][nb][3]: k_code_rate's triples, then k_code_rate_block's
+    uint8_t *d_sc = nullptr;
+    std::vector<uint8_t> recs((size_t)nb * DBG_REC_STRIDE);
+    auto run = [&]() -> int {
+        HIPCHK(hipMalloc((void **)&d_P, nin * sizeof(cf)));
+        HIPCHK(hipMalloc((void **)&d_cr, (size_t)6 * nb * sizeof(float)));
+        HIPCHK(hipMalloc((void **)&d_sc, recs.size()));
+        HIPCHK(hipMemcpy(d_P, P_c64, nin * sizeof(cf), hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(d_cr, 0x5a, (size_t)6 * nb * sizeof(float)));
+        HIPCHK(hipMemset(d_sc, 0, recs.size()));
+        for (int b = 0; b < nb; ++b)
+            hipLaunchKernelGGL(k_code_rate, dim3(1), dim3(1024), 0, nullptr, (const cf *)(d_P + (size_t)b * n), d_cr + 3 * (size_t)b, offset,
+                               len);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_code_rate_block, dim3(nb), dim3(1024), 0, nullptr, (const cf *)d_P, d_cr + 3 * (size_t)nb, offset, len, n,
+                           spsym_min, capacity, reinterpret_cast<BlockScalars *>(d_sc), (size_t)DBG_REC_STRIDE);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpy(triples, d_cr, (size_t)3 * nb * sizeof(float), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(block_triples, d_cr + 3 * (size_t)nb, (size_t)3 * nb * sizeof(float), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(recs.data(), d_sc, recs.size(), hipMemcpyDeviceToHost));
+        return MFB_OK;
+    };
+    rc = run();
+    if (d_P) (void)hipFree(d_P);
+    if (d_cr) (void)hipFree(d_cr);
+    if (d_sc) (void)hipFree(d_sc);
+    if (rc) return rc;
+    for (int b = 0; b < nb; ++b) {
+        BlockScalars sc;
+        memcpy(&sc, recs.data() + (size_t)b * DBG_REC_STRIDE, sizeof(sc));
+        rate[2 * b] = sc.spSym;
+        rate[2 * b + 1] = sc.codeOffset;
+        launch_args[2 * b] = sc.spSymF;
+        launch_args[2 * b + 1] = sc.offsetF;
+        counts[2 * b] = sc.count;
+        counts[2 * b + 1] = sc.rate_fallback;
+    }
+    return MFB_OK;
+}
+
+extern "C" int mfb_debug_centres(int device, const float *sig_c64, int M, int lenSig, int W, int op, float spSym, float offset,
+                                 int capacity, int nthreads, int32_t *sym, int32_t *cen, float *mag) {
+    if (!sig_c64 || !sym || !cen || !mag || M < 1 || lenSig < 1 || W < 1 || op < 0 || op > 2 || capacity < 0 || nthreads < 1)
+        return MFB_ERR_ARG;
+    if (!(spSym >= 2.0f) || !(offset >= 0.f) || !(offset < 2147483648.f)) return MFB_ERR_ARG;       // as mfb_find_centres; a code phase is >= 0
+    if (nthreads > (1 << 20) || lenSig > (1 << 22) || (size_t)M * (size_t)lenSig > DBG_TAIL_MAX_ELEMS) return MFB_ERR_UNSUPPORTED;
+    int rc = debug_device_ok(device);
+    if (rc) return rc;
+    const int nblk = (nthreads + 255) / 256;
+    const size_t nin = (size_t)M * lenSig, nent = (size_t)nblk * 256;
+    cf *d_sig = nullptr;
+    int32_t *d_out = nullptr;        // [3][nent]: sym, cen, mag
+    auto run = [&]() -> int {
+        HIPCHK(hipMalloc((void **)&d_sig, nin * sizeof(cf)));
+        HIPCHK(hipMalloc((void **)&d_out, 3 * nent * sizeof(int32_t)));
+        HIPCHK(hipMemcpy(d_sig, sig_c64, nin * sizeof(cf), hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(d_out, 0x5a, 3 * nent * sizeof(int32_t)));        // the canary: what the kernel leaves alone stays 0x5a5a5a5a
+        hipLaunchKernelGGL(k_centres, dim3(nblk), dim3(256), 0, nullptr, (int *)d_out, (int *)(d_out + nent),
+                           reinterpret_cast<float *>(d_out + 2 * nent), (const cf *)d_sig, spSym, offset, lenSig, M, W, op, capacity);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpy(sym, d_out, nent * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(cen, d_out + nent, nent * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(mag, d_out + 2 * nent, nent * sizeof(float), hipMemcpyDeviceToHost));
+        return MFB_OK;
+    };
+    rc = run();
+    if (d_sig) (void)hipFree(d_sig);
+    if (d_out) (void)hipFree(d_out);
+    return rc;
+}
+
 extern "C" int mfb_find_centres(mfb_ctx *c, float spSym, float offset, int op, int count, int32_t *sym, int32_t *cen,
                                 float *mag) {
     if (!c || !sym || !cen || !mag) return MFB_ERR_ARG;

@@ -325,7 +325,17 @@ DEVI void centres_body(int *outSym, int *outIdx, float *mag, const cf *sig, floa
     if (x >= capacity) return;
     const float half = (float)(W / 2);  // WINDOW_WIDTH/2 is an integer division (demodulator_base.py:407)
     const float base = __fmaf_rn((float)x, spSym, -half);
-    int arrayIdx = (int)__fadd_rn(base, offset);
+    const float start = __fadd_rn(base, offset);
+    // A start at or past the end is decided in float, before the conversion: x * spSym may pass 2^31, where (int) is undefined and
+    // arrayIdx + W overflows (a NaN start lands here too).  lenSig <= 2^22 is exact in fp32 and truncation never crosses an
+    // integer, so start < lenSig <=> (int)start < lenSig: every start inside the block takes the branch it always took.
+    if (!(start < (float)lenSig)) {     // a symbol past the end of the block: the reference leaves its buffers untouched there
+        outSym[x] = INT32_MIN;
+        outIdx[x] = INT32_MIN;
+        mag[x] = 0.f;
+        return;
+    }
+    int arrayIdx = (int)start;
     int maxArrayIdx = arrayIdx + W;
     int offsetComp = (int)offset;
     if (arrayIdx < 0) {
@@ -335,28 +345,22 @@ DEVI void centres_body(int *outSym, int *outIdx, float *mag, const cf *sig, floa
     if (maxArrayIdx > lenSig) maxArrayIdx = lenSig;
     maxArrayIdx -= arrayIdx;
     int maxIdx = -1, maxCentreIdx = -1;
-    if (arrayIdx < lenSig) {
-        float maxVal = 0.f;
-        for (int m = 0; m < M; ++m) {
-            const cf *row = sig + (size_t)m * lenSig + arrayIdx;
-            for (int k = 0; k < maxArrayIdx; ++k) {
-                const cf z = row[k];
-                const float tmp = (op == 0) ? abs2c(z) : (op == 1 ? fabsf(z.x) : fabsf(z.y));
-                if (tmp > maxVal) {
-                    maxVal = tmp;
-                    maxIdx = m;
-                    maxCentreIdx = k;
-                }
+    float maxVal = 0.f;
+    for (int m = 0; m < M; ++m) {
+        const cf *row = sig + (size_t)m * lenSig + arrayIdx;
+        for (int k = 0; k < maxArrayIdx; ++k) {
+            const cf z = row[k];
+            const float tmp = (op == 0) ? abs2c(z) : (op == 1 ? fabsf(z.x) : fabsf(z.y));
+            if (tmp > maxVal) {
+                maxVal = tmp;
+                maxIdx = m;
+                maxCentreIdx = k;
             }
         }
-        outSym[x] = maxIdx;
-        outIdx[x] = (int)__fadd_rn(__fadd_rn(base, (float)maxCentreIdx), (float)offsetComp);
-        mag[x] = maxVal;
-    } else {            // a symbol past the end of the block: the reference leaves its buffers untouched there
-        outSym[x] = INT32_MIN;
-        outIdx[x] = INT32_MIN;
-        mag[x] = 0.f;
     }
+    outSym[x] = maxIdx;
+    outIdx[x] = (int)__fadd_rn(__fadd_rn(base, (float)maxCentreIdx), (float)offsetComp);
+    mag[x] = maxVal;
 }
 __global__ void k_centres(int *outSym, int *outIdx, float *mag, const cf *sig, float spSym, float offset,
                           int lenSig, int M, int W, int op, int capacity) {

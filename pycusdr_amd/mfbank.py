@@ -48,6 +48,55 @@ def debug_unpack(raw, fmt, scale=None, device=0, out=None):
     return out
 
 
+def debug_envelope(xc, off=0, device=0):
+    """Test seam (mfb_debug_envelope): k_envelope on ``xc`` complex64 [nb][M][N] (or [M][N]) with the product's launch shape;
+    float32 [nb][N] (or [N]): the sum of |xc[m]|^2 over the filters off <= m < M - off."""
+    lib = _lib.load()
+    xc = np.ascontiguousarray(xc)
+    if xc.dtype != np.complex64 or xc.ndim not in (2, 3):
+        raise TypeError(f'xc is complex64 [nb][M][N] or [M][N], got {xc.dtype} {xc.shape}')
+    nb, M, N = (1,) + xc.shape if xc.ndim == 2 else xc.shape
+    env = np.empty((nb, N), np.float32)
+    _lib.check(lib.mfb_debug_envelope(int(device), _ptr(xc), nb, M, N, int(off), _ptr(env)), 'mfb_debug_envelope')
+    return env[0] if xc.ndim == 2 else env
+
+
+def debug_code_rate(P, offset, length, spsym_min=0, capacity=0, device=0):
+    """Test seam (mfb_debug_code_rate): the rate argmax over [offset, offset + length) of every window of ``P`` complex64 [nb][n],
+    by k_code_rate (one launch per window) and by k_code_rate_block (one launch, block length n).  A dict: ``triples`` and
+    ``block_triples`` float32 [nb][3] = {k*, arg, |P[k*]|^2}, and the block form's scalars per window: ``spSym``, ``codeOffset``
+    (float64), ``spSymF``, ``offsetF`` (float32), ``count``, ``rate_fallback`` (int32)."""
+    lib = _lib.load()
+    P = np.ascontiguousarray(P)
+    if P.dtype != np.complex64 or P.ndim != 2:
+        raise TypeError(f'P is complex64 [nb][n], got {P.dtype} {P.shape}')
+    nb, n = P.shape
+    tri, btri = np.empty((nb, 3), np.float32), np.empty((nb, 3), np.float32)
+    rate, largs, counts = np.empty((nb, 2), np.float64), np.empty((nb, 2), np.float32), np.empty((nb, 2), np.int32)
+    _lib.check(lib.mfb_debug_code_rate(int(device), _ptr(P), nb, n, int(offset), int(length), int(spsym_min), int(capacity), _ptr(tri),
+                                       _ptr(btri), _ptr(rate), _ptr(largs), _ptr(counts)), 'mfb_debug_code_rate')
+    return dict(triples=tri, block_triples=btri, spSym=rate[:, 0].copy(), codeOffset=rate[:, 1].copy(), spSymF=largs[:, 0].copy(),
+                offsetF=largs[:, 1].copy(), count=counts[:, 0].copy(), rate_fallback=counts[:, 1].copy())
+
+
+DEBUG_CANARY = 0x5a5a5a5a          # what mfb_debug_centres fills its outputs with before the launch
+
+
+def debug_centres(sig, W, op, spSym, offset, capacity, nthreads, device=0):
+    """Test seam (mfb_debug_centres): k_centres on ``sig`` complex64 [M][lenSig] with ``nthreads`` threads.  (sym int32, centres
+    int32, magnitude float32), ceil(nthreads / 256) * 256 entries each; entries the kernel did not write hold DEBUG_CANARY."""
+    lib = _lib.load()
+    sig = np.ascontiguousarray(sig)
+    if sig.dtype != np.complex64 or sig.ndim != 2:
+        raise TypeError(f'sig is complex64 [M][lenSig], got {sig.dtype} {sig.shape}')
+    M, lenSig = sig.shape
+    nent = (int(nthreads) + 255) // 256 * 256
+    sym, cen, mag = np.empty(nent, np.int32), np.empty(nent, np.int32), np.empty(nent, np.float32)
+    _lib.check(lib.mfb_debug_centres(int(device), _ptr(sig), M, lenSig, int(W), int(op), C.c_float(spSym), C.c_float(offset),
+                                     int(capacity), int(nthreads), _ptr(sym), _ptr(cen), _ptr(mag)), 'mfb_debug_centres')
+    return sym, cen, mag
+
+
 class HostCopy:
     """The library's host copy worker (mfb_hostcopy_*): ``submit(dst, dst_off, src)`` queues ``dst[dst_off:dst_off + len(src)] = src``
     for a thread of its own and returns at once; ``drain()`` returns when every queued copy has been made.  Arrays handed to
