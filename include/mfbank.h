@@ -55,7 +55,9 @@ int mfb_abi_version(void);   /* 2: search paths, mfb_xcorr; 3: mfb_set_search_mo
                               * mfb_receive_blocks_end_record; 8: mfb_hostcopy_*; 9: mfb_set_batch_overlap, mfb_get_batch_scores, mfb_get_search_info, mfb_set_cu_share, mfb_receive_blocks_end_record
                               * reports the size it needs.  Calls added without a change to an existing prototype do not bump it: a caller
                               * finds them by symbol (dlsym) -- mfb_set_sample_format, mfb_get_sample_format, mfb_input_buffer_raw,
-                              * mfb_window_buffer_raw, mfb_debug_unpack, mfb_debug_envelope, mfb_debug_code_rate, mfb_debug_centres */
+                              * mfb_window_buffer_raw, mfb_debug_unpack, mfb_debug_envelope, mfb_debug_code_rate, mfb_debug_centres, mfb_set_device_snr,
+                              * mfb_get_block_snr, mfb_debug_band_means (sizeof and offsets of mfb_block_result, mfb_record_layout and
+                              * BlockScalars unchanged: still 9) */
 
 /* Create a handle on HIP device `device` for blocks of N = 2^log2N samples, `num_dopplers`
  * Doppler bins plus `doppler_offset` leading noise-reference bins (DB:150-159), M matched
@@ -250,7 +252,8 @@ typedef struct mfb_block_result {
     double spSym, codeOffset;/* DB:733-752 */
     int32_t count;           /* symbols written to sym / cen / mag */
     int32_t rate_fallback;   /* k* == 0: spSym = 10 (DB:737-740) */
-    int32_t band_len[2];     /* elements of the signal / noise window; > band_capacity: not delivered, fetch with mfb_get_spectrum */
+    int32_t band_len[2];     /* elements of the signal / noise window; > band_capacity: not delivered, fetch with mfb_get_spectrum
+                              * (mfb_set_device_snr: the true lengths; the windows' means are delivered instead, whatever the length) */
 } mfb_block_result;
 /* One block, one call: uploadAndFindCarrier (UHF.py:7-16 -> DB:548-632) + demodulate (DB:711-859, device stages). */
 int mfb_receive_block(mfb_ctx *ctx, const mfb_block_params *params, mfb_block_result *result, int32_t *sym, int32_t *centres,
@@ -427,6 +430,29 @@ int mfb_get_peak_clip_tail(mfb_ctx *ctx, float *host_c64, int count, int32_t *va
  * the number of indices, the first min(count, cap) of them (ascending) into idx.  Valid until `slot` is begun again (each slot keeps its own buffers).
  * MFB_ERR_STATE if that flight is not collected or was not clipped. */
 int mfb_get_block_clips(mfb_ctx *ctx, int slot, int block, int32_t *idx, int cap, int32_t *count);
+
+/* computeSNR's two means on the device (DB:635-667).  The reference takes 20 log10(mean|X_sig| / mean|X_noise| - 1) over two windows
+ * of the block's spectrum on the host (DB:651-661); the block calls above deliver those windows up to band_capacity elements, and a
+ * block of a batch whose windows are longer has no SNR.  With this mode on (off by default), every SEARCHED block of
+ * mfb_receive_block, mfb_receive_block_begin / _end, mfb_receive_blocks_begin / _end and _end_record gets a launch behind its pick that
+ * computes np.mean(np.abs(window)) of both windows as float32 -- window = piece 0 then piece 1 of BlockScalars.band, np.concatenate's
+ * order when the band wraps around 0 Hz; numpy's |x|, its pairwise float32 sum over 8192-element chunks, (float)((double)sum / n); NaN
+ * for an empty window -- bit for bit what numpy gives from the spectrum slices, for windows of ANY length (csrc/snr_kernels.hpp).
+ * Delivery: the first complex64 element of the block's signal-window region -- in its record (off_bands) and in bands_c64 (block b:
+ * bands_c64 + b * 4 * band_capacity floats) -- is (mean_signal, mean_noise); NO spectrum sample is copied, so band_capacity may be 1;
+ * band_len still reports the windows' true lengths; the device-to-host copy stays one per flight.  With the mode on and
+ * band_capacity == 0 the record has no room for them: the means are NOT computed and NOT delivered.  Fixed-shift blocks have no pick
+ * and no SNR, as before.  With the mode off nothing changes: no launch, no byte of any record.
+ * Switching drops the recorded graphs; MFB_ERR_STATE while anything is in flight. */
+int mfb_set_device_snr(mfb_ctx *ctx, int on);
+/* The same two means (DB:651-661: np.mean(np.abs(...)) of the signal and of the noise window) and the windows' lengths of block
+ * `block` (0 for mfb_receive_block_*) of the flight collected last from `slot`.  Valid until `slot` is begun again.  MFB_ERR_STATE if
+ * that flight is not collected, was not searched with mfb_set_device_snr on, or had band_capacity == 0. */
+int mfb_get_block_snr(mfb_ctx *ctx, int slot, int block, float means[2], int32_t lens[2]);
+/* Test seam of mfb_set_device_snr: the same kernel and device function (DB:651-661 on the device) on an INJECTED spectrum X_c64
+ * complex64 [N] and n injected windows pieces int32 [n][2][2] = [piece][start, length], in one launch; means float32 [n].
+ * MFB_ERR_ARG for a piece outside [0, N] or a window longer than N.  Handle-less, on `device`. */
+int mfb_debug_band_means(int device, const float *X_c64, int N, int n, const int32_t *pieces, float *means);
 
 /* Symbol centres on the matched-filter outputs left by mfb_demodulate.  Replaces findCentres
  * (CU:78-146) + the three memcpy_dtoh of cudaFindCentres (DB:996-1006).  Writes `count` =

@@ -125,6 +125,8 @@ PROTOTYPES = {
     'mfb_get_peak_clip_tail': (_i, [_vp, _vp, _i, _ip]),
     'mfb_get_block_clips': (_i, [_vp, _i, _i, _vp, _i, _ip]),
     'mfb_get_batch_scores': (_i, [_vp, _i, _vp]),
+    'mfb_set_device_snr': (_i, [_vp, _i]),
+    'mfb_get_block_snr': (_i, [_vp, _i, _i, _vp, _vp]),
     'mfb_get_search_info': (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     'mfb_set_cu_share': (_i, [_vp, _i, _i]),
     'mfb_receive_blocks_end': (_i, [_vp, _i, C.POINTER(BlockResult), _vp, _vp, _vp, _i, _vp]),
@@ -168,6 +170,7 @@ PROTOTYPES = {
     'mfb_input_buffer_raw': (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     'mfb_window_buffer_raw': (_i, [_vp, _i, _i, _i, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     'mfb_debug_unpack': (_i, [_i, _i, C.c_float, _vp, C.c_size_t, _vp]),
+    'mfb_debug_band_means': (_i, [_i, _vp, _i, _i, _vp, _vp]),
     'mfb_debug_envelope': (_i, [_i, _vp, _i, _i, _i, _i, _vp]),
     'mfb_debug_code_rate': (_i, [_i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'mfb_debug_centres': (_i, [_i, _vp, _i, _i, _i, _i, C.c_float, C.c_float, _i, _i, _vp, _vp, _vp]),

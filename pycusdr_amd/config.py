@@ -1,7 +1,12 @@
 """Config dictionaries with the reference's key layout (config/base.json, config/benchmark/*.json,
 config/CC11xx.json): builders for the geometries the tests and benches use, and ``load_config`` for a user's
 own files in the reference's format (JSON with // comments, layered through "configBase"; the reference
-reads them with rjsmin + pyLoadModularJson, pyCuSDR.py:61)."""
+reads them with rjsmin + pyLoadModularJson, pyCuSDR.py:61).
+
+Optional keys of this port sit in a "HIP" block next to the reference's "CUDA" block of a GPU settings entry
+(``conf['GPU'][name]['HIP']``; read by ``demodulator_base.Demodulator`` and the runner): "search_path", "search_basis",
+"search_mode", "one_call", "device_clip", "sample_format" / "sample_scale", "blocks_per_call", and "device_snr" (true: the two
+means computeSNR divides are taken on the device for every searched block, whatever the length of its spectrum windows)."""
 import copy
 import json
 import os

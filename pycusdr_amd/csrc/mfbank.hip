@@ -56,6 +56,7 @@
 #include "energy_kernels.hpp"
 #include "stream_kernels.hpp"
 #include "clip_kernels.hpp"
+#include "snr_kernels.hpp"
 #include "unpack_kernels.hpp"
 #include "hostcopy.hpp"
 #include "record_layout.hpp"
@@ -70,6 +71,7 @@ struct BlockFlight {      // one block -- or one batch of nb blocks -- between m
     RecordLayout lay;     // where things sit inside a record; lay.bytes apart in the staging buffer (batches)
     unsigned long long seq;
     bool clip;            // the block(s) went through the peak clip (mfb_get_block_clips)
+    bool dsnr;            // searched with mfb_set_device_snr on: the record holds the two window means (mfb_get_block_snr)
 };
 
 constexpr int WG_NB = 32;
@@ -176,6 +178,7 @@ struct mfb_ctx {
     bool use_z2;                  // the transforms being enqueued use d_Z2 (part 2)
     bool s2_busy;                 // something was enqueued on s2 since the last wait for it
     bool batch_overlap;           // mfb_set_batch_overlap
+    bool device_snr;              // mfb_set_device_snr
     int last_batch_blocks;        // blocks of the batch begun last (mfb_get_batch_scores)
     int cu_part, cu_parts;        // mfb_set_cu_share (0, 0: the whole device)
     BlockGraph wgraph2[2][2][2][WG_NB + 1];     // part 2's recorded graphs (wgraph holds part 1's)
@@ -2446,9 +2449,16 @@ static int block_enqueue_p1(mfb_ctx *c, const mfb_block_params *p, const BlkBufs
         } else if ((rc = mfb_search_async(c))) {
             return rc;
         }
+        // (mfb_set_device_snr: no spectrum sample is copied; the windows' means go where the signal window would begin)
         hipLaunchKernelGGL(k_pick_block, dim3(nb), dim3(64), 0, c->stream, (const float *)bb.sum, bb.res, c->D, c->Doff, c->M, c->sum_all,
-                           (const int *)c->d_shifts, c->Dtot, c->N, p->snr_window, (const cf *)bb.X, r.scal, r.bands, geo.bcap, r.rec);
+                           (const int *)c->d_shifts, c->Dtot, c->N, p->snr_window, (const cf *)bb.X, r.scal, r.bands,
+                           c->device_snr ? 0 : geo.bcap, r.rec);
         HIPCHK(hipGetLastError());
+        if (c->device_snr && geo.bcap > 0) {
+            hipLaunchKernelGGL(k_band_means, dim3(2, nb), dim3(SNR_THREADS), 0, c->stream, (const float2 *)bb.X, (size_t)c->N, c->N,
+                               (const int *)&r.scal->band[0][0][0], r.rec, (float *)r.bands, r.rec);
+            HIPCHK(hipGetLastError());
+        }
     } else {
         hipLaunchKernelGGL(k_block_clear, dim3(nb), dim3(1), 0, c->stream, r.scal, r.rec);
         HIPCHK(hipGetLastError());
@@ -2687,6 +2697,7 @@ static void flight_fill(mfb_ctx *c, BlockFlight &f, const mfb_block_params *p, c
     f.nb = nb;
     f.lay = lay;
     f.clip = clip;
+    f.dsnr = c->device_snr && p->mode == MFB_BLOCK_SEARCH && geo.bcap > 0;
 }
 // Enqueue: everything up to and including the ONE device-to-host copy into the flight's page-locked staging; no wait.
 static int block_begin(mfb_ctx *c, const mfb_block_params *p, int slot) {
@@ -2768,7 +2779,9 @@ static void record_unpack(const BlockFlight &f, const uint8_t *h, const BlockSca
     memcpy(sym, h + l.sym, (size_t)n * sizeof(int));
     memcpy(cen, h + l.cen, (size_t)n * sizeof(int));
     memcpy(mag, h + l.mag, (size_t)n * sizeof(float));
-    if (f.mode == MFB_BLOCK_SEARCH && f.bcap > 0) {
+    if (f.dsnr) {
+        memcpy(bands_c64, h + l.bands, sizeof(cf));       // (mean_signal, mean_noise)
+    } else if (f.mode == MFB_BLOCK_SEARCH && f.bcap > 0) {
         const int l0 = hs.band_len[0] < f.bcap ? hs.band_len[0] : f.bcap, l1 = hs.band_len[1] < f.bcap ? hs.band_len[1] : f.bcap;
         memcpy(bands_c64, h + l.bands, (size_t)l0 * sizeof(cf));
         memcpy(bands_c64 + (size_t)2 * f.bcap, h + l.bands + (size_t)f.bcap * sizeof(cf), (size_t)l1 * sizeof(cf));
@@ -2860,6 +2873,30 @@ extern "C" int mfb_set_batch_overlap(mfb_ctx *c, int on) {
         ++c->epoch;               // the recorded graphs belong to the other arrangement
         c->batch_overlap = on != 0;
     }
+    return MFB_OK;
+}
+// The two means of computeSNR's spectrum windows (DB:635-667) on the device instead of the windows themselves (snr_kernels.hpp)
+extern "C" int mfb_set_device_snr(mfb_ctx *c, int on) {
+    if (!c || on < 0 || on > 1) return MFB_ERR_ARG;
+    if (c->flight[0].active || c->flight[1].active) return MFB_ERR_STATE;
+    if (c->device_snr != (on != 0)) {
+        HIPCHK(hipSetDevice(c->device));
+        HIPCHK(sync_streams(c));
+        ++c->epoch;               // the recorded graphs hold the other arrangement
+        c->device_snr = on != 0;
+    }
+    return MFB_OK;
+}
+extern "C" int mfb_get_block_snr(mfb_ctx *c, int slot, int block, float means[2], int32_t lens[2]) {
+    if (!c || slot < 0 || slot > 1 || block < 0 || !means || !lens) return MFB_ERR_ARG;
+    const BlockFlight &f = c->flight[slot];
+    if (f.active || !f.dsnr || block >= (f.nb ? f.nb : 1)) return MFB_ERR_STATE;
+    const uint8_t *h = c->h_blk[slot] + (size_t)block * f.lay.bytes;
+    BlockScalars hs;
+    memcpy(&hs, h + f.lay.scalars, sizeof(hs));
+    memcpy(means, h + f.lay.bands, 2 * sizeof(float));
+    lens[0] = hs.band_len[0];
+    lens[1] = hs.band_len[1];
     return MFB_OK;
 }
 // Device buffers whose addresses recorded graphs hold grow as a group: wait for what uses them, drop the graphs (epoch), free, allocate.
@@ -3414,6 +3451,41 @@ extern "C" int mfb_debug_envelope(int device, const float *xc_c64, int nb, int M
     rc = run();
     if (d_xc) (void)hipFree(d_xc);
     if (d_env) (void)hipFree(d_env);
+    return rc;
+}
+
+// k_band_means on an injected spectrum X[N] and n injected windows, one launch
+extern "C" int mfb_debug_band_means(int device, const float *X_c64, int N, int n, const int32_t *pieces, float *means) {
+    if (!X_c64 || !pieces || !means || N < 1 || n < 1) return MFB_ERR_ARG;
+    if (n > 65535 || N > SNR_MAX_CHUNKS * SNR_CHUNK) return MFB_ERR_UNSUPPORTED;      // (the largest block: 2^22)
+    for (int i = 0; i < n; ++i) {
+        const int32_t *q = pieces + 4 * (size_t)i;
+        if (q[0] < 0 || q[1] < 0 || q[2] < 0 || q[3] < 0 || (long long)q[0] + q[1] > N || (long long)q[2] + q[3] > N ||
+            (long long)q[1] + q[3] > N)
+            return MFB_ERR_ARG;
+    }
+    int rc = debug_device_ok(device);
+    if (rc) return rc;
+    cf *d_X = nullptr;
+    int *d_p = nullptr;
+    float *d_m = nullptr;
+    auto run = [&]() -> int {
+        HIPCHK(hipMalloc((void **)&d_X, (size_t)N * sizeof(cf)));
+        HIPCHK(hipMalloc((void **)&d_p, (size_t)n * 4 * sizeof(int)));
+        HIPCHK(hipMalloc((void **)&d_m, (size_t)n * sizeof(float)));
+        HIPCHK(hipMemcpy(d_X, X_c64, (size_t)N * sizeof(cf), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_p, pieces, (size_t)n * 4 * sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(d_m, 0x5a, (size_t)n * sizeof(float)));
+        hipLaunchKernelGGL(k_band_means, dim3(1, n), dim3(SNR_THREADS), 0, nullptr, (const float2 *)d_X, (size_t)0, N, (const int *)d_p,
+                           4 * sizeof(int), d_m, sizeof(float));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpy(means, d_m, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+        return MFB_OK;
+    };
+    rc = run();
+    if (d_X) (void)hipFree(d_X);
+    if (d_p) (void)hipFree(d_p);
+    if (d_m) (void)hipFree(d_m);
     return rc;
 }
 

@@ -189,6 +189,9 @@ class Demodulator:
         # integer IQ samples in the page-locked inputs, converted on the device: "HIP": {"sample_format": ..., "sample_scale": ...}
         self.sample_format = confGPU.get('HIP', {}).get('sample_format', 'cf32')
         _, self.sample_dtype, self.sample_scale = sample_format_config(confGPU.get('HIP', {}), self.backend, shard)
+        if confGPU.get('HIP', {}).get('device_snr', False) and shard is not None:
+            raise ValueError('"device_snr" is not supported together with sharding (a sharded pick is made behind the exchange; its SNR '
+                             'stays on the host)')
 
         # filters and LUTs from the protocol plugin
         try:
@@ -249,7 +252,17 @@ class Demodulator:
         #   "HIP": {"one_call": false}
         self._one_call = bool(hip_cfg.get('one_call', True)) and shard is None and hasattr(self.bank, 'receive_block')
         self._pending = None
-        if self._one_call:
+        # computeSNR's two means of every searched block on the device (mfb_set_device_snr; the reference takes them on the host,
+        # DB:651-661), so that a block has an SNR whatever the length of its windows -- in a batch too:
+        #   "HIP": {"device_snr": true}
+        self._device_snr = bool(hip_cfg.get('device_snr', False))
+        if self._device_snr:
+            if not self._one_call:
+                raise ValueError('"device_snr" needs the one-call block path ("one_call": false switches it off)')
+            self.bank.set_device_snr(True)
+            self.bank.BAND_CAPACITY = 1          # the two means travel in one complex64 element; no spectrum sample does
+            log.info('[%s]: the SNR windows\' means are computed on the device for every block', radioName)
+        elif self._one_call:
             # room for the two spectrum windows computeSNR reads (DB:635-667), whichever neighbouring pair of bins the pick
             # falls between: the block call then always delivers them, and nothing ever has to be fetched from a spectrum
             # that a later block may already have replaced
@@ -520,7 +533,7 @@ class Demodulator:
         before its slot is begun again."""
         R = self.bank.end_blocks_record(slot) if record is None else record
         s, nb = R.s, R.nb
-        snr = self._batch_snr(R)
+        snr = self._snr_from_means(R.snr_means[:, 0], R.snr_means[:, 1]) if R.snr_means is not None else self._batch_snr(R)
         stages = R.stages and getattr(self, '_stages', False)
         nrzs = self._bitLUT_u8 is None
         out = []
@@ -633,6 +646,13 @@ class Demodulator:
             noise = np.abs(R.bands[:, 1, :l1]).mean(axis=1) if l1 else np.full(R.nb, np.nan, np.float32)
             return list(20 * np.log10(sig / noise - 1))
 
+    @staticmethod
+    def _snr_from_means(sig, noise):
+        """computeSNR's last line (DB:662-667) on the two float32 means the device delivered (mfb_set_device_snr): the same float32
+        operations under the same errstate; scalars or one value per block."""
+        with np.errstate(divide='ignore', invalid='ignore'):
+            return 20 * np.log10(sig / noise - 1)
+
     def _estimate_from_block(self, blk):
         """The host half of __findUHF (reference DB:604-632) on what mfb_receive_block returned: Hz interpolation, SNR,
         the tuple the caller gets.  The shift interpolation itself ran on the device, same float64 operations."""
@@ -646,7 +666,10 @@ class Demodulator:
         lowVal, highVal = self.doppHzLUT[lowIdx], self.doppHzLUT[highIdx]
         bestDopplerScaled = lowVal + (highVal - lowVal) * frac
         self.dopplerIdxlast = np.int32(blk['shift'])
-        SNR = self.computeSNR(lowIdx, highIdx, 5, bands=blk['bands'])
+        if 'snr_means' in blk:
+            SNR = self._snr_from_means(*blk['snr_means'])
+        else:
+            SNR = self.computeSNR(lowIdx, highIdx, 5, bands=blk['bands'])
         freqOffset = bestDopplerScaled - self.centreFreqOffset
         sdev_Hz = float(best[1]) / self.Nfft * self.sampleRate
         return freqOffset, sdev_Hz, self.clippedPeakIPure, SNR

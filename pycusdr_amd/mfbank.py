@@ -79,6 +79,22 @@ def debug_code_rate(P, offset, length, spsym_min=0, capacity=0, device=0):
                 offsetF=largs[:, 1].copy(), count=counts[:, 0].copy(), rate_fallback=counts[:, 1].copy())
 
 
+def debug_band_means(X, pieces, device=0):
+    """Test seam (mfb_debug_band_means): k_band_means on the spectrum ``X`` complex64 [N] and the windows ``pieces`` int32 [n][2][2]
+    = [piece][start, length] (a window is piece 0 then piece 1), in one launch.  float32 [n]: ``np.mean(np.abs(window))`` of each,
+    NaN for an empty one."""
+    lib = _lib.load()
+    X = np.ascontiguousarray(X)
+    if X.dtype != np.complex64 or X.ndim != 1:
+        raise TypeError(f'X is complex64 [N], got {X.dtype} {X.shape}')
+    pieces = np.ascontiguousarray(pieces, dtype=np.int32)
+    if pieces.ndim != 3 or pieces.shape[1:] != (2, 2):
+        raise ValueError(f'pieces is int32 [n][2][2], got {pieces.shape}')
+    means = np.empty(len(pieces), np.float32)
+    _lib.check(lib.mfb_debug_band_means(int(device), _ptr(X), X.size, len(pieces), _ptr(pieces), _ptr(means)), 'mfb_debug_band_means')
+    return means
+
+
 DEBUG_CANARY = 0x5a5a5a5a          # what mfb_debug_centres fills its outputs with before the launch
 
 
@@ -196,6 +212,7 @@ class BatchRecord:
             return a[:, off:off + count * np.dtype(dt).itemsize].view(dt)
         self.sym, self.cen, self.mag = arr(lay.off_sym, n, np.int32), arr(lay.off_cen, n, np.int32), arr(lay.off_mag, n, np.float32)
         self.bands = arr(lay.off_bands, 2 * lay.band_capacity, np.complex64).reshape(nb, 2, lay.band_capacity) if lay.band_capacity else None
+        self.snr_means = None      # MFBank.set_device_snr: float32 [nb][2] = (mean |X| of the signal window, of the noise window)
         self.stages = bool(lay.stream_stages)
         if self.stages:
             self.bits, self.cen8, self.trust = (arr(lay.off_bits, n, np.uint8), arr(lay.off_centres_u8, n, np.uint8),
@@ -220,7 +237,9 @@ class BatchRecord:
         if self.clipped is not None:
             d['clipped'] = self.clipped[b]
         l0, l1 = s['band_len'][b]
-        if self.searched and self.bands is not None and l0 <= self.bcap and l1 <= self.bcap:
+        if self.snr_means is not None:
+            d['snr_means'], d['band_len'] = (self.snr_means[b, 0], self.snr_means[b, 1]), (l0, l1)
+        elif self.searched and self.bands is not None and l0 <= self.bcap and l1 <= self.bcap:
             d['bands'] = (self.bands[b, 0, :l0], self.bands[b, 1, :l1])
         return d
 
@@ -491,7 +510,11 @@ class MFBank:
                'cr': (np.float32(R.cr[0]), np.float32(R.cr[1]), np.float32(R.cr[2])), 'spSym': float(R.spSym),
                'codeOffset': float(R.codeOffset), 'rate_fallback': bool(R.rate_fallback),
                'symbols': sym[:n].copy(), 'centres': cen[:n].copy(), 'magnitudes': mag[:n].copy(), 'bands': None}
-        if searched and R.band_len[0] <= self.BAND_CAPACITY and R.band_len[1] <= self.BAND_CAPACITY:
+        if searched and getattr(self, '_device_snr', False) and bands.shape[1] > 0:
+            # (mean_signal, mean_noise) sit where the signal window would begin; no spectrum sample came along
+            m = bands[0, :1].view(np.float32)
+            out['snr_means'], out['band_len'] = (np.float32(m[0]), np.float32(m[1])), (int(R.band_len[0]), int(R.band_len[1]))
+        elif searched and R.band_len[0] <= self.BAND_CAPACITY and R.band_len[1] <= self.BAND_CAPACITY:
             out['bands'] = (bands[0, :R.band_len[0]].copy(), bands[1, :R.band_len[1]].copy())
         return out
 
@@ -551,6 +574,21 @@ class MFBank:
             _lib.check(self._lib.mfb_get_block_clips(self._h, int(slot), int(block), _ptr(buf), buf.size, C.byref(n)),
                        'mfb_get_block_clips')
         return buf[:n.value].astype(np.int64)
+
+    # -- computeSNR's two means on the device (reference DB:635-667) --------------------------------
+    def set_device_snr(self, on=True):
+        """Let the device take ``np.mean(np.abs(...))`` of the two spectrum windows computeSNR reads, for every searched block of every
+        call path (mfb_set_device_snr): block results then carry 'snr_means' = (signal, noise) as float32 and 'band_len' instead of
+        'bands', whatever the windows' lengths, and ``BAND_CAPACITY`` may be 1.  Nothing may be in flight.  Off by default."""
+        _lib.check(self._lib.mfb_set_device_snr(self._h, 1 if on else 0), 'mfb_set_device_snr')
+        self._device_snr = bool(on)
+
+    def block_snr(self, slot, block=0):
+        """((mean_signal, mean_noise) float32, (signal window length, noise window length)) of block ``block`` of the flight collected
+        last from ``slot`` (mfb_get_block_snr); RuntimeError if that flight ran without ``set_device_snr``."""
+        means, lens = np.empty(2, np.float32), np.empty(2, np.int32)
+        _lib.check(self._lib.mfb_get_block_snr(self._h, int(slot), int(block), _ptr(means), _ptr(lens)), 'mfb_get_block_snr')
+        return (means[0], means[1]), (int(lens[0]), int(lens[1]))
 
     def debug_block_scalars(self, picks, triples, spsym_min, snr_window=5, max_symbols=None):
         """Test seam (mfb_debug_block_scalars): the one-call path's two float64 device stages on injected picks
@@ -643,6 +681,8 @@ class MFBank:
         self._clipped[int(slot)] = getattr(self, '_clip', False)
         self._searched = getattr(self, '_searched', {})
         self._searched[int(slot)] = fixed_shift is None
+        self._dsnr = getattr(self, '_dsnr', {})
+        self._dsnr[int(slot)] = getattr(self, '_device_snr', False) and fixed_shift is None and self.BAND_CAPACITY > 0
         self._batch = getattr(self, '_batch', {})
         self._batch[int(slot)] = (int(nblocks), int(k_offset) + int(k_len) + 1)
         self._flying = getattr(self, '_flying', set()) | {int(slot)}
@@ -676,6 +716,8 @@ class MFBank:
             self._flying = getattr(self, '_flying', set()) - {slot}
         _lib.check(rc, 'mfb_receive_blocks_end_record')
         R = BatchRecord(buf, lay, self._searched.get(slot, True))
+        if getattr(self, '_dsnr', {}).get(slot, False) and R.bands is not None:
+            R.snr_means = R.bands[:, 0, :1].view(np.float32)
         if getattr(self, '_clipped', {}).get(slot, False):
             R.clipped = BlockClips(self, slot, R.nb)       # fetched block by block where they are needed
         return R

@@ -3,8 +3,10 @@ collected one batch behind, no host stages, no decoder -- what mfb_receive_block
 bound (the receive loop in Python is: ~20 us of host work per block).  The A/B of the batch's two streams
 (MFB_BATCH_SPLIT=0/1, profiles/r06_chain.md).
 usage: python3 tools/batch_device_rate.py [log2N] [bins] [B] [batches] [stages 0|1] [overlap 0|1] [--sample-format cf32|sc16|sc8] [--reps R]
+       [--device-snr 0|1]
 --sample-format: the windows hold the radio's integers (mfb_set_sample_format; the stream quantised with one step = 2^-11 / 2^-5),
-converted on the device behind the copy; --reps: timed repeats (default 3), the median is printed last."""
+converted on the device behind the copy; --reps: timed repeats (default 3), the median is printed last; --device-snr 1: the SNR
+windows' means on the device ("HIP": {"device_snr": true}; profiles/device_snr.md)."""
 import sys
 import time
 import numpy as np
@@ -22,6 +24,7 @@ def _option(name, default):
 
 fmt = _option('--sample-format', 'cf32')
 reps = int(_option('--reps', 3))
+device_snr = bool(int(_option('--device-snr', 0)))
 from pycusdr_amd.hostcpu import quiet_blas  # noqa: E402
 quiet_blas()
 from pycusdr_amd import config as cfg, signals as sg  # noqa: E402
@@ -41,6 +44,8 @@ conf = cfg.bench_config('bench_GMSK', blockSize=log2N, doppCarrierSteps=D)
 bits = {'cf32': None, 'sc16': 11, 'sc8': 5}[fmt]
 if bits is not None:
     conf['GPU']['UHF'].setdefault('HIP', {}).update(sample_format=fmt, sample_scale=2.0 ** -bits)
+if device_snr:
+    conf['GPU']['UHF'].setdefault('HIP', {})['device_snr'] = True
 p = loadProtocol('bench_GMSK')(conf=conf)
 run = DemodulatorRunner(conf, p, 'UHF-H')
 dec = Decoder(conf, p)
@@ -74,5 +79,5 @@ for rep in range(reps):
     rates.append(B * step / dt / 1e6)
     print(f'N=2^{log2N} D={D} B={B} stages={int(stages)} overlap={int(overlap)} {fmt}: {dt * 1e6:8.1f} us per batch, {dt / B * 1e6:6.2f} us per block, '
           f'{rates[-1]:8.1f} Msamples/s', flush=True)
-print(f'N=2^{log2N} D={D} B={B} stages={int(stages)} overlap={int(overlap)} {fmt}: median of {reps}: {float(np.median(rates)):8.1f} Msamples/s', flush=True)
+print(f'N=2^{log2N} D={D} B={B} stages={int(stages)} overlap={int(overlap)} {fmt} device_snr={int(device_snr)}: median of {reps}: {float(np.median(rates)):8.1f} Msamples/s', flush=True)
 run.close()
