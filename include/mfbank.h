@@ -56,7 +56,7 @@ int mfb_abi_version(void);   /* 2: search paths, mfb_xcorr; 3: mfb_set_search_mo
                               * reports the size it needs.  Calls added without a change to an existing prototype do not bump it: a caller
                               * finds them by symbol (dlsym) -- mfb_set_sample_format, mfb_get_sample_format, mfb_input_buffer_raw,
                               * mfb_window_buffer_raw, mfb_debug_unpack, mfb_debug_envelope, mfb_debug_code_rate, mfb_debug_centres, mfb_set_device_snr,
-                              * mfb_get_block_snr, mfb_debug_band_means (sizeof and offsets of mfb_block_result, mfb_record_layout and
+                              * mfb_get_block_snr, mfb_debug_band_means, mfb_debug_search_plan (sizeof and offsets of mfb_block_result, mfb_record_layout and
                               * BlockScalars unchanged: still 9) */
 
 /* Create a handle on HIP device `device` for blocks of N = 2^log2N samples, `num_dopplers`
@@ -303,6 +303,39 @@ int mfb_set_cu_share(mfb_ctx *ctx, int part, int parts);
  * is mixed in time and transformed.  Either way the table is the reference's |IFFT(X[(k + s) mod N] H_m[k])|^2 sums (CU:339-373,
  * 421-480) to fp32 rounding.  MFB_SEG_FSM=0 in the environment keeps the time-side form. */
 int mfb_get_search_info(mfb_ctx *ctx, int *filter_side, int *bins_per_forward);
+/* What mfb_debug_search_plan (below) is asked and answers: plain ints; a field that does not apply is 0. */
+typedef struct mfb_plan_inputs {
+    int32_t N, Dtot, M, MU;        /* block length, bins (num_dopplers + doppler_offset), filters, sign-unique filters */
+    int32_t MB;                    /* rank of the span basis, 0 = none built */
+    int32_t sum_all, uniform_mult; /* SUM_ALL_MASKS; every unique filter stands for equally many of the M */
+    int32_t T;                     /* taps of the bank */
+    int32_t basis_req, path_req, segl_req, seg_wpc, seg_mpb;   /* mfb_set_search_basis, mfb_set_search_path */
+    int32_t num_cus;
+    int32_t shifts_known;          /* a shift table of Dtot entries has been set */
+    int32_t fsm, wrap_mfma;        /* MFB_SEG_FSM, MFB_SEG_WRAP_MFMA of the environment (1 = on) */
+    int32_t rect_fb, rect_fs;      /* MFB_SEG_FSM_RECT (0 = automatic) */
+    int32_t group;                 /* MFB_SEG_FSM_GROUP (-1 = automatic) */
+} mfb_plan_inputs;
+typedef struct mfb_seg_plan {      /* geometry of one k_seg launch */
+    int32_t nsg, wpg, bsplit, ssplit, mpb, mgroups, igroups, grid, lds_bytes;
+} mfb_seg_plan;
+typedef struct mfb_search_plan {
+    int32_t path, segl, V, T, Q, basis;         /* the segments: MFB_PATH_*, log2 L, valid outputs, laid-out taps, segments, MFB_BASIS_* */
+    int32_t form;                               /* main launch: 0 none, 1 k_seg, 2 k_segf<256>, 3 k_segf<2048>, 4 k_segw<13, 3> */
+    int32_t sumq, presum, wrap_kt;              /* k_segf's SUMQ variant, rows counted equally, K-steps of k_segw */
+    int32_t pv, nfull, ntotal, parts, rows;     /* valid register slots, complete slots, slots, partial sums a row, rows a bin */
+    mfb_seg_plan main_seg;                      /* form 1 */
+    int32_t nsg, gbins, fb, fs, nbc, nsc, grid, lds_bytes;   /* forms 2 ... 4 */
+    mfb_seg_plan tail;                          /* the masked launch over the incomplete slots (ntotal > nfull) */
+    mfb_seg_plan store;                         /* the matched-filter pass of the same nblocks (mfb_demodulate, SEG_STORE) */
+    int32_t need_tables, need_rows, need_span, need_segl, need_wkt;   /* the per-bin tables forms 2 ... 4 read */
+} mfb_search_plan;
+/* The whole plan of the next segment search of `nblocks` blocks, as the launches take it (no reference counterpart: a test seam, like
+ * mfb_debug_block_scalars; csrc/search_plan.hpp).  With a handle, *inputs is FILLED from it -- what the planner is asked -- and
+ * planned with the segments the handle has resolved; with ctx = NULL the given inputs are planned, segments included: host only, no
+ * device and no HIP call (like mfb_analyze_rank).  MFB_ERR_UNSUPPORTED where mfb_set_search_path would refuse the inputs,
+ * MFB_ERR_STATE for a handle without filters. */
+int mfb_debug_search_plan(mfb_ctx *ctx_or_null, mfb_plan_inputs *inputs, int nblocks, mfb_search_plan *out);
 /* The doppSum table (num_dopplers + doppler_offset rows of M floats, as mfb_get_scores: GPU_bufDoppSum, DB:594-601) of block
  * `block` of the batch begun LAST, once that batch has been collected and before the next one is begun.  MFB_ERR_STATE otherwise
  * (no batch, a fixed-shift batch, block beyond it). */

@@ -83,6 +83,26 @@ class CombineResult(C.Structure):
                 ('matched_slaves', C.c_int32 * 3), ('reserved', C.c_int32), ('slave', CombineSlave * 3)]
 
 
+class PlanInputs(C.Structure):
+    """mfb_plan_inputs of include/mfbank.h."""
+    _fields_ = [(k, C.c_int32) for k in ('N', 'Dtot', 'M', 'MU', 'MB', 'sum_all', 'uniform_mult', 'T', 'basis_req', 'path_req', 'segl_req',
+                                         'seg_wpc', 'seg_mpb', 'num_cus', 'shifts_known', 'fsm', 'wrap_mfma', 'rect_fb', 'rect_fs', 'group')]
+
+
+class SegPlan(C.Structure):
+    """mfb_seg_plan of include/mfbank.h."""
+    _fields_ = [(k, C.c_int32) for k in ('nsg', 'wpg', 'bsplit', 'ssplit', 'mpb', 'mgroups', 'igroups', 'grid', 'lds_bytes')]
+
+
+class SearchPlan(C.Structure):
+    """mfb_search_plan of include/mfbank.h."""
+    _fields_ = [(k, C.c_int32) for k in ('path', 'segl', 'V', 'T', 'Q', 'basis', 'form', 'sumq', 'presum', 'wrap_kt', 'pv', 'nfull',
+                                         'ntotal', 'parts', 'rows')] + [('main_seg', SegPlan)] + \
+               [(k, C.c_int32) for k in ('nsg', 'gbins', 'fb', 'fs', 'nbc', 'nsc', 'grid', 'lds_bytes')] + \
+               [('tail', SegPlan), ('store', SegPlan)] + \
+               [(k, C.c_int32) for k in ('need_tables', 'need_rows', 'need_span', 'need_segl', 'need_wkt')]
+
+
 # name -> (restype, argtypes); exactly the prototypes of include/mfbank.h
 PROTOTYPES = {
     'mfb_strerror': (C.c_char_p, [_i]),
@@ -128,6 +148,7 @@ PROTOTYPES = {
     'mfb_set_device_snr': (_i, [_vp, _i]),
     'mfb_get_block_snr': (_i, [_vp, _i, _i, _vp, _vp]),
     'mfb_get_search_info': (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
+    'mfb_debug_search_plan': (_i, [_vp, C.POINTER(PlanInputs), _i, C.POINTER(SearchPlan)]),
     'mfb_set_cu_share': (_i, [_vp, _i, _i]),
     'mfb_receive_blocks_end': (_i, [_vp, _i, C.POINTER(BlockResult), _vp, _vp, _vp, _i, _vp]),
     'mfb_receive_blocks_end_record': (_i, [_vp, _i, _vp, C.c_size_t, C.POINTER(RecordLayout)]),

@@ -49,6 +49,7 @@
 #include "filter_taps.hpp"
 #include "seg_kernels.hpp"
 #include "wrap_kernels.hpp"
+#include "search_plan.hpp"
 #include "twopass_kernels.hpp"
 #include "small_kernels.hpp"
 #include "sync_kernels.hpp"
@@ -208,7 +209,6 @@ struct mfb_ctx {
     u32x4 *d_Wb = nullptr;               // [Dtot][KT][2][64]: B fragments of the wrap-around outputs (wrap_kernels.hpp), built with d_Gs
     int *d_Wexp = nullptr;               // [Dtot]: their powers of two
     int wb_kt = 0;                       // K-steps d_Wb was built for (0: not built)
-    int fsm_fb = 0, fsm_fs = 0;          // rectangle of a wave: bins x slots (0: default)
     // interference-peak clipping before the forward transform (clip_kernels.hpp, mfb_set_peak_clip; DB:670-707)
     float clip_scale = 0.f;              // 0: off
     int clip_ov = 0;                     // > 0: block b's first clip_ov samples are block b - 1's clipped tail
@@ -445,30 +445,51 @@ static int attr_p2() {
     }
     return MFB_OK;
 }
-template <int L>
-static int attr_seg() {
-    const int b = (int)SegCfg<L>::lds_bytes(L == 8192 ? 8 : SEG_MPB_MAX);     // (8192 points: 157 KiB with 8 filters per pass is all a CU has)
-    HIPCHK(hipFuncSetAttribute((const void *)k_seg<L, SEG_STORE, -1>, hipFuncAttributeMaxDynamicSharedMemorySize, b));
-#define MFB_ATTR_PV(PV_) HIPCHK(hipFuncSetAttribute((const void *)k_seg<L, SEG_REDUCE, PV_>, hipFuncAttributeMaxDynamicSharedMemorySize, b))
-    MFB_ATTR_PV(-1);
-    if constexpr (seg_ppl(L) == 32) {
-        MFB_ATTR_PV(16); MFB_ATTR_PV(17); MFB_ATTR_PV(18); MFB_ATTR_PV(19); MFB_ATTR_PV(20); MFB_ATTR_PV(21); MFB_ATTR_PV(22);
-        MFB_ATTR_PV(23); MFB_ATTR_PV(24); MFB_ATTR_PV(25); MFB_ATTR_PV(26); MFB_ATTR_PV(27); MFB_ATTR_PV(28); MFB_ATTR_PV(29);
-        MFB_ATTR_PV(30); MFB_ATTR_PV(31); MFB_ATTR_PV(32);
-    } else {
-        MFB_ATTR_PV(8);
-        MFB_ATTR_PV(9);
-        MFB_ATTR_PV(10);
-        MFB_ATTR_PV(11);
-        MFB_ATTR_PV(12);
-        MFB_ATTR_PV(13);
-        MFB_ATTR_PV(14);
-        MFB_ATTR_PV(15);
-        MFB_ATTR_PV(16);
-    }
-#undef MFB_ATTR_PV
-    return MFB_OK;
+// ---- the search's kernel instantiations, enumerated ONCE per family ----------------------------------------------------------------
+// visit_*(f) calls f(tag) for every instantiation of the family until a call returns something other than VISIT_NEXT, and returns
+// that.  Setting the attributes visits all of a family; a launch visits until (segment length, mode or variant, pv) matches.  The
+// ranges are seg_ppl, segf_has_sumq and segf_has_presum themselves, and nothing else is instantiated: no launch reaches a kernel whose
+// attribute was never set.  PV: valid register slots of a complete segment (half ... all) for the branch-free form, -1 = masked.
+constexpr int VISIT_NEXT = -1;
+template <int SEGL_, int MODE_, int PV_>
+struct SegInst {       // k_seg<L, MODE, PV> | k_segf<L, PV, SUMQ = MODE>
+    static constexpr int SEGL = SEGL_, L = 1 << SEGL_, MODE = MODE_, PV = PV_;
+};
+template <int SEGL, class F, int... I>
+static int visit_seg_l(F &f, std::integer_sequence<int, I...>) {
+    int rc = f(SegInst<SEGL, SEG_STORE, -1>{});
+    if (rc == VISIT_NEXT) rc = f(SegInst<SEGL, SEG_REDUCE, -1>{});
+    (void)((rc == VISIT_NEXT && (rc = f(SegInst<SEGL, SEG_REDUCE, seg_ppl(1 << SEGL) / 2 + I>{})) == VISIT_NEXT) && ...);
+    return rc;
 }
+using SegLens = std::integer_sequence<int, 8, 9, 10, 11, 12, SEG_LOG2L_MAX>;
+template <class F, int... SEGL>
+static int visit_seg(F f, std::integer_sequence<int, SEGL...>) {
+    int rc = VISIT_NEXT;
+    (void)(((rc = visit_seg_l<SEGL>(f, SegSlots<(1 << SEGL)>{})) == VISIT_NEXT) && ...);
+    return rc;
+}
+template <int SEGL, class F, int... I>
+static int visit_segf_l(F &f, std::integer_sequence<int, I...>) {
+    int rc = VISIT_NEXT;
+    auto variants = [&](auto pv) {
+        constexpr int L = 1 << SEGL, PV = decltype(pv)::value;
+        rc = f(SegInst<SEGL, 0, PV>{});
+        if constexpr (segf_has_sumq<L, PV>())
+            if (rc == VISIT_NEXT) rc = f(SegInst<SEGL, 1, PV>{});
+        if constexpr (segf_has_presum<L, PV>())
+            if (rc == VISIT_NEXT) rc = f(SegInst<SEGL, 2, PV>{});
+        return rc == VISIT_NEXT;
+    };
+    (void)(variants(std::integral_constant<int, seg_ppl(1 << SEGL) / 2 + I>{}) && ...);
+    return rc;
+}
+template <class F>
+static int visit_segf(F f) {
+    const int rc = visit_segf_l<8>(f, SegSlots<256>{});
+    return rc != VISIT_NEXT ? rc : visit_segf_l<11>(f, SegSlots<2048>{});
+}
+#define MFB_MAX_LDS(K_, B_) HIPCHK(hipFuncSetAttribute((const void *)K_, hipFuncAttributeMaxDynamicSharedMemorySize, B_))
 static int set_kernel_attributes(const mfb_ctx *c) {
     int rc = MFB_OK;
     switch (c->l1) {
@@ -484,37 +505,22 @@ static int set_kernel_attributes(const mfb_ctx *c) {
         default: break;   // <= 4096 points: 35 KiB
     }
     if (rc) return rc;
-    if ((rc = attr_seg<256>())) return rc;
-    {
-        const int b = (int)(SegCfg<256>::LDS_ELEMS * sizeof(cf) + (size_t)(SegCfg<256>::BLOCK / 64) * SEG_MPB_MAX * SEG_ACC_STRIDE * sizeof(float));
-#define MFB_ATTR_F(PV_) HIPCHK(hipFuncSetAttribute((const void *)k_segf<256, PV_>, hipFuncAttributeMaxDynamicSharedMemorySize, b))
-        MFB_ATTR_F(8); MFB_ATTR_F(9); MFB_ATTR_F(10); MFB_ATTR_F(11); MFB_ATTR_F(12); MFB_ATTR_F(13); MFB_ATTR_F(14); MFB_ATTR_F(15); MFB_ATTR_F(16);
-#undef MFB_ATTR_F
-#define MFB_ATTR_Q(L_, PV_, B_)                                                                                                       \
-    if constexpr (segf_has_sumq<L_, PV_>())                                                                                           \
-        HIPCHK(hipFuncSetAttribute((const void *)k_segf<L_, PV_, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, B_));                    \
-    if constexpr (segf_has_presum<L_, PV_>())                                                                                         \
-        HIPCHK(hipFuncSetAttribute((const void *)k_segf<L_, PV_, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, B_))
-        MFB_ATTR_Q(256, 11, b); MFB_ATTR_Q(256, 12, b); MFB_ATTR_Q(256, 13, b); MFB_ATTR_Q(256, 14, b); MFB_ATTR_Q(256, 15, b);
-        {
-            const int bw = (int)SegWCfg<13, 3>::lds_bytes();
-            HIPCHK(hipFuncSetAttribute((const void *)k_segw<13, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, bw));
-        }
-        const int b2 = (int)(SegCfg<2048>::LDS_ELEMS * sizeof(cf) + (size_t)(SegCfg<2048>::BLOCK / 64) * 8 * SEG_ACC_STRIDE * sizeof(float));
-#define MFB_ATTR_F(PV_) HIPCHK(hipFuncSetAttribute((const void *)k_segf<2048, PV_>, hipFuncAttributeMaxDynamicSharedMemorySize, b2))
-        MFB_ATTR_F(16); MFB_ATTR_F(17); MFB_ATTR_F(18); MFB_ATTR_F(19); MFB_ATTR_F(20); MFB_ATTR_F(21); MFB_ATTR_F(22); MFB_ATTR_F(23); MFB_ATTR_F(24);
-        MFB_ATTR_F(25); MFB_ATTR_F(26); MFB_ATTR_F(27); MFB_ATTR_F(28); MFB_ATTR_F(29); MFB_ATTR_F(30); MFB_ATTR_F(31); MFB_ATTR_F(32);
-#undef MFB_ATTR_F
-        MFB_ATTR_Q(2048, 22, b2); MFB_ATTR_Q(2048, 23, b2); MFB_ATTR_Q(2048, 24, b2); MFB_ATTR_Q(2048, 25, b2); MFB_ATTR_Q(2048, 26, b2);
-        MFB_ATTR_Q(2048, 27, b2); MFB_ATTR_Q(2048, 28, b2); MFB_ATTR_Q(2048, 29, b2); MFB_ATTR_Q(2048, 30, b2); MFB_ATTR_Q(2048, 31, b2);
-#undef MFB_ATTR_Q
-    }
-    if ((rc = attr_seg<512>())) return rc;
-    if ((rc = attr_seg<1024>())) return rc;
-    if ((rc = attr_seg<2048>())) return rc;
-    if ((rc = attr_seg<4096>())) return rc;
-    return attr_seg<8192>();
+    rc = visit_seg([](auto k) -> int {
+        using K = decltype(k);
+        MFB_MAX_LDS((k_seg<K::L, K::MODE, K::PV>), seg_lds_bytes(K::SEGL, SEG_REDUCE, seg_mpb_cap(K::SEGL)));
+        return VISIT_NEXT;
+    }, SegLens{});
+    if (rc == VISIT_NEXT)
+        rc = visit_segf([](auto k) -> int {
+            using K = decltype(k);
+            MFB_MAX_LDS((k_segf<K::L, K::PV, K::MODE>), segf_lds_bytes<K::L>(segf_rows_cap(K::L)));
+            return VISIT_NEXT;
+        });
+    if (rc != VISIT_NEXT) return rc;
+    MFB_MAX_LDS((k_segw<SEGW_PV, SEGW_KT>), segw_lds_bytes());
+    return MFB_OK;
 }
+#undef MFB_MAX_LDS
 
 static int create_impl(mfb_ctx *c) {
     HIPCHK(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
@@ -809,80 +815,28 @@ extern "C" int mfb_get_info(mfb_ctx *c, int *N1, int *N2, int *unique_filters) {
 }
 
 // ---- search path ---------------------------------------------------------------------------------
-// Valid outputs per complete segment: the largest multiple of NT = L / (points per lane) not above L - T + 1, so that
-// they are whole register slots (seg_kernels.hpp); 0 if fewer than half of a segment would be valid.
-#define SEG_LOG2L_MAX 13      // 8192-point segments: filters of up to 4097 taps
-#define SEG_TWOPASS_COST 6.45  // the two-pass path in the units of seg_cost (ms per block at C2's geometry)
-static int seg_valid(int l, int T) {
-    const int L = 1 << l, ppl = seg_ppl(L), NT = L / ppl;
-    const int pv = (L - T + 1) / NT;
-    return pv >= ppl / 2 ? pv * NT : 0;
+// What the planner (search_plan.hpp) is asked for this handle: the only bridge between the two.
+static SearchInputs search_inputs(const mfb_ctx *c) {
+    SearchInputs in = search_env();       // (the switches)
+    in.N = c->N, in.Dtot = c->Dtot, in.M = c->M, in.MU = c->MU, in.MB = c->MB;
+    in.sum_all = c->sum_all;
+    in.uniform_mult = std::all_of(c->h_mult.begin(), c->h_mult.end(), [&](int m) { return m == c->h_mult[0]; });
+    in.T = c->bank ? c->bank->T : 0;
+    in.basis_req = c->basis_req, in.path_req = c->path_req, in.segl_req = c->segl_req, in.seg_wpc = c->seg_wpc, in.seg_mpb = c->seg_mpb;
+    in.num_cus = c->num_cus;
+    in.shifts_known = (int)c->h_shifts.size() == c->Dtot;
+    return in;
 }
-// Relative cost of one segment point per filter, MEASURED on MI355X at C2 (time x V / L, 48 taps, D = 256,
-// M = 8; tools/seg_probe.py): the 256-point kernel is by far the cheapest per point (one twiddled pass,
-// three waves per SIMD, phase table in LDS), so it wins whenever at least ~2/3 of a segment is valid; the
-// cost of a valid output is this divided by the segment efficiency V / L.  Re-measured late in round 3 at the settled
-// clock and with a quiet host (profiles/r03_ramp.md: the first ~30 ms after an idle spell run 8-20 % slow, and a probe whose
-// own BLAS threads get the process throttled starves the device the same way -- some earlier tables carried both effects):
-// GMSK bank, 256 ... 4096 points: 1.597 / 2.128 / 2.070 / 2.443 / 2.648 ms; CC11xx bank (384 taps) on five devices:
-// 2048 points 2.69-2.77 ms, 4096 points 2.90-2.96 ms (the 2048-point kernel gained 5 % from one team per workgroup);
-// BPSK bank (80 taps), 256 / 512 / 1024 points: 3.74 / 4.28 / 4.15 ms.  Figures with 32 workgroups per CU in the grid.
-// Round 4: the 2048-point kernel became one wave per segment with one LDS exchange per transform (seg_kernels.hpp, W32):
-// 2.51 against 2.72 ms on one device for the 384-tap bank (profiles/r04_long_filter.md), hence 2.20 -> 2.03.  8192 points (one
-// eight-wave team per CU, four passes): 4.67 ms at 2049 taps, 5.05 at 2050, 5.48 at 3000, 6.61 at 4097 -> 3.45 per point; in
-// these units the two-pass path costs 6.45 whatever the filter (6.5 ms), so the longest filters of the range stay there.
-static double seg_cost(int l, int T, int MU = 8) {
-    // Round 6 (fused transforms, the shift on the filters' side for 256 and 2048 points; gpurun_out/r06_taps.txt: random banks at C2,
-    // lengths forced beside the chosen one): 256 points 1.49 ms at 64 taps, 1.74 at 96 -> 1.10; 2048 points 1.90 at 100 taps, 2.28 at 512,
-    // 2.68 at 768, 3.24 at 1025 -> 1.75 (1.62 ... 1.78: dead register slots are pruned as the valid share shrinks); 4096 points 2.98 at
-    // 768 taps, 3.53 at 1150 -> 2.43.  The 2048-point kernel now keeps 650 ... ~850 taps that went to 4096 points (2.68 against 2.98 ms
-    // at 768 taps); the hand-over from 256 points stays just under 100 taps (1.91 against 1.90 ms at 100).
-    // ... and once more with the complement second pass (gpurun_out/r06_taps2.txt), whose cost falls with the share of valid slots:
-    // 256 points 1.28 ms at 48 taps, 1.44 at 64, 1.60 at 80, 1.75 at 88 / 96 (10 valid slots: no complement) -> 1.08; 2048 points 1.45 ms
-    // at 64 taps, 1.60 at 72 ... 100, 2.45 at 640, 2.69 at 768, 3.16 at 900 -> 1.60.  The hand-over from 256 to 2048 points moves from
-    // just under 100 taps to 81 (1.75 against 1.60 ms at 88 and 96 taps; a tie at 64 ... 80), 2048 points keep everything up to 1025.
-    static const double per_point[14] = {0, 0, 0, 0, 0, 0, 0, 0, MFB_FFT_FUSED ? (MFB_SEG_COMPLEMENT ? 1.08 : 1.10) : 1.35, 1.94, 2.02,
-                                         MFB_SEG_W32 ? (MFB_FFT_FUSED ? (MFB_SEG_COMPLEMENT ? 1.60 : 1.75) : 2.03) : 2.20,
-                                         MFB_FFT_FUSED ? 2.43 : 2.55, 3.45};
-    const int V = seg_valid(l, T);
-    if (!V) return 1e30;
-    // (the 2048-point kernel takes the filter-side shift and the complement pass for up to 8 filters per bin only: with more it runs
-    // round 6's fused transforms on seg_body -- 2.32 ms on the 384-tap bank, 1.89 per point)
-    const double pp = (l == 11 && MFB_SEG_W32 && MFB_FFT_FUSED && MU > 8) ? 1.89 : per_point[l];
-    return pp * (double)(1 << l) / (double)V;
-}
-
-static int choose_segl(const mfb_ctx *c, int T, bool may_decline) {
-    int best = 0;
-    double bc = 1e30;
-    for (int l = 8; l <= SEG_LOG2L_MAX; ++l) {
-        if (!seg_valid(l, T) || (4 << l) > c->N) continue;    // at least half of every segment valid, >= 4 segments
-        const double cost = seg_cost(l, T, c->MU);
-        if (cost < bc) {
-            bc = cost;
-            best = l;
-        }
-    }
-    // barely half of an 8192-point segment valid: the two-pass path is no slower (unless the caller insists on segments)
-    if (may_decline && bc > SEG_TWOPASS_COST) return 0;
-    return best;
-}
+static Segments segments(const mfb_ctx *c) { return Segments{c->path, c->segl, c->V, c->T, c->Q, c->basis, true}; }   // (those in force)
 
 static int fsm_prepare_eager(mfb_ctx *c);
 // settle path and segment length from the request and the analysed bank; (re)build G and W_L
 static int resolve_path(mfb_ctx *c) {
     ++c->epoch;               // whatever changes here changes the launches of a block
     if (!c->have_filters || !c->bank) return MFB_OK;
-    const int T = c->bank->T;
-    int l = 0;
-    if (c->path_req != MFB_PATH_TWOPASS) {
-        if (c->segl_req) {
-            if (c->segl_req >= 8 && c->segl_req <= SEG_LOG2L_MAX && seg_valid(c->segl_req, T) && (2 << c->segl_req) <= c->N) l = c->segl_req;
-        } else {
-            l = choose_segl(c, T, c->path_req == MFB_PATH_AUTO);
-        }
-    }
-    if (c->path_req == MFB_PATH_SEGMENT && !l) return MFB_ERR_UNSUPPORTED;
+    const Segments sg = resolve_segments(search_inputs(c));
+    if (!sg.ok) return MFB_ERR_UNSUPPORTED;
+    const int l = sg.segl;
     HIPCHK(sync_streams(c));
     if (!l) {
         c->path = MFB_PATH_TWOPASS;
@@ -892,7 +846,7 @@ static int resolve_path(mfb_ctx *c) {
         const int L = 1 << l;
         if (c->segl != l || !c->d_G) {
             std::vector<float> G;
-            taps::segment_spectra(*c->bank, L, L - seg_valid(l, T) + 1, &G, seg_ppl(L));
+            taps::segment_spectra(*c->bank, L, sg.T, &G, seg_ppl(L));
             if (c->d_G) HIPCHK(hipFree(c->d_G));
             c->d_G = nullptr;
             HIPCHK(dev_alloc((void **)&c->d_G, G.size() * sizeof(float)));
@@ -909,14 +863,13 @@ static int resolve_path(mfb_ctx *c) {
                 c->twL_len = L;
             }
         }
-        // opt-in span basis of the SUM_ALL search (filter_taps.hpp): rank(C) filters instead of M
-        c->basis = MFB_BASIS_FILTERS;
+        // opt-in span basis of the SUM_ALL search: its rank is found here, and the basis settled with it
         if (c->basis_req == MFB_BASIS_SPAN && c->sum_all) {
             if (c->gb_l != l || !c->d_Gb) {
                 taps::Bank sb;
                 c->MB = taps::span_basis(*c->bank, &sb);
                 std::vector<float> G;
-                if (c->MB > 0) taps::segment_spectra(sb, L, L - seg_valid(l, T) + 1, &G, seg_ppl(L));
+                if (c->MB > 0) taps::segment_spectra(sb, L, sg.T, &G, seg_ppl(L));
                 if (c->d_Gb) HIPCHK(hipFree(c->d_Gb));
                 c->d_Gb = nullptr;
                 c->gb_l = 0;
@@ -926,14 +879,14 @@ static int resolve_path(mfb_ctx *c) {
                     c->gb_l = l;
                 }
             }
-            if (c->MB > 0) c->basis = MFB_BASIS_SPAN;
         }
         c->path = MFB_PATH_SEGMENT;
         c->segl = l;
-        c->V = seg_valid(l, T);
-        c->T = L - c->V + 1;          // taps the segments are laid out for (>= the bank's T)
+        c->V = sg.V;
+        c->T = sg.T;                  // taps the segments are laid out for (>= the bank's T)
         c->win_start = c->bank->start;
-        c->Q = (c->N + c->V - 1) / c->V;
+        c->Q = sg.Q;
+        c->basis = resolve_segments(search_inputs(c)).basis;
     }
     if (c->path == MFB_PATH_TWOPASS) {
         if (c->chunk_auto) c->chunk = default_chunk(c);
@@ -1277,123 +1230,15 @@ static int forward_fft(mfb_ctx *c, const cf *src_c, const float *src_r, cf *dst,
 
 
 // ---- single-pass overlap-save launches -------------------------------------------------------------
-template <int L, int MODE, int PV>
-static int launch_seg_k(mfb_ctx *c, const SegArgs &a, int grid) {
-    const size_t lds = SegCfg<L>::lds_bytes(MODE == SEG_REDUCE ? a.mpb : 0);
-    hipLaunchKernelGGL((k_seg<L, MODE, PV>), dim3(grid), dim3(SegCfg<L>::BLOCK), lds, c->stream, a);
-    HIPCHK(hipGetLastError());
-    return MFB_OK;
-}
-// pv: valid register slots of a complete segment (half of the points per lane ... all of them) for the branch-free
-// instantiation, -1 = masked
-template <int L, int PV0, int PV1>
-static int launch_seg_pv(mfb_ctx *c, const SegArgs &a, int grid, int pv) {
-    if constexpr (PV0 > PV1) {
-        return MFB_ERR_UNSUPPORTED;
-    } else {
-        if (pv == PV0) return launch_seg_k<L, SEG_REDUCE, PV0>(c, a, grid);
-        return launch_seg_pv<L, PV0 + 1, PV1>(c, a, grid, pv);
-    }
-}
-template <int L>
-static int launch_seg_l(mfb_ctx *c, const SegArgs &a, int grid, int mode, int pv) {
-    if (mode == SEG_STORE) return launch_seg_k<L, SEG_STORE, -1>(c, a, grid);
-    if constexpr (seg_ppl(L) == 32) {
-        if (pv == -1) return launch_seg_k<L, SEG_REDUCE, -1>(c, a, grid);
-        return launch_seg_pv<L, 16, 32>(c, a, grid, pv);
-    } else {
-        if (pv == -1) return launch_seg_k<L, SEG_REDUCE, -1>(c, a, grid);
-        return launch_seg_pv<L, 8, 16>(c, a, grid, pv);
-    }
-}
-static int launch_seg(mfb_ctx *c, const SegArgs &a, int grid, int mode, int pv) {
-    switch (c->segl) {
-        case 8: return launch_seg_l<256>(c, a, grid, mode, pv);
-        case 9: return launch_seg_l<512>(c, a, grid, mode, pv);
-        case 10: return launch_seg_l<1024>(c, a, grid, mode, pv);
-        case 11: return launch_seg_l<2048>(c, a, grid, mode, pv);
-        case 12: return launch_seg_l<4096>(c, a, grid, mode, pv);
-        case 13: return launch_seg_l<8192>(c, a, grid, mode, pv);
-    }
-    return MFB_ERR_UNSUPPORTED;
-}
-
-// Decomposition of one launch over `nslots` slots (a slot = CT neighbouring segments, one team
-// iteration): nsg segment groups (8 = one per XCD under round-robin placement), each with wpg workgroups
-// = bsplit Doppler streams x ssplit slot sub-ranges (x TPW teams).
-struct SegGeom {
-    int NT, TEAM, CT, TPW, WPT;
-    bool wave_sync;
-};
-static SegGeom seg_geom(const mfb_ctx *c) {
-    SegGeom g;
-    const int L = 1 << c->segl;
-    g.NT = L / seg_ppl(L);
-    g.TEAM = g.NT < 64 ? 64 : g.NT;
-    g.CT = g.TEAM / g.NT;
-    g.TPW = seg_block_threads(g.NT) / g.TEAM;
-    g.WPT = g.TEAM / 64;
-    g.wave_sync = g.NT <= 64;
-    return g;
-}
-struct SegPlan {
-    int nsg, wpg, bsplit, ssplit, mpb, mgroups, grid;
-    int igroups;      // > 1: the filter groups are walked inside a team (REDUCE launches of large problems), mgroups == 1
-};
-static SegPlan plan_seg(const mfb_ctx *c, int dc, int nfilters, int nslots, int mpb_want, bool inner_groups = false) {
-    const SegGeom g = seg_geom(c);
-    SegPlan p;
-    p.nsg = nslots >= 64 ? 8 : 1;
-    // L = 256 runs three workgroups per CU only while a workgroup's LDS stays under 53 KiB: 8 filters per pass
-    // (the wave-local 2048-point kernel keeps two workgroups per CU only while a workgroup's LDS stays under 80 KiB: 8 per pass)
-    // (so does the 8192-point kernel: its one team per CU has 157 KiB with 8 filters per pass)
-    int mpb = mpb_want > 0 ? mpb_want : ((c->segl <= 8 || c->segl == 13 || seg_ppl(1 << c->segl) == 32) ? 8 : SEG_MPB_MAX);
-    if (c->segl == 13 && mpb > 8) mpb = 8;
-    if (mpb > SEG_MPB_MAX) mpb = SEG_MPB_MAX;
-    if (mpb > nfilters) mpb = nfilters;
-    p.mgroups = (nfilters + mpb - 1) / mpb;
-    p.mpb = (nfilters + p.mgroups - 1) / p.mgroups;   // balanced
-    p.igroups = 1;
-    // Workgroups in the grid per CU.  More than are resident at once (3 / 2 per CU): the surplus is dealt out as workgroups
-    // retire, which evens out CUs that finish at different times.  Measured at C2, L = 256, settled clock, quiet host
-    // (tools/seg_probe.py): 8 per CU 1.615 ms, 12: 1.615, 16: 1.613, 24: 1.604, 32: 1.596, 48: 1.595 -- about 1 %.  (Round 2's
-    // table here -- 12: 1.90, 16: 1.71, 32: 1.655 "on an uneven device" -- was mostly the probe: its first variant ran in the
-    // clock ramp after the handle was built.)  Small blocks are unaffected (the grid never has more teams than (bin, slot) units).
-    const int wpc = c->seg_wpc > 0 ? c->seg_wpc : 32;
-    // workgroups per group: wpc 256-thread workgroups' worth of teams per CU, over the device's CUs
-    const int teams = wpc * c->num_cus * 256 / g.TEAM;         // teams in the whole grid
-    int wpg = teams / g.TPW / p.nsg;
-    if (wpg < 1) wpg = 1;
-    // never more teams than (bin, slot) units in a group
-    const long long units = (long long)dc * ((nslots + p.nsg - 1) / p.nsg);
-    while (wpg > 1 && (long long)wpg * g.TPW > units) wpg >>= 1;
-    // Several filter groups and plenty of (bin, slot) units: a team walks the groups itself on ONE forward transform per
-    // segment instead of a workgroup per group each repeating it (1 of 18 transforms of the BPSK bank).  REDUCE launches only.
-    if (inner_groups && c->segl <= 8 && p.mgroups > 1 && units >= 4LL * wpg * g.TPW) {      // (the 256-point kernel only: seg_kernels.hpp)
-        p.igroups = p.mgroups;
-        p.mgroups = 1;
-    }
-    p.wpg = wpg;
-    // bsplit * ssplit = wpg * TPW teams; barrier teams of one workgroup must share the Doppler stream.
-    // Of all factorisations take the one whose busiest team has the least (bins x slots) to do;
-    // ties go to more Doppler streams (fewer partial-sum columns).
-    const int tg = g.wave_sync ? wpg * g.TPW : wpg;
-    const int glen = (nslots + p.nsg - 1) / p.nsg;
-    int bs = 1;
-    long long best = -1;
-    for (int d = 1; d <= tg; ++d) {
-        if (tg % d) continue;
-        const int ss = g.wave_sync ? tg / d : (wpg / d) * g.TPW;
-        const long long work = (long long)((dc + d - 1) / d) * ((glen + ss - 1) / ss);
-        if (best < 0 || work <= best) {
-            best = work;
-            bs = d;
-        }
-    }
-    p.bsplit = bs;
-    p.ssplit = g.wave_sync ? tg / bs : (wpg / bs) * g.TPW;
-    p.grid = p.nsg * p.mgroups * p.wpg;
-    return p;
+static int launch_seg(mfb_ctx *c, const SegArgs &a, const SegPlan &p, int mode, int pv) {
+    const int rc = visit_seg([&](auto k) -> int {
+        using K = decltype(k);
+        if (K::SEGL != c->segl || K::MODE != mode || K::PV != pv) return VISIT_NEXT;
+        hipLaunchKernelGGL((k_seg<K::L, K::MODE, K::PV>), dim3(p.grid), dim3(SegCfg<K::L>::BLOCK), (size_t)p.lds_bytes, c->stream, a);
+        HIPCHK(hipGetLastError());
+        return MFB_OK;
+    }, SegLens{});
+    return rc == VISIT_NEXT ? MFB_ERR_UNSUPPORTED : rc;
 }
 
 static SegArgs seg_base(mfb_ctx *c, const SegPlan &p) {
@@ -1417,15 +1262,6 @@ static SegArgs seg_base(mfb_ctx *c, const SegPlan &p) {
     a.scale = 1.0f / 262144.0f;
     return a;
 }
-
-// slots whose segments are all complete (branch-free kernel) and the rest (masked kernel)
-static void seg_slots(const mfb_ctx *c, int *full, int *total) {
-    const SegGeom g = seg_geom(c);
-    const int qfull = c->N / c->V;                    // complete segments
-    *full = qfull / g.CT;
-    *total = (c->Q + g.CT - 1) / g.CT;
-}
-
 
 #define MIRROR_MAX_N (1 << 18)
 // d_X is about to be overwritten: the copy of the previous spectrum must have left it
@@ -1538,38 +1374,10 @@ extern "C" int mfb_upload_device(mfb_ctx *c, const void *dev) {
 }
 
 // ---- the search with the shift on the filter side (seg_kernels.hpp, segf_body) ------------------------------------------------------
-// MFB_SEG_FSM=0 in the environment keeps the search on seg_body (the A/B switch of profiles/r06_fft_ops.md); MFB_SEG_FSM_RECT="fb,fs"
-// sets the rectangle a wave takes (bins x slots).
-static bool fsm_enabled() {
-    static const int on = getenv("MFB_SEG_FSM") ? atoi(getenv("MFB_SEG_FSM")) : 1;
-    return on != 0 && MFB_FFT_FUSED;
-}
-// MFB_SEG_WRAP_MFMA=0 in the environment keeps the wrap-around energy of the 256-point search on the vector ALUs (segf_body) instead of
-// the matrix cores (wrap_kernels.hpp, k_segw): the A/B switch of profiles/r07_wrap_mfma.md
-static bool wrap_mfma_enabled() {
-    static const int on = getenv("MFB_SEG_WRAP_MFMA") ? atoi(getenv("MFB_SEG_WRAP_MFMA")) : 1;
-    return on != 0;
-}
-// K-steps of the matrix-core form of the search, 0 where it does not run: 256-point segments, SUM_ALL searches whose rows k_finalize
-// counts equally (segf_body's SUMQ = 2 form), one 16-column tile per bin (MU <= 8) and the instantiated shape -- 13 valid register
-// slots and at most three K-steps of 16 taps, which is 34 ... 48 taps (the 8-filter GMSK / FSK banks): seg_valid leaves 33 taps 14 valid
-// slots, and 49 taps, which still have 13, need a fourth K-step.  The BPSK bank (80 taps, 16 rows) keeps segf_body.
-// (tests/seg_model.py, wrap_form, restates this; tests/test_gpu_wrap_sweep.py holds the device to it at 33 | 34 and 48 | 49 taps.)
-// Blocks of 2^18 samples and more only: a single small block (2^15 ... 2^17 samples x 64 bins) gets one-bin rectangles from fsm_plan, and
-// there the forward transform and the A fragments, built per (slot, bin) at one wave per SIMD, made the search slower than segf_body
-// (bench.py --full, recv_b1_n17_d64: 607 against 763 Msamples/s).  The choice depends on the bank and the block length alone -- never on
-// the number of bins, the rectangle or the grid -- so that a (block, shift) scores the same bits from any handle, shard, tuning or batch.
-static int wrap_kt(const mfb_ctx *c, bool span, int MU) {
-    if (!wrap_mfma_enabled() || c->segl != 8 || c->N < (1 << 18) || !c->sum_all || !MFB_SEG_SUMQ || !c->bank || MU > 8) return 0;
-    const bool presum = span || std::all_of(c->h_mult.begin(), c->h_mult.end(), [&](int m) { return m == c->h_mult[0]; });
-    if (!presum || !segf_has_presum<256, 13>() || c->V != 13 * SegCfg<256>::NT) return 0;
-    const int T = c->bank->T;
-    return (T > 32 && T <= 48) ? 3 : 0;
-}
 // per-bin spectra of the bank in force (the unique filters, or the span basis), built when the shifts or the filters have changed
-static int fsm_prepare(mfb_ctx *c, bool span, int rows) {
-    const int wkt = wrap_kt(c, span, rows);
-    if (c->d_Gs && c->gs_rows == rows && c->gs_span == (span ? 1 : 0) && c->gs_l == c->segl && c->wb_kt == wkt) return MFB_OK;
+static int fsm_prepare(mfb_ctx *c, const SearchPlan &plan) {
+    const int span = plan.need_span, rows = plan.need_rows, wkt = plan.need_wkt;
+    if (c->d_Gs && c->gs_rows == rows && c->gs_span == span && c->gs_l == c->segl && c->wb_kt == wkt) return MFB_OK;
     if ((int)c->h_shifts.size() != c->Dtot || !c->bank) return MFB_ERR_STATE;
     std::vector<float> G, Q;
     std::vector<uint16_t> W;
@@ -1577,7 +1385,7 @@ static int fsm_prepare(mfb_ctx *c, bool span, int rows) {
     // SUM_ALL searches: the per-bin table of sum_rows w |G|^2 (segf_body, SUMQ); w = how often k_finalize counts the row, relative to
     // row 0, whose partial sums carry the bin's total
     std::vector<float> *q = (c->sum_all && MFB_SEG_SUMQ) ? &Q : nullptr;
-    const int L = 1 << c->segl, Te = L - seg_valid(c->segl, c->bank->T) + 1;
+    const int L = 1 << c->segl, Te = c->T;
     if (span) {
         taps::Bank sb;
         if (taps::span_basis(*c->bank, &sb) != rows) return MFB_ERR_STATE;
@@ -1615,237 +1423,70 @@ static int fsm_prepare(mfb_ctx *c, bool span, int rows) {
         c->wb_kt = wkt;
     }
     c->gs_rows = rows;
-    c->gs_span = span ? 1 : 0;
+    c->gs_span = span;
     c->gs_l = c->segl;
     return MFB_OK;
 }
-// A wave's rectangle (bins x slots) and what a group of the grid is.  The forward transform is shared by fb bins -- 1 / (fb MU) of
-// the inverse work --; small rectangles keep the grid over-subscribed (the surplus evens out CUs that finish at different times, as
-// in plan_seg).  Measured (profiles/r06_fft_ops.md): 128 (bin, filter) transforms of 256 points per forward transform -- 16 bins
-// of the 8-filter banks, 8 of the BPSK bank's 16 --, 64 of 2048 points.  Groups (blockIdx % 8 = XCD): an eighth of the BINS when
-// there are enough of them -- every XCD then keeps its share of the per-bin spectra in its L2 (C3: +4.5 %; the 2048-point kernel,
-// 32 MiB of spectra at 256 bins: 2.09 against 2.49 ms) and the samples stream through all of them --, else an eighth of the slots.
-//
-// The matrix-core form (k_segw) plans for itself.  A wave of it pays a slot's prologue -- samples, window, forward transform and the
-// 160 fragment registers, the matrix pipe idle and nothing else on the SIMD -- once per rectangle, so its rectangle is the group's
-// whole share of bins, in equal chunks of at most SEGW_FB (256 bins: 32, one chunk; 1024: four chunks of 32), and SEGW_FS slots
-// (measured, profiles/r12_wrap_slots.md: C2 2055 Msamples/s at 16 x 1, 2295 at 32 x 1, 2316 at 32 x 2, 2310 ... 2323 at 32 x 5, 2273
-// at 32 x 10, one launch round with nothing to even out).  It holds one wave per SIMD, not three: its small-launch bound is a wave for
-// every SIMD, reached by giving up slots per wave first, which cost nothing, and bins only then.
-//
-// The wide plan of k_segw (profiles/r14_wrap_wide.md): chunks of at most SEGW_WIDE_FB = 64 bins, so that a slot's fragments are built
-// by half as many waves (C3 1.068x, 384 bins 1.07x, C2 1.03x on top of the pick's copy).  Its groups are always groups of BINS, with
-// the four waves of a workgroup on four slots of the same bins: they fetch the same 7 KiB of tables a bin (Wb 6 KiB, Qs 1 KiB) at
-// about the same time, so three of four fetches end in the CU's vector cache.  Over groups of slots the four waves are the four
-// chunks of one slot, every fetch goes to the L2 (measured at C2: 20.7 M L2 hits a launch against 7.0 M) and 64 bins gain 1 %
-// instead of 4.  So where an eighth of the bins does not fill a chunk and a quarter does (Dtot <= 256), the grid has FOUR groups,
-// each on a pair of XCDs (blockIdx % 4); from there on eight.  Under 128 bins the plan above stands.  A rectangle twice as long needs
-// twice the rounds to even out CUs that finish at different times, so the wide plan applies only where a launch of one-slot
-// rectangles has four waves for every SIMD, and it takes the most slots a wave (5 ... 1) that keep those four rounds (C2: 5040 waves
-// of 64 x 1; C3: 5040 of 64 x 4).  Anything smaller gets the plan above, unchanged.  Which form runs does not depend on the
-// rectangle or the groups (wrap_kt).
-struct FsmPlan {
-    bool ok, segw;
-    int nsg, gbins, fb, fs, nbc, nsc;
-};
-constexpr int SEGW_FB = 32, SEGW_FS = 5;
-constexpr int SEGW_WIDE_FB = 64, SEGW_WIDE_ROUNDS = 4;
-// whether launch_fsm takes k_segw<13, 3>: the bank, the basis and the block length decide (wrap_kt), nothing else
-static bool fsm_segw(const mfb_ctx *c, int MU) {
-    return wrap_kt(c, c->basis == MFB_BASIS_SPAN, MU) == 3;
-}
-static FsmPlan fsm_plan(const mfb_ctx *c, int MU, int nfull, int nb = 1) {
-    static int env_fb = 0, env_fs = 0;
-    static const bool env_read = [] {
-        const char *e = getenv("MFB_SEG_FSM_RECT");
-        if (e) sscanf(e, "%d,%d", &env_fb, &env_fs);
-        return true;
-    }();
-    (void)env_read;
-    static const int env_gb = getenv("MFB_SEG_FSM_GROUP") ? atoi(getenv("MFB_SEG_FSM_GROUP")) : -1;
-    FsmPlan p;
-    memset(&p, 0, sizeof(p));
-    const bool w32 = c->segl == 11;
-    p.segw = fsm_segw(c, MU);
-    p.nsg = nfull >= 64 ? 8 : 1;
-    const int per_fwd = w32 ? 64 : 128;
-    const bool fb_set = c->fsm_fb > 0 || env_fb > 0, fs_set = c->fsm_fs > 0 || env_fs > 0;
-    int fb = c->fsm_fb > 0 ? c->fsm_fb : (env_fb > 0 ? env_fb : (per_fwd / MU > 2 ? per_fwd / MU : 2));
-    int fs = c->fsm_fs > 0 ? c->fsm_fs : (env_fs > 0 ? env_fs : (p.segw ? SEGW_FS : 1));
-    if (p.segw && !fb_set && env_gb < 0 && p.nsg > 1 && c->Dtot >= 4 * SEGW_FB) {
-        // the wide plan, where the launch is long enough for it
-        const int wnsg = c->Dtot <= 4 * SEGW_WIDE_FB ? 4 : 8;
-        const int share = (c->Dtot + wnsg - 1) / wnsg;
-        const int chunks = (share + SEGW_WIDE_FB - 1) / SEGW_WIDE_FB;
-        const long long want = (long long)SEGW_WIDE_ROUNDS * 4 * c->num_cus;
-        auto wwaves = [&](int s) { return (long long)nb * wnsg * chunks * ((nfull + s - 1) / s); };
-        if (wwaves(1) >= want) {
-            if (fs > nfull) fs = nfull;
-            while (!fs_set && fs > 1 && wwaves(fs) < want) --fs;
-            p.nsg = wnsg;
-            p.gbins = 1;
-            p.fb = (share + chunks - 1) / chunks;
-            p.fs = fs;
-            p.nbc = (share + p.fb - 1) / p.fb;
-            p.nsc = (nfull + fs - 1) / fs;
-            p.ok = true;
-            return p;
-        }
-    }
-    if (fb > c->Dtot) fb = c->Dtot;
-    p.gbins = env_gb >= 0 ? (env_gb != 0) : (p.nsg > 1 && c->Dtot >= p.nsg * fb ? 1 : 0);
-    if (p.gbins && c->Dtot < p.nsg) p.gbins = 0;
-    if (w32 && !p.gbins && p.nsg > 1 && env_gb < 0) {
-        // the long kernel's spectra (16 KiB per (bin, filter)) must stay in an L2: fewer bins per rectangle, or not this kernel
-        fb = c->Dtot / p.nsg;
-        if (fb < 1) return p;
-        p.gbins = 1;
-    }
-    const int glen = p.gbins ? nfull : (nfull + p.nsg - 1) / p.nsg;
-    const int gblen = p.gbins ? (c->Dtot + p.nsg - 1) / p.nsg : c->Dtot;
-    if (p.segw && !fb_set) {
-        const int chunks = (gblen + SEGW_FB - 1) / SEGW_FB;
-        fb = (gblen + chunks - 1) / chunks;
-    }
-    if (fs > glen) fs = glen;
-    if (fb > gblen) fb = gblen;
-    if (fb < 1 || fs < 1) return p;
-    // Small problems (one block of 2^15 samples x 64 bins: 2496 (bin, slot) units) must not be folded into a few long waves: the
-    // rectangle shrinks until the launch has twice the waves the device holds at once -- at one bin per rectangle the forward
-    // transform is no longer shared, and what is left of the gain is the mixing multiply (measured: bench.py's one-block loop at
-    // 2^15 x 64 fell from 250 to 155 Msamples/s with 16-bin rectangles: 156 waves on 1024 SIMDs)
-    auto waves = [&] { return (long long)nb * p.nsg * ((gblen + fb - 1) / fb) * ((glen + fs - 1) / fs); };
-    if (p.segw) {
-        const long long want = 4LL * c->num_cus;
-        while (!fs_set && fs > 1 && waves() < want) fs = (fs + 1) >> 1;
-        while (!fb_set && fb > 1 && waves() < want) fb = (fb + 1) >> 1;
-    } else if (!fb_set) {
-        const long long want = 2LL * c->num_cus * 4 * (w32 ? 2 : 3);
-        while (fb > 1 && waves() < want) fb >>= 1;
-    }
-    p.fb = fb;
-    p.fs = fs;
-    p.nbc = (gblen + fb - 1) / fb;
-    p.nsc = (glen + fs - 1) / fs;
-    p.ok = true;
-    return p;
-}
-template <int L, int PV0, int PV1>
-static int launch_segf_pv(mfb_ctx *c, const SegFArgs &a, int grid, size_t lds, int pv) {
-    if constexpr (PV0 > PV1) {
-        return MFB_ERR_UNSUPPORTED;
-    } else {
-        if (pv == PV0) {
-            bool done = false;
-            if constexpr (segf_has_presum<L, PV0>()) {
-                if (a.Qs && a.presum) {      // ... and the filter rows summed in registers
-                    hipLaunchKernelGGL((k_segf<L, PV0, 2>), dim3(grid), dim3(SegCfg<L>::BLOCK), lds, c->stream, a);
-                    done = true;
-                }
-            }
-            if constexpr (segf_has_sumq<L, PV0>()) {
-                if (a.Qs && !done) {         // SUM_ALL: the Parseval half of the complement form once per bin
-                    hipLaunchKernelGGL((k_segf<L, PV0, 1>), dim3(grid), dim3(SegCfg<L>::BLOCK), lds, c->stream, a);
-                    done = true;
-                }
-            }
-            if (!done) hipLaunchKernelGGL((k_segf<L, PV0, 0>), dim3(grid), dim3(SegCfg<L>::BLOCK), lds, c->stream, a);
-            HIPCHK(hipGetLastError());
-            return MFB_OK;
-        }
-        return launch_segf_pv<L, PV0 + 1, PV1>(c, a, grid, lds, pv);
-    }
-}
-// the complete slots of nb blocks through k_segf; the caller has the partial sums reserved
-static int launch_fsm(mfb_ctx *c, int nb, const cf *x, int xstride, int MU, int nfull, int parts, int pv) {
+// the complete slots of nb blocks through k_segf / k_segw, as planned; the caller has the partial sums reserved
+static int launch_fsm(mfb_ctx *c, const SearchPlan &p, int nb, const cf *x, int xstride) {
+    // fsm_prepare built the bin tables for this plan; tables that do not match it are an error, not a reason to run another form
+    const bool tables = c->d_Gs && c->gs_rows == p.need_rows && c->gs_span == p.need_span && c->gs_l == p.need_segl && c->wb_kt == p.need_wkt &&
+                        (!p.sumq || c->d_Qs) && (!p.need_wkt || (c->d_Wb && c->d_Wexp));
+    if (!tables || (p.form == SEARCH_SEGW && (p.sumq != 2 || p.pv != SEGW_PV))) return MFB_ERR_STATE;
     SegFArgs a;
     memset(&a, 0, sizeof(a));
-    a.x = x;
-    a.Gs = c->d_Gs;
+    a.x = x, a.xstride = xstride, a.nblk = nb, a.dper = c->Dtot;
+    a.Gs = c->d_Gs, a.twL = c->d_twL;
     a.Qs = c->sum_all ? c->d_Qs : nullptr;
-    a.presum = c->gs_span == 1 || std::all_of(c->h_mult.begin(), c->h_mult.end(), [&](int m) { return m == c->h_mult[0]; }) ? 1 : 0;
-    a.twL = c->d_twL;
-    a.partials = c->d_part;
-    a.N = c->N;
-    a.V = c->V;
-    a.slot0 = 0;
-    a.nslots = nfull;
-    a.MU = MU;
-    a.dper = c->Dtot;
-    a.nblk = nb;
-    a.xstride = xstride;
-    const FsmPlan fp = fsm_plan(c, MU, nfull, nb);
-    if (!fp.ok) return MFB_ERR_UNSUPPORTED;
-    a.nsg = fp.nsg;
-    a.gbins = fp.gbins;
-    a.fb = fp.fb;
-    a.fs = fp.fs;
-    a.nbc = fp.nbc;
-    a.nsc = fp.nsc;
-    a.part_row0 = 0;
-    a.parts = parts;
+    a.presum = p.presum;
+    a.partials = c->d_part, a.part_row0 = 0, a.parts = p.parts;
+    a.N = c->N, a.V = c->V, a.MU = p.rows;
+    a.slot0 = 0, a.nslots = p.nfull;
+    a.nsg = p.nsg, a.gbins = p.gbins, a.fb = p.fb, a.fs = p.fs, a.nbc = p.nbc, a.nsc = p.nsc;
     a.scale = 1.0f / 262144.0f;
-    const bool w32 = c->segl == 11;
-    const long long waves = (long long)nb * a.nbc * a.nsc;
-    const int wpb = SegCfg<256>::BLOCK / 64;
-    static_assert(SegCfg<256>::BLOCK == SegCfg<2048>::BLOCK || !MFB_SEG_W32, "four independent waves per workgroup");
-    const int grid = a.nsg * (int)((waves + wpb - 1) / wpb);
-    if (w32) {
-        const size_t lds = SegCfg<2048>::LDS_ELEMS * sizeof(cf) + (size_t)wpb * MU * SEG_ACC_STRIDE * sizeof(float);
-        return launch_segf_pv<2048, 16, 32>(c, a, grid, lds, pv);
-    }
     // the wrap-around energy on the matrix cores (wrap_kernels.hpp)
-    if (fp.segw) {
-        // fsm_prepare built the bin tables from the same answer of wrap_kt; tables that do not match it are an error, not a reason
-        // to run the other form
-        const bool tables = a.Qs && a.presum && c->d_Wb && c->wb_kt == 3 && c->gs_span == (c->basis == MFB_BASIS_SPAN ? 1 : 0);
-        if (!tables || pv != 13) return MFB_ERR_STATE;
-        SegWArgs w;
-        w.f = a;
-        w.Wb = c->d_Wb;
-        w.Wexp = c->d_Wexp;
-        w.T = c->bank->T;
-        const size_t wlds = SegWCfg<13, 3>::lds_bytes();
-        hipLaunchKernelGGL((k_segw<13, 3>), dim3(grid), dim3(SegCfg<256>::BLOCK), wlds, c->stream, w);
+    if (p.form == SEARCH_SEGW) {
+        const SegWArgs w = {a, c->d_Wb, c->d_Wexp, c->bank->T};
+        hipLaunchKernelGGL((k_segw<SEGW_PV, SEGW_KT>), dim3(p.grid), dim3(SegCfg<256>::BLOCK), (size_t)p.lds_bytes, c->stream, w);
         HIPCHK(hipGetLastError());
         return MFB_OK;
     }
-    const size_t lds = SegCfg<256>::LDS_ELEMS * sizeof(cf) + (size_t)wpb * MU * SEG_ACC_STRIDE * sizeof(float);
-    return launch_segf_pv<256, 8, 16>(c, a, grid, lds, pv);
+    const int rc = visit_segf([&](auto k) -> int {
+        using K = decltype(k);
+        if (K::SEGL != p.segl || K::PV != p.pv || K::MODE != p.sumq) return VISIT_NEXT;
+        hipLaunchKernelGGL((k_segf<K::L, K::PV, K::MODE>), dim3(p.grid), dim3(SegCfg<K::L>::BLOCK), (size_t)p.lds_bytes, c->stream, a);
+        HIPCHK(hipGetLastError());
+        return MFB_OK;
+    });
+    return rc == VISIT_NEXT ? MFB_ERR_UNSUPPORTED : rc;
 }
 
 // Build the per-bin spectra as soon as filters, shifts and the path are known (mfb_set_filters / mfb_set_shifts / mfb_set_search_*),
 // not inside the first search: 512 transforms of 2048 points for the 384-tap bank at 64 bins are 10-20 ms of host work, which does
 // not belong into a receive loop's first block.  (The search still checks, and builds what is missing.)
 static int fsm_prepare_eager(mfb_ctx *c) {
-    if (!c->have_filters || !c->have_shifts || c->path != MFB_PATH_SEGMENT || !fsm_enabled()) return MFB_OK;
-    const bool span = c->basis == MFB_BASIS_SPAN;
-    const int MU = span ? c->MB : c->MU;
-    int nfull, ntotal;
-    seg_slots(c, &nfull, &ntotal);
-    const bool fsm_l = c->segl == 8 || (c->segl == 11 && MFB_SEG_W32 && MU <= 8 && (size_t)c->Dtot * MU * 16384 <= ((size_t)256 << 20));
-    if (!(fsm_l && MU <= SEG_MPB_MAX && nfull > 0 && (int)c->h_shifts.size() == c->Dtot && fsm_plan(c, MU, nfull).ok)) return MFB_OK;
-    return fsm_prepare(c, span, MU);
+    if (!c->have_filters || !c->have_shifts || c->path != MFB_PATH_SEGMENT) return MFB_OK;
+    const SearchPlan p = plan_search(search_inputs(c), segments(c), 1);
+    return p.need_tables ? fsm_prepare(c, p) : MFB_OK;
 }
 // how the segment search of the next block will run: filter_side = 1 when the Doppler shift sits on the filters' side (k_segf: one
 // forward transform per segment for `bins_per_forward` bins), 0 when every (bin, segment) is mixed and transformed (k_seg)
 extern "C" int mfb_get_search_info(mfb_ctx *c, int *filter_side, int *bins_per_forward) {
     if (!c || !filter_side || !bins_per_forward) return MFB_ERR_ARG;
-    *filter_side = 0;
-    *bins_per_forward = 1;
-    if (c->path != MFB_PATH_SEGMENT || !c->have_filters) return MFB_OK;
-    const bool span = c->basis == MFB_BASIS_SPAN;
-    const int MU = span ? c->MB : c->MU;
-    int nfull, ntotal;
-    seg_slots(c, &nfull, &ntotal);
-    const bool fsm_l = c->segl == 8 || (c->segl == 11 && MFB_SEG_W32 && MU <= 8 && (size_t)c->Dtot * MU * 16384 <= ((size_t)256 << 20));
-    if (fsm_l && fsm_enabled() && MU <= SEG_MPB_MAX && nfull > 0 && (int)c->h_shifts.size() == c->Dtot) {
-        const FsmPlan p = fsm_plan(c, MU, nfull);
-        if (p.ok) {
-            *filter_side = 1;
-            *bins_per_forward = p.fb;
-        }
-    }
+    const bool planned = c->path == MFB_PATH_SEGMENT && c->have_filters;
+    const SearchPlan p = planned ? plan_search(search_inputs(c), segments(c), 1) : SearchPlan{};
+    *filter_side = p.need_tables;
+    *bins_per_forward = p.need_tables ? p.fb : 1;
+    return MFB_OK;
+}
+extern "C" int mfb_debug_search_plan(mfb_ctx *c, mfb_plan_inputs *inputs, int nblocks, mfb_search_plan *out) {
+    if (!inputs || !out || nblocks < 1) return MFB_ERR_ARG;
+    if (c && !c->have_filters) return MFB_ERR_STATE;
+    if (c) *inputs = search_inputs(c);
+    const Segments sg = c ? segments(c) : resolve_segments(*inputs);
+    if (!sg.ok) return MFB_ERR_UNSUPPORTED;
+    *out = plan_search(*inputs, sg, nblocks);
+    if (sg.path == MFB_PATH_SEGMENT) out->store = plan_store(*inputs, sg, nblocks);     // ... and the matched-filter pass of the same blocks
     return MFB_OK;
 }
 
@@ -1854,57 +1495,31 @@ extern "C" int mfb_get_search_info(mfb_ctx *c, int *filter_side, int *bins_per_f
 // the plain search of one block.  A score depends on the block, the shift and the filter only (seg_kernels.hpp), so a
 // block's rows come out bit for bit the same whichever batch it is part of.
 static int seg_search_enqueue(mfb_ctx *c, int nb, const cf *x, int xstride, float *dsum) {
-    // all bins in ONE launch: nothing of length N is written, so there is nothing to chunk.  A second,
-    // tiny launch of the masked instantiation covers the slots that hold incomplete segments.
-    const bool span = c->basis == MFB_BASIS_SPAN;
-    const int MU = span ? c->MB : c->MU;     // filters transformed per bin
-    const int rows = nb * c->Dtot;           // Doppler streams of the launch
-    int nfull, ntotal;
-    seg_slots(c, &nfull, &ntotal);
-    const SegPlan pm = plan_seg(c, rows, MU, nfull > 0 ? nfull : 1, c->seg_mpb, true);
-    // the tail is a handful of units: spread the filters too (2 per pass) so that it is short
-    const SegPlan pt = plan_seg(c, rows, MU, ntotal - nfull > 0 ? ntotal - nfull : 1, c->seg_mpb > 0 && c->seg_mpb < 2 ? c->seg_mpb : 2);
-    // one partial per (bin, filter, slot, wave of the team): the index depends on the slot alone (seg_kernels.hpp)
-    const int parts = ntotal * seg_geom(c).WPT;
-    int rc = reserve_partials(c, (size_t)rows * MU * parts);
+    const SearchPlan p = plan_search(search_inputs(c), segments(c), nb);     // every decision of this search, taken once
+    const bool span = p.basis == MFB_BASIS_SPAN;
+    const int MU = p.rows, rows = nb * c->Dtot;      // filters transformed per bin, Doppler streams of the launch
+    int rc = reserve_partials(c, (size_t)rows * MU * p.parts);
     if (rc) return rc;
-    // 256-point segments: the shift on the filter side -- one forward transform per segment for all bins (segf_body)
-    // (the wave-local 2048-point kernel too: 8 filters per pass there, and per-bin spectra of 16 KiB per (bin, filter) -- up to 256 MiB)
-    const bool fsm_l = c->segl == 8 || (c->segl == 11 && MFB_SEG_W32 && MU <= 8 && (size_t)c->Dtot * MU * 16384 <= ((size_t)256 << 20));
-    const bool fsm = fsm_l && fsm_enabled() && MU <= SEG_MPB_MAX && nfull > 0 && (int)c->h_shifts.size() == c->Dtot && fsm_plan(c, MU, nfull).ok;
-    if (fsm && (rc = fsm_prepare(c, span, MU))) return rc;       // (built by the first block: nothing is allocated inside a graph capture)
-    SegArgs am = seg_base(c, pm), at = seg_base(c, pt);
-    for (SegArgs *q : {&am, &at}) {
-        if (span) {
-            q->G = c->d_Gb;
-            q->Grows = c->MB;
-        }
-        q->x = x;
-        q->rows = (!span && MU < c->M) ? c->d_uniq : nullptr;
-        q->shifts = c->d_shifts;
-        q->partials = c->d_part;
-        q->MU = MU;
-        q->dc = rows;
-        q->parts = parts;
-        if (nb > 1) {
-            q->dper = c->Dtot;
-            q->xstride = xstride;
-        }
-    }
-    am.slot0 = 0;
-    am.nslots = nfull;
-    at.slot0 = nfull;
-    at.nslots = ntotal - nfull;
-    const int pv = c->V / seg_geom(c).NT;
+    if (p.need_tables && (rc = fsm_prepare(c, p))) return rc;       // (built by the first block: nothing is allocated inside a graph capture)
+    auto seg_args = [&](const SegPlan &sp, int slot0, int nslots) {
+        SegArgs a = seg_base(c, sp);
+        if (span) a.G = c->d_Gb, a.Grows = c->MB;
+        a.x = x, a.shifts = c->d_shifts, a.partials = c->d_part;
+        a.rows = (!span && MU < c->M) ? c->d_uniq : nullptr;
+        a.MU = MU, a.dc = rows, a.parts = p.parts;
+        if (nb > 1) a.dper = c->Dtot, a.xstride = xstride;
+        a.slot0 = slot0, a.nslots = nslots;
+        return a;
+    };
     prof_mark(c, 0);
     // (both roles inside one grid were tried: the merged kernel ran 8-10 % slower than two launches)
-    if (fsm) rc = launch_fsm(c, nb, x, xstride, MU, nfull, parts, pv);
-    else if (nfull > 0) rc = launch_seg(c, am, pm.grid, SEG_REDUCE, pv);
-    if (!rc && ntotal > nfull) rc = launch_seg(c, at, pt.grid, SEG_REDUCE, -1);
+    if (p.need_tables) rc = launch_fsm(c, p, nb, x, xstride);
+    else if (p.form == SEARCH_SEG) rc = launch_seg(c, seg_args(p.main_seg, 0, p.nfull), p.main_seg, SEG_REDUCE, p.pv);
+    if (!rc && p.ntotal > p.nfull) rc = launch_seg(c, seg_args(p.tail, p.nfull, p.ntotal - p.nfull), p.tail, SEG_REDUCE, -1);
     if (rc) return rc;
     prof_mark(c, 0);
     hipLaunchKernelGGL(k_finalize, dim3(rows), dim3(fin_threads(MU)), 0, c->stream, c->d_part, dsum, rows, c->M, MU,
-                       span ? (const int *)nullptr : (const int *)c->d_rep, parts, c->sum_all);
+                       span ? (const int *)nullptr : (const int *)c->d_rep, p.parts, c->sum_all);
     HIPCHK(hipGetLastError());
     return MFB_OK;
 }
@@ -2135,13 +1750,13 @@ static int demod_enqueue(mfb_ctx *c, const BlkBufs &bb, int shift, const int *sh
     const int nb = bb.nb;
     if (c->path == MFB_PATH_SEGMENT) {
         // the same segment kernel, storing y in natural order instead of reducing it (no transpose)
-        int nfull, ntotal;
-        seg_slots(c, &nfull, &ntotal);
         // one bin: spread the slots over the chip.  When a team takes all M filters of its segments (M <= 16) it also
         // sums the symbol-energy envelope (sumXCorrBuffMasks, CU:191-205) in the same pass; otherwise the filters are
-        // spread too and k_envelope follows
+        // spread too and k_envelope follows (plan_store)
         const bool fused_env = c->M <= SEG_MPB_MAX;
-        const SegPlan p = plan_seg(c, nb, c->M, ntotal, fused_env ? c->M : 4);
+        const SegPlan p = plan_store(search_inputs(c), segments(c), nb);
+        int nfull, ntotal;
+        seg_slots(c->N, segments(c), &nfull, &ntotal);
         SegArgs sa = seg_base(c, p);
         sa.x = bb.x;
         sa.out = bb.xc;
@@ -2164,7 +1779,7 @@ static int demod_enqueue(mfb_ctx *c, const BlkBufs &bb, int shift, const int *sh
             sa.sstride = shift_stride;
             sa.ostride = (long long)c->M * c->N;
         }
-        rc = launch_seg(c, sa, p.grid, SEG_STORE, -1);
+        rc = launch_seg(c, sa, p, SEG_STORE, -1);
         if (rc) return rc;
     } else {
         if (nb != 1) return MFB_ERR_UNSUPPORTED;        // batches of blocks run on the segment path

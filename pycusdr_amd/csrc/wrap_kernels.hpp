@@ -10,7 +10,7 @@
 // run here as v_mfma_f32_16x16x32_f16: row tile rt (16 outputs) x K-step kk (taps 16 kk ... 16 kk + 15, real and imaginary halves of the
 // window).  The Toeplitz block of (rt, kk) depends on rt - kk only, so a segment has RT + KT - 1 distinct A fragments.
 // The instantiated shape (PV = 13 valid register slots, KT = 3) serves banks of 34 ... 48 taps: with 33 taps a segment has 14 valid
-// slots, 49 taps need a fourth K-step (mfbank.hip, wrap_kt).  Taps 16 KT - 1 down to T are zero rows of the B fragments, and the
+// slots, 49 taps need a fourth K-step (search_plan.hpp, wrap_kt).  Taps 16 KT - 1 down to T are zero rows of the B fragments, and the
 // window is zeroed below offset -(T - 1), so that the segment's scale comes from the samples the product reads.
 //
 // fp16 precision from a split: each operand is scaled by a power of two chosen from the data (the segment window: its largest
@@ -23,7 +23,7 @@
 // A bin's number depends on its own tables and the slot's samples only, summed in one fixed order: the same bits whichever bins share
 // the rectangle, whatever the grid or the batch.
 //
-// The rectangle of bins x slots is this form's own (mfbank.hip, fsm_plan): a slot's prologue -- samples, window, forward transform and
+// The rectangle of bins x slots is this form's own (search_plan.hpp, fsm_plan): a slot's prologue -- samples, window, forward transform and
 // the 160 fragment registers -- runs with the matrix pipe idle and nothing else on the SIMD, so a wave takes its group's whole share
 // of bins, up to 32 a chunk, and pays the prologue once for them (profiles/r12_wrap_slots.md: C2 1.13x over 16 bins) -- up to 64 a
 // chunk where the launch is long enough to keep four rounds of waves (profiles/r14_wrap_wide.md: the fixed part of a slot is 9.4 k

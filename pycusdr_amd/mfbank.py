@@ -384,6 +384,11 @@ class MFBank:
         _lib.check(self._lib.mfb_get_search_info(self._h, C.byref(f), C.byref(b)), 'mfb_get_search_info')
         return {'filter_side': bool(f.value), 'bins_per_forward': int(b.value)}
 
+    def debug_search_plan(self, nblocks=1):
+        """(inputs, plan) of the next segment search of `nblocks` blocks: what the planner is asked for this handle, and every
+        launch and table decision it takes (mfb_debug_search_plan; both as dicts of ints, see debug_search_plan below)."""
+        return debug_search_plan(None, nblocks, _handle=self._h)
+
     def xcorr(self, a, b):
         """ifft(fft(a, N) * conj(fft(b, N))) for real sequences a, b (reference lib/customXCorr.py:5-18);
         N is this handle's block length.  The handle's filters and input are invalidated."""
@@ -835,6 +840,26 @@ def analyze_rank(masks):
     r = C.c_int()
     _lib.check(lib.mfb_analyze_rank(_ptr(masks), masks.shape[0], masks.shape[1], C.byref(r)), 'mfb_analyze_rank')
     return r.value
+
+
+def _struct_dict(s):
+    out = {}
+    for name, typ in s._fields_:
+        v = getattr(s, name)
+        if issubclass(typ, C.Structure):
+            out.update({f'{name}.{k}': x for k, x in _struct_dict(v).items()})
+        else:
+            out[name] = int(v)
+    return out
+
+
+def debug_search_plan(inputs, nblocks=1, _handle=None):
+    """The segment search's plan for a dict of mfb_plan_inputs fields (include/mfbank.h) -- host-only, no GPU needed.  Returns
+    (inputs, plan) as flat dicts of ints (nested launch geometries as 'tail.grid', ...); ValueError where the library refuses."""
+    lib = _lib.load()
+    i, p = _lib.PlanInputs(**(inputs or {})), _lib.SearchPlan()
+    _lib.check(lib.mfb_debug_search_plan(_handle, C.byref(i), int(nblocks), C.byref(p)), 'mfb_debug_search_plan')
+    return _struct_dict(i), _struct_dict(p)
 
 
 _xcorr_banks = {}

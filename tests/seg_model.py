@@ -89,7 +89,7 @@ def segment_xcorr(x, masks, shift, L, thr=1e-13):
 
 
 def seg_valid(T, L=256, NT=16):
-    """Valid outputs per complete L-point segment (mfbank.hip, seg_valid): whole register slots of NT outputs, 0 when fewer than
+    """Valid outputs per complete L-point segment (csrc/search_plan.hpp, seg_valid): whole register slots of NT outputs, 0 when fewer than
     half of the segment's slots would be valid."""
     pv = (L - T + 1) // NT
     return pv * NT if pv >= (L // NT) // 2 else 0
@@ -97,7 +97,7 @@ def seg_valid(T, L=256, NT=16):
 
 def wrap_form(N, counts, T, sum_all, span_rank=None, log2L=8):
     """Which form of the filter-side search scores a block: 'matrix' (wrap_kernels.hpp, k_segw) or 'vector' (segf_body).  Restates
-    wrap_kt of mfbank.hip as a function of the block length N, how often each unique filter of the bank counts (``counts``: one entry
+    wrap_kt of csrc/search_plan.hpp as a function of the block length N, how often each unique filter of the bank counts (``counts``: one entry
     per filter the search transforms; exact copies and exact negatives of an earlier filter count with it), the taps T of the bank's
     common support, SUM_ALL, and -- for the span basis -- the rank of the bank (None: the default basis, the unique filters)."""
     rows = len(counts) if span_rank is None else span_rank

@@ -1,4 +1,4 @@
-"""The slots of a wave of the matrix-core search (wrap_kernels.hpp, k_segw): the planner (fsm_plan) gives this form a rectangle of its
+"""The slots of a wave of the matrix-core search (wrap_kernels.hpp, k_segw): the planner (fsm_plan, csrc/search_plan.hpp) gives this form a rectangle of its
 own -- the group's whole share of bins, up to 32 a chunk, and several slots a wave --, so that a wave now walks from slot to slot with
 its fragments, windows and bin tables rebuilt each time.  What a wave keeps from slot to slot must not reach the bits: every
 rectangle (MFB_SEG_FSM_RECT = bins,slots, and the planner's default without it) is held to the one-bin, one-slot rectangle, which

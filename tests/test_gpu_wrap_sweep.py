@@ -3,7 +3,7 @@ that reaches it -- not the bench_GMSK headline alone (tests/test_gpu_wrap_mfma.p
 oracle (tests/tools/fuzz_wrap.py), the other shipped 48-tap banks, the span basis, batches of blocks, exact power-of-two scaling of
 the input, and handles whose shifts, filters and basis change while they live.
 
-Which form scores a block is ``seg_model.wrap_form``, a restatement of wrap_kt (mfbank.hip); where it says 'matrix' the tables of
+Which form scores a block is ``seg_model.wrap_form``, a restatement of wrap_kt (csrc/search_plan.hpp); where it says 'matrix' the tables of
 the two settings of MFB_SEG_WRAP_MFMA must differ, where it says 'vector' they must be bit-equal.  MFB_SEG_WRAP_MFMA is read once
 per process: each form runs in a child of its own, every child under a time limit, and a child that fails ends the test."""
 import os

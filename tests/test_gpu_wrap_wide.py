@@ -1,4 +1,4 @@
-"""Rectangles of 64 bins in the matrix-core search (wrap_kernels.hpp, k_segw; the planner is fsm_plan in mfbank.hip): a wave that
+"""Rectangles of 64 bins in the matrix-core search (wrap_kernels.hpp, k_segw; the planner is fsm_plan in csrc/search_plan.hpp): a wave that
 builds a slot's fragments once for 64 bins instead of 32, over groups of slots, over eight groups of bins or over four.  The bits
 must not know: every table is equal to the one-bin, one-slot rectangle's of the same D on both inputs of the child, picks equal.
 bench_GMSK at 2^18 samples (315 complete slots), the smallest block on this form; one child per rectangle
