@@ -32,6 +32,7 @@
 //   envelope        cuda_kernels.cu:191-205             rate/phase  cuda_kernels.cu:236-320
 //   centres         cuda_kernels.cu:78-146
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -40,6 +41,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <deque>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -60,6 +62,7 @@
 #include "snr_kernels.hpp"
 #include "unpack_kernels.hpp"
 #include "hostcopy.hpp"
+#include "hip_owned.hpp"
 #include "record_layout.hpp"
 
 // ------------------------------------------------------------------------------------------------
@@ -85,129 +88,132 @@ struct BlockGraph {
     bool seen, failed;
 };
 
+// Every buffer, event and library-made stream of a handle is an owner (hip_owned.hpp), and every member has an initialiser: adding one
+// is one declaration here.  ~mfb_ctx releases them in reverse order of declaration, so the four streams, declared first, go last:
+// behind every event recorded on them and every buffer their work used (mfb_destroy has waited for all four by then).
 struct mfb_ctx {
-    int device;
-    int log2N, N, N1, N2, l1, l2, lo;
-    int D, Doff, Dtot, M, W, sum_all, cs_off;
-    int chunk, mpb, jsplit;
-    int MU;               // unique filter rows (up to sign)
-    bool chunk_auto;      // chunk still at its default (recomputed when the bank turns out to have duplicates)
-    int *d_uniq, *d_rep;  // [MU] bank row of each unique filter; [M] unique index of each filter
-    int parts, srb;
-    int num_cus;          // compute units of the handle's device
-    hipStream_t own_stream, stream;
-    cf *h_in;  // pinned
+    Stream own_stream, copy_stream, in_stream, s2;   // the handle's own; the spectrum mirror's; host-to-device copies of the block path; part 2 (below)
+    hipStream_t stream = nullptr;                    // own_stream, or the caller's (mfb_set_stream): not owned
+    int device = 0;
+    int log2N = 0, N = 0, N1 = 0, N2 = 0, l1 = 0, l2 = 0, lo = 0;
+    int D = 0, Doff = 0, Dtot = 0, M = 0, W = 0, sum_all = 0, cs_off = 0;
+    int chunk = 0, mpb = 0, jsplit = 0;
+    int MU = 0;           // unique filter rows (up to sign)
+    bool chunk_auto = false;      // chunk still at its default (recomputed when the bank turns out to have duplicates)
+    DevBuf<int> d_uniq, d_rep;    // [MU] bank row of each unique filter; [M] unique index of each filter
+    int parts = 0, srb = 0;
+    int num_cus = 0;      // compute units of the handle's device
+    HostBuf<cf> h_in;     // pinned
     // page-locked landing zone of the small read-backs (pick, rate/phase, spectrum windows, symbol decisions): a
     // copy into pageable memory is staged by the runtime with a round trip of its own per copy
-    uint8_t *h_back;
-    size_t back_cap;
+    HostBuf<uint8_t> h_back;
+    size_t back_cap = 0;
     // the pick's own page-locked slot: k_pick stores its two floats there itself (h_pick_dev: the slot as the device addresses it),
     // so that no copy -- a blit kernel and its dispatch gap for 8 bytes -- stands between the kernel and the host's read
-    float *h_pick, *h_pick_dev;
+    HostBuf<float> h_pick;
+    float *h_pick_dev = nullptr;
     // Host mirror of the spectrum for small blocks.  The reference keeps the spectrum in host-mapped memory and reads
     // its SNR windows straight from there (DB:456-457, 651-661); here the first mfb_get_spectrum on a handle turns on
     // an asynchronous copy of every new spectrum (own stream, beside the search), so that later window reads cost no
     // host-device round trip.  Blocks above MIRROR_MAX_N keep fetching windows on demand.
-    cf *h_X;
-    bool mirror, mirror_valid;
-    hipStream_t copy_stream;
-    hipEvent_t ev_fft, ev_X;
-    cf *d_x, *d_X, *d_masks, *d_Z, *d_xc, *d_P;
-    const cf *d_in;  // current time-domain input (d_x or caller's device pointer)
-    float *d_env;
-    int *d_shifts;
-    cf *d_tw1, *d_tw2, *d_twLo, *d_twHi;
-    float *d_part, *d_sum, *d_res, *d_cr;
-    int *d_sym, *d_cen;
-    float *d_mag;
-    int cap;  // capacity of the centres buffers
-    size_t z_rows;  // rows allocated in d_Z
-    bool have_filters, have_shifts, have_input, have_xc;
-    hipEvent_t t0, t1;
-    bool prof;
+    HostBuf<cf> h_X;
+    bool mirror = false, mirror_valid = false;
+    Event ev_fft, ev_X;
+    DevBuf<cf> d_x, d_X, d_masks, d_Z, d_xc, d_P;
+    const cf *d_in = nullptr;  // current time-domain input (d_x or caller's device pointer): not owned
+    DevBuf<float> d_env;
+    DevBuf<int> d_shifts;
+    DevBuf<cf> d_tw1, d_tw2, d_twLo, d_twHi;
+    DevBuf<float> d_part, d_sum, d_res, d_cr;
+    DevBuf<int> d_sym, d_cen;
+    DevBuf<float> d_mag;
+    int cap = 0;  // capacity of the centres buffers
+    size_t z_rows = 0;  // rows allocated in d_Z
+    bool have_filters = false, have_shifts = false, have_input = false, have_xc = false;
+    Event t0, t1;
+    bool prof = false;
     // single-pass overlap-save path (seg_kernels.hpp)
-    int path_req, segl_req;   // requested: MFB_PATH_*, log2 L (0 = automatic)
-    int path, segl;           // resolved
-    int T, win_start, V, Q;   // taps, window start, valid outputs per segment, segments
-    int seg_wpc, seg_mpb;     // workgroups per CU, filters per team pass (0 = automatic)
-    cf *d_G, *d_twL;
-    int twL_len;
-    size_t part_cap;          // floats allocated in d_part
-    taps::Bank *bank;         // host copy of the taps (kept so that L can be changed)
-    int basis_req, basis;     // MFB_BASIS_*: requested / in force
-    int MB;                   // filters of the span basis
-    cf *d_Gb;                 // their segment spectra [MB][L] (slot-pair layout)
-    int gb_l;                 // segment length d_Gb was built for
-    int search_mode;          // MFB_SEARCH_*: transforms (default) or the opt-in spectral-energy shortcut
-    float *d_pow, *d_W;       // |X|^2 [N]; filter energy [R][N] (R = 1 under SUM_ALL_MASKS, else M)
-    cf *h_in2;                // second page-locked input buffer (blocks in flight alternate between the two)
-    cf *d_x2;                 // its device copy: the next block's samples arrive (own stream) while the current block is searched
-    hipStream_t in_stream;    // host-to-device copies of the block path
-    hipEvent_t ev_h2d[2];     // [input buffer]: the copy has landed
-    hipEvent_t ev_xfree[2];   // [input buffer]: the last block that read this device copy has been enqueued and finished
-    uint8_t *h_blk[2];        // page-locked staging of the two block flights
-    size_t blk_cap[2];
-    hipEvent_t ev_blk[2];
-    BlockFlight flight[2];
-    unsigned long long blk_seq;
-    BlockGraph bgraph[2][2];  // [input buffer][slot]: the block's launches as a HIP graph
-    unsigned long long epoch; // bumped by every change that invalidates them
-    uint8_t *d_blkout;        // mfb_receive_block: the block's result record (scalars | SNR windows | symbols), one copy to the host
-    uint8_t *d_blkout2;       // ... of flight slot 1 when a block runs as two parts on two streams (mfb_set_batch_overlap)
-    BlockGraph bgraph2[2][2]; // part 2's recorded graphs ([input buffer][slot]; bgraph holds part 1's, or the whole block)
-    BlockScalars *d_scal;     // = d_blkout
-    int band_cap;
-    bool W_valid;
+    int path_req = 0, segl_req = 0;   // requested: MFB_PATH_*, log2 L (0 = automatic)
+    int path = 0, segl = 0;           // resolved
+    int T = 0, win_start = 0, V = 0, Q = 0;   // taps, window start, valid outputs per segment, segments
+    int seg_wpc = 0, seg_mpb = 0;     // workgroups per CU, filters per team pass (0 = automatic)
+    DevBuf<cf> d_G, d_twL;
+    int twL_len = 0;
+    size_t part_cap = 0;              // floats allocated in d_part
+    std::unique_ptr<taps::Bank> bank; // host copy of the taps (kept so that L can be changed)
+    int basis_req = 0, basis = 0;     // MFB_BASIS_*: requested / in force
+    int MB = 0;                       // filters of the span basis
+    DevBuf<cf> d_Gb;                  // their segment spectra [MB][L] (slot-pair layout)
+    int gb_l = 0;                     // segment length d_Gb was built for
+    int search_mode = 0;              // MFB_SEARCH_*: transforms (default) or the opt-in spectral-energy shortcut
+    DevBuf<float> d_pow, d_W;         // |X|^2 [N]; filter energy [R][N] (R = 1 under SUM_ALL_MASKS, else M)
+    HostBuf<cf> h_in2;                // second page-locked input buffer (blocks in flight alternate between the two)
+    DevBuf<cf> d_x2;                  // its device copy: the next block's samples arrive (own stream) while the current block is searched
+    Event ev_h2d[2];                  // [input buffer]: the copy has landed
+    Event ev_xfree[2];                // [input buffer]: the last block that read this device copy has been enqueued and finished
+    HostBuf<uint8_t> h_blk[2];        // page-locked staging of the two block flights
+    size_t blk_cap[2] = {};
+    Event ev_blk[2];
+    BlockFlight flight[2] = {};
+    unsigned long long blk_seq = 0;
+    BlockGraph bgraph[2][2] = {};     // [input buffer][slot]: the block's launches as a HIP graph
+    unsigned long long epoch = 0;     // bumped by every change that invalidates them
+    DevBuf<uint8_t> d_blkout;         // mfb_receive_block: the block's result record (scalars | SNR windows | symbols), one copy to the host
+    DevBuf<uint8_t> d_blkout2;        // ... of flight slot 1 when a block runs as two parts on two streams (mfb_set_batch_overlap)
+    BlockGraph bgraph2[2][2] = {};    // part 2's recorded graphs ([input buffer][slot]; bgraph holds part 1's, or the whole block)
+    BlockScalars *d_scal = nullptr;   // = d_blkout: not owned
+    int band_cap = 0;
+    bool W_valid = false;
     // batches of blocks (mfb_receive_blocks_*): B consecutive blocks of ONE contiguous window of samples per launch set
-    int win_blocks, win_stride;   // capacity in blocks and block advance (N - overlap) the windows were made for
-    cf *h_win[2], *d_win[2];      // page-locked windows of win_blocks * win_stride + (N - win_stride) samples, and their device copies
-    hipEvent_t ev_wh2d[2], ev_wfree[2];
-    int bat_cap;                  // blocks the batch work buffers below hold
-    cf *d_Xb, *d_xcb, *d_Pb;      // spectra [B][N], matched-filter outputs [B][M][N], envelope spectra [B][N]
-    float *d_envb, *d_sumb, *d_resb, *d_crb;   // envelopes [B][N], doppSum [B][Dtot][M], picks [B][2], rate triples [B][3]
-    uint8_t *d_batout;            // result records [B][rec] of the batch in flight slot 0 ...
-    uint8_t *d_batout2;           // ... and slot 1 (the next batch's search writes its picks while this one's records are still read)
-    size_t batout_cap;
+    int win_blocks = 0, win_stride = 0;   // capacity in blocks and block advance (N - overlap) the windows were made for
+    HostBuf<cf> h_win[2];                 // page-locked windows of win_blocks * win_stride + (N - win_stride) samples ...
+    DevBuf<cf> d_win[2];                  // ... and their device copies
+    Event ev_wh2d[2], ev_wfree[2];
+    int bat_cap = 0;                      // blocks the batch work buffers below hold
+    DevBuf<cf> d_Xb, d_xcb, d_Pb;         // spectra [B][N], matched-filter outputs [B][M][N], envelope spectra [B][N]
+    DevBuf<float> d_envb, d_sumb, d_resb, d_crb;   // envelopes [B][N], doppSum [B][Dtot][M], picks [B][2], rate triples [B][3]
+    DevBuf<uint8_t> d_batout;             // result records [B][rec] of the batch in flight slot 0 ...
+    DevBuf<uint8_t> d_batout2;            // ... and slot 1 (the next batch's search writes its picks while this one's records are still read)
+    size_t batout_cap = 0;
     // A batch in two parts on two streams (round 6).  Part 1 -- forward transforms, search, pick: the kernels that fill the chip --
     // stays on `stream`; part 2 -- matched filters at the picked shift, envelope, its spectrum, rate, centres, the integer stages,
     // the read-back: a chain of small launches that leaves most of the chip idle -- goes to `s2`, behind an event, with an
     // intermediate of its own for its transforms (d_Z2).  The next batch's part 1 then runs beside this batch's part 2.
-    hipStream_t s2;
-    hipEvent_t ev_p1[2];          // [slot]: part 1 of the batch in that flight has been enqueued and finished
-    cf *d_Z2;
-    size_t z2_rows;
-    bool use_z2;                  // the transforms being enqueued use d_Z2 (part 2)
-    bool s2_busy;                 // something was enqueued on s2 since the last wait for it
-    bool batch_overlap;           // mfb_set_batch_overlap
-    bool device_snr;              // mfb_set_device_snr
-    int last_batch_blocks;        // blocks of the batch begun last (mfb_get_batch_scores)
-    int cu_part, cu_parts;        // mfb_set_cu_share (0, 0: the whole device)
-    BlockGraph wgraph2[2][2][2][WG_NB + 1];     // part 2's recorded graphs (wgraph holds part 1's)
+    Event ev_p1[2];               // [slot]: part 1 of the batch in that flight has been enqueued and finished
+    DevBuf<cf> d_Z2;
+    size_t z2_rows = 0;
+    bool use_z2 = false;          // the transforms being enqueued use d_Z2 (part 2)
+    bool s2_busy = false;         // something was enqueued on s2 since the last wait for it
+    bool batch_overlap = false;   // mfb_set_batch_overlap
+    bool device_snr = false;      // mfb_set_device_snr
+    int last_batch_blocks = 0;    // blocks of the batch begun last (mfb_get_batch_scores)
+    int cu_part = 0, cu_parts = 0;        // mfb_set_cu_share (0, 0: the whole device)
+    BlockGraph wgraph2[2][2][2][WG_NB + 1] = {};     // part 2's recorded graphs (wgraph holds part 1's)
     // [window][slot][carry parity][blocks of the batch]: a receive loop that takes whatever is complete (1 ... B blocks per call)
     // keeps one recorded graph per batch size it has met twice; sizes above WG_NB share entry 0 (recorded again when the size changes)
-    BlockGraph wgraph[2][2][2][WG_NB + 1];
+    BlockGraph wgraph[2][2][2][WG_NB + 1] = {};
     // the integer stages behind the symbol decisions on the device (stream_kernels.hpp; mfb_set_stream_stages): A12 bit lookup,
     // A13 block-overlap alignment, A14 sync search on the stream without a stash -- batches only
-    bool st_on;
-    StreamArgs st;                // constant part (LUTs, thresholds, templates); records, carries filled per batch
-    uint8_t *d_lut8;
-    int *d_lut3;
-    int8_t *d_sttmpl;
-    StreamCarry *d_carry[2];      // [parity]: the previous batch's tail and bit ring / this batch's
-    int carry_cur;                // buffer that holds the state the next batch starts from
-    StreamCarry *h_seed;          // page-locked staging of mfb_stream_seed
-    std::vector<hipEvent_t> ev[2];
-    std::vector<hipEvent_t> ev_pool;
+    bool st_on = false;
+    StreamArgs st = {};           // constant part (LUTs, thresholds, templates; its pointers own nothing); records, carries filled per batch
+    DevBuf<uint8_t> d_lut8;
+    DevBuf<int> d_lut3;
+    DevBuf<int8_t> d_sttmpl;
+    DevBuf<StreamCarry> d_carry[2];   // [parity]: the previous batch's tail and bit ring / this batch's
+    int carry_cur = 0;                // buffer that holds the state the next batch starts from
+    HostBuf<StreamCarry> h_seed;      // page-locked staging of mfb_stream_seed
+    std::vector<Event> ev[2];
+    std::vector<Event> ev_pool;
     // the search with the Doppler shift on the filter side (seg_kernels.hpp, segf_body; 256-point segments): per-bin spectra
     std::vector<int> h_shifts, h_uniq;   // host copies of the shift table and of the unique-filter map
     std::vector<int> h_mult;             // how many of the M filters each unique one stands for (k_finalize counts its row that often)
-    float *d_Qs = nullptr;               // [Dtot][L]: per-bin sum over the rows of |d_Gs|^2 (SUM_ALL searches; segf_body SUMQ), built with d_Gs
-    cf *d_Gs = nullptr;                  // [Dtot][rows][L]: rows = the unique filters, or the span basis
+    DevBuf<float> d_Qs;                  // [Dtot][L]: per-bin sum over the rows of |d_Gs|^2 (SUM_ALL searches; segf_body SUMQ), built with d_Gs
+    DevBuf<cf> d_Gs;                     // [Dtot][rows][L]: rows = the unique filters, or the span basis
     int gs_rows = 0;                     // rows per bin d_Gs was built for (0: not built)
     int gs_span = -1;                    // ... and for which basis
     int gs_l = 0;                        // ... and segment length (log2)
-    u32x4 *d_Wb = nullptr;               // [Dtot][KT][2][64]: B fragments of the wrap-around outputs (wrap_kernels.hpp), built with d_Gs
-    int *d_Wexp = nullptr;               // [Dtot]: their powers of two
+    DevBuf<u32x4> d_Wb;                  // [Dtot][KT][2][64]: B fragments of the wrap-around outputs (wrap_kernels.hpp), built with d_Gs
+    DevBuf<int> d_Wexp;                  // [Dtot]: their powers of two
     int wb_kt = 0;                       // K-steps d_Wb was built for (0: not built)
     // interference-peak clipping before the forward transform (clip_kernels.hpp, mfb_set_peak_clip; DB:670-707)
     float clip_scale = 0.f;              // 0: off
@@ -215,18 +221,18 @@ struct mfb_ctx {
     bool clip_restart = false;           // the next block's overlap is taken as given
     int clip_cap[2] = {};                // blocks the flight buffers below hold, per slot
     int clip_ws_cap = 0;                 // ... and the shared workspace
-    cf *d_clipx[2] = {};                 // [flight slot]: clipped blocks [clip_cap][N] -- what the transforms and part 2 read
-    int *d_clipi[2] = {}, *d_cliph[2] = {};   // ... their indices [clip_cap][N] and heads [clip_cap][CLIP_HEAD]
-    int32_t *h_cliph[2] = {};            // page-locked copies of the heads (read back with the flight)
-    float *d_clips = nullptr;            // leaf sums of the two rounds [2][clip_ws_cap][N / 128] and thresholds [clip_ws_cap][2]
-    int *d_clipw = nullptr;              // per-wave counts and tail flags [2][clip_ws_cap][N / 1024]
-    ClipTail *d_ctail = nullptr;         // the last clipped block's tail (stable address: captured graphs hold it)
+    DevBuf<cf> d_clipx[2];               // [flight slot]: clipped blocks [clip_cap][N] -- what the transforms and part 2 read
+    DevBuf<int> d_clipi[2], d_cliph[2];  // ... their indices [clip_cap][N] and heads [clip_cap][CLIP_HEAD]
+    HostBuf<int32_t> h_cliph[2];         // page-locked copies of the heads (read back with the flight)
+    DevBuf<float> d_clips;               // leaf sums of the two rounds [2][clip_ws_cap][N / 128] and thresholds [clip_ws_cap][2]
+    DevBuf<int> d_clipw;                 // per-wave counts and tail flags [2][clip_ws_cap][N / 1024]
+    DevBuf<ClipTail> d_ctail;            // the last clipped block's tail (stable address: captured graphs hold it)
     int ctail_cap = 0;
     // integer IQ samples in the page-locked inputs (unpack_kernels.hpp, mfb_set_sample_format): the raw bytes land in a staging
     // buffer of the input's own and k_unpack writes complex64 into the device copy everything else reads
     int fmt = MFB_SAMPLES_CF32;
     float fmt_scale = 1.f;
-    void *d_raw[4] = {};                 // [input buffer 0 / 1, window 0 / 1]: allocated at the first copy that needs it
+    DevBuf<void> d_raw[4];               // [input buffer 0 / 1, window 0 / 1]: allocated at the first copy that needs it
     size_t raw_cap[4] = {};
 };
 
@@ -238,6 +244,15 @@ struct mfb_ctx {
             return (e_ == hipErrorOutOfMemory) ? MFB_ERR_ALLOC : MFB_ERR_HIP;               \
         }                                                                                    \
     } while (0)
+
+// The one device check: `device` exists (and is below `limit`, where per-device tables are indexed by it) and is now the current one.
+static int device_ok(int device, int limit = INT_MAX) {
+    int ndev = 0;
+    HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev || device >= limit) return MFB_ERR_ARG;
+    HIPCHK(hipSetDevice(device));
+    return MFB_OK;
+}
 
 // the handle's stream and -- when a batch has put work there since the last wait -- the second stream of the batch path
 static hipError_t sync_streams(mfb_ctx *c) {
@@ -332,8 +347,8 @@ static void append_fused_tables(std::vector<cf> &v, int L) {
     }
 }
 
-static int upload_tw(cf **dst, const std::vector<cf> &v) {
-    HIPCHK(dev_alloc((void **)dst, v.size() * sizeof(cf)));
+static int upload_tw(DevBuf<cf> *dst, const std::vector<cf> &v) {
+    HIPCHK(dst->alloc(v.size() * sizeof(cf), dev_alloc));
     HIPCHK(hipMemcpy(*dst, v.data(), v.size() * sizeof(cf), hipMemcpyHostToDevice));
     return MFB_OK;
 }
@@ -360,6 +375,23 @@ static int default_chunk(const mfb_ctx *c) {
     return (int)ch;
 }
 
+// The bookkeeping half of every grow-only reserve of a handle, for one buffer or a group that shares a capacity: free all of them,
+// then allocate all of them (dev_alloc).  The capacity is 0 -- and whatever is missing empty -- until all of the group exist again.
+// The policy half stays with the caller, BEFORE the call: which streams to wait for, and whether recorded graphs die (epoch,
+// graph_drop).  A hipFree that fails is reported (MFB_ERR_HIP), as it always was on these paths; only teardown ignores it.
+struct GrowBuf {
+    Mem<DevFree> *buf;
+    size_t bytes;
+};
+template <class Cap>
+static int grow_buffers(Cap *cap, Cap want, std::initializer_list<GrowBuf> bufs) {
+    *cap = 0;
+    for (const GrowBuf &b : bufs) HIPCHK(b.buf->reset());
+    for (const GrowBuf &b : bufs) HIPCHK(b.buf->alloc(b.bytes, dev_alloc));
+    *cap = want;
+    return MFB_OK;
+}
+
 // Intermediate of the two-pass transforms.  The segment path needs one row only (the plain forward
 // transforms of A3 / A10 still run two-pass); the two-pass search needs chunk * MU rows.
 static size_t z_rows_needed(const mfb_ctx *c) {
@@ -371,15 +403,8 @@ static size_t z_rows_needed(const mfb_ctx *c) {
 static int alloc_Z(mfb_ctx *c) {
     const size_t need = z_rows_needed(c);
     if (c->d_Z && c->z_rows >= need) return MFB_OK;
-    if (c->d_Z) {
-        HIPCHK(sync_streams(c));
-        HIPCHK(hipFree(c->d_Z));
-        c->d_Z = nullptr;
-        c->z_rows = 0;
-    }
-    HIPCHK(dev_alloc((void **)&c->d_Z, need * c->N * sizeof(cf)));
-    c->z_rows = need;
-    return MFB_OK;
+    if (c->d_Z) HIPCHK(sync_streams(c));
+    return grow_buffers(&c->z_rows, need, {{&c->d_Z, need * c->N * sizeof(cf)}});
 }
 
 static int reserve_partials(mfb_ctx *c, size_t floats) {
@@ -387,13 +412,8 @@ static int reserve_partials(mfb_ctx *c, size_t floats) {
     if (c->d_part) {
         HIPCHK(sync_streams(c));
         ++c->epoch;          // recorded block graphs hold the old address
-        HIPCHK(hipFree(c->d_part));
-        c->d_part = nullptr;
-        c->part_cap = 0;
     }
-    HIPCHK(dev_alloc((void **)&c->d_part, floats * sizeof(float)));
-    c->part_cap = floats;
-    return MFB_OK;
+    return grow_buffers(&c->part_cap, floats, {{&c->d_part, floats * sizeof(float)}});
 }
 
 // Device-side result record of a block: [BlockScalars, 256 B][bands 2 x bcap complex64][sym][cen][mag] (nthreads each),
@@ -408,18 +428,13 @@ static RecordLayout rec_layout(int bcap, int nthreads, bool stages = false) {
 static int blkout_reserve(mfb_ctx *c, int bcap) {
     if (c->d_blkout && bcap <= c->band_cap) return MFB_OK;
     HIPCHK(sync_streams(c));
-    if (c->d_blkout) {
-        ++c->epoch;          // captured block graphs hold the old record's address (and d_scal): none of them may replay
-        HIPCHK(hipFree(c->d_blkout));
-    }
-    c->d_blkout = nullptr;
+    if (c->d_blkout) ++c->epoch;       // captured block graphs hold the old record's address (and d_scal): none of them may replay
     c->band_cap = 0;
-    HIPCHK(dev_alloc((void **)&c->d_blkout, rec_layout(bcap, c->cap).bytes));
-    if (c->d_blkout2) HIPCHK(hipFree(c->d_blkout2));
-    c->d_blkout2 = nullptr;
-    HIPCHK(dev_alloc((void **)&c->d_blkout2, rec_layout(bcap, c->cap).bytes));        // flight slot 1 (two streams: mfb_set_batch_overlap)
+    const size_t bytes = rec_layout(bcap, c->cap).bytes;
+    HIPCHK(c->d_blkout.alloc(bytes, dev_alloc));
+    HIPCHK(c->d_blkout2.alloc(bytes, dev_alloc));        // flight slot 1 (two streams: mfb_set_batch_overlap)
     c->band_cap = bcap;
-    c->d_scal = (BlockScalars *)c->d_blkout;
+    c->d_scal = (BlockScalars *)c->d_blkout.get();
     return MFB_OK;
 }
 
@@ -523,40 +538,40 @@ static int set_kernel_attributes(const mfb_ctx *c) {
 #undef MFB_MAX_LDS
 
 static int create_impl(mfb_ctx *c) {
-    HIPCHK(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
+    HIPCHK(hipStreamCreateWithFlags(out(c->own_stream), hipStreamNonBlocking));
     c->stream = c->own_stream;
-    HIPCHK(hipEventCreate(&c->t0));
-    HIPCHK(hipEventCreate(&c->t1));
+    HIPCHK(hipEventCreate(out(c->t0)));
+    HIPCHK(hipEventCreate(out(c->t1)));
     int rc = set_kernel_attributes(c);
     if (rc) return rc;
     const int M = c->M;
     const size_t nb = (size_t)c->N * sizeof(cf);
-    HIPCHK(hipHostMalloc((void **)&c->h_in, nb, hipHostMallocDefault));
+    HIPCHK(c->h_in.alloc(nb, hip_host_malloc));
     memset(c->h_in, 0, nb);
     // three arrays of at most N/2 symbol decisions, the block scalars and the two SNR windows of mfb_receive_block
     c->back_cap = (size_t)3 * (c->N / 2) * sizeof(int) + ((size_t)256 << 10);
     if (c->back_cap < ((size_t)64 << 10)) c->back_cap = (size_t)64 << 10;
-    HIPCHK(hipHostMalloc((void **)&c->h_back, c->back_cap, hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void **)&c->h_pick, 2 * sizeof(float), hipHostMallocDefault));
+    HIPCHK(c->h_back.alloc(c->back_cap, hip_host_malloc));
+    HIPCHK(c->h_pick.alloc(2 * sizeof(float), hip_host_malloc));
     HIPCHK(hipHostGetDevicePointer((void **)&c->h_pick_dev, c->h_pick, 0));
-    HIPCHK(dev_alloc((void **)&c->d_x, nb));
-    HIPCHK(dev_alloc((void **)&c->d_X, nb));
-    HIPCHK(dev_alloc((void **)&c->d_masks, nb * M));
-    HIPCHK(dev_alloc((void **)&c->d_xc, nb * M));
-    HIPCHK(dev_alloc((void **)&c->d_P, nb));
-    HIPCHK(dev_alloc((void **)&c->d_env, (size_t)c->N * sizeof(float)));
-    HIPCHK(dev_alloc((void **)&c->d_shifts, (size_t)c->Dtot * sizeof(int)));
+    HIPCHK(c->d_x.alloc(nb, dev_alloc));
+    HIPCHK(c->d_X.alloc(nb, dev_alloc));
+    HIPCHK(c->d_masks.alloc(nb * M, dev_alloc));
+    HIPCHK(c->d_xc.alloc(nb * M, dev_alloc));
+    HIPCHK(c->d_P.alloc(nb, dev_alloc));
+    HIPCHK(c->d_env.alloc((size_t)c->N * sizeof(float), dev_alloc));
+    HIPCHK(c->d_shifts.alloc((size_t)c->Dtot * sizeof(int), dev_alloc));
     if ((rc = reserve_partials(c, (size_t)c->Dtot * M * c->N1))) return rc;
-    HIPCHK(dev_alloc((void **)&c->d_sum, (size_t)c->Dtot * M * sizeof(float)));
+    HIPCHK(c->d_sum.alloc((size_t)c->Dtot * M * sizeof(float), dev_alloc));
     HIPCHK(hipMemset(c->d_sum, 0, (size_t)c->Dtot * M * sizeof(float)));
-    HIPCHK(dev_alloc((void **)&c->d_res, 2 * sizeof(float)));
-    HIPCHK(dev_alloc((void **)&c->d_uniq, (size_t)M * sizeof(int)));
-    HIPCHK(dev_alloc((void **)&c->d_rep, (size_t)M * sizeof(int)));
-    HIPCHK(dev_alloc((void **)&c->d_cr, 3 * sizeof(float)));
+    HIPCHK(c->d_res.alloc(2 * sizeof(float), dev_alloc));
+    HIPCHK(c->d_uniq.alloc((size_t)M * sizeof(int), dev_alloc));
+    HIPCHK(c->d_rep.alloc((size_t)M * sizeof(int), dev_alloc));
+    HIPCHK(c->d_cr.alloc(3 * sizeof(float), dev_alloc));
     c->cap = c->N / 2;  // symbols never shorter than 2 samples
-    HIPCHK(dev_alloc((void **)&c->d_sym, (size_t)c->cap * sizeof(int)));
-    HIPCHK(dev_alloc((void **)&c->d_cen, (size_t)c->cap * sizeof(int)));
-    HIPCHK(dev_alloc((void **)&c->d_mag, (size_t)c->cap * sizeof(float)));
+    HIPCHK(c->d_sym.alloc((size_t)c->cap * sizeof(int), dev_alloc));
+    HIPCHK(c->d_cen.alloc((size_t)c->cap * sizeof(int), dev_alloc));
+    HIPCHK(c->d_mag.alloc((size_t)c->cap * sizeof(float), dev_alloc));
     // one row for the plain forward transforms; the search's share is sized when the filters arrive
     if ((rc = alloc_Z(c))) return rc;
     // block path (mfb_receive_block*): everything it needs exists before the first block -- page-locking memory and creating
@@ -565,8 +580,8 @@ static int create_impl(mfb_ctx *c) {
     for (int i = 0; i < 2; ++i) {
         // scalars + three arrays of the symbols a rate window of +-10 % around 4 samples per symbol admits + the two windows
         c->blk_cap[i] = rec_layout(c->band_cap, c->N / 3).bytes;
-        HIPCHK(hipHostMalloc((void **)&c->h_blk[i], c->blk_cap[i], hipHostMallocDefault));
-        HIPCHK(hipEventCreateWithFlags(&c->ev_blk[i], hipEventDisableTiming));
+        HIPCHK(c->h_blk[i].alloc(c->blk_cap[i], hip_host_malloc));
+        HIPCHK(hipEventCreateWithFlags(out(c->ev_blk[i]), hipEventDisableTiming));
     }
 
     std::vector<cf> t;
@@ -582,6 +597,9 @@ static int create_impl(mfb_ctx *c) {
     return MFB_OK;
 }
 
+struct CtxDestroy {
+    void operator()(mfb_ctx *c) const { (void)mfb_destroy(c); }
+};
 static int create_body(mfb_ctx **out, int device, int log2N, int num_dopplers, int doppler_offset, int M,
                        int window_width, int sum_all_masks, int code_search_mask_offset) {
     if (!out) return MFB_ERR_ARG;
@@ -590,15 +608,14 @@ static int create_body(mfb_ctx **out, int device, int log2N, int num_dopplers, i
         code_search_mask_offset < 0 || 2 * code_search_mask_offset >= M)
         return MFB_ERR_ARG;
     if (log2N < 10 || log2N > 22) return MFB_ERR_UNSUPPORTED;
-    int ndev = 0;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return MFB_ERR_ARG;
-    HIPCHK(hipSetDevice(device));
+    int rc = device_ok(device);
+    if (rc) return rc;
     int ncu = 0;
     HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
 
-    mfb_ctx *c = new mfb_ctx();
-    memset((void *)c, 0, offsetof(mfb_ctx, ev));  // everything before the vectors
+    // any failure below -- a status or an exception -- frees what was allocated so far (mfb_destroy tolerates partial handles):
+    // the counterpart of the reference's context teardown, demodulator_base.py:517-530
+    std::unique_ptr<mfb_ctx, CtxDestroy> c(new mfb_ctx());
     c->device = device;
     c->num_cus = ncu > 0 ? ncu : 256;
     c->log2N = log2N;
@@ -626,27 +643,14 @@ static int create_body(mfb_ctx **out, int device, int log2N, int num_dopplers, i
     // Cache (chunk 1-2) does not pay: the cache streams no faster than HBM (tools/ubench/mall.hip).
     c->MU = M;
     c->chunk_auto = true;
-    c->chunk = default_chunk(c);
+    c->chunk = default_chunk(c.get());
     c->mpb = M < 8 ? M : 8;
     c->jsplit = 32;
-    set_rows_per_block(c, 64);
+    set_rows_per_block(c.get(), 64);
     c->path_req = MFB_PATH_AUTO;
     c->path = MFB_PATH_TWOPASS;
-
-    // any failure below frees what was allocated so far (mfb_destroy tolerates partial handles):
-    // the counterpart of the reference's context teardown, demodulator_base.py:517-530
-    int rc;
-    try {
-        rc = create_impl(c);
-    } catch (...) {
-        (void)mfb_destroy(c);
-        throw;
-    }
-    if (rc) {
-        (void)mfb_destroy(c);
-        return rc;
-    }
-    *out = c;
+    if ((rc = create_impl(c.get()))) return rc;
+    *out = c.release();
     return MFB_OK;
 }
 extern "C" int mfb_create(mfb_ctx **out, int device, int log2N, int num_dopplers, int doppler_offset, int M,
@@ -677,65 +681,8 @@ extern "C" int mfb_destroy(mfb_ctx *c) {
     if (c->s2) (void)hipStreamSynchronize(c->s2);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     if (c->in_stream) (void)hipStreamSynchronize(c->in_stream);
-    void *bufs[] = {c->d_uniq, c->d_rep, c->d_x,  c->d_X,    c->d_masks, c->d_Z,   c->d_xc,  c->d_P,   c->d_env, c->d_shifts, c->d_tw1,
-                    c->d_tw2, c->d_twLo, c->d_twHi,  c->d_part, c->d_sum, c->d_res, c->d_cr,  c->d_sym,    c->d_cen, c->d_mag,
-                    c->d_G, c->d_twL, c->d_Gb, c->d_pow, c->d_W, c->d_blkout, c->d_blkout2, c->d_x2,
-                    c->d_win[0], c->d_win[1], c->d_Xb, c->d_xcb, c->d_Pb, c->d_envb, c->d_sumb, c->d_resb, c->d_crb, c->d_batout, c->d_batout2, c->d_Z2,
-                    c->d_lut8, c->d_lut3, c->d_sttmpl, c->d_carry[0], c->d_carry[1]};
-    for (void *p : bufs)
-        if (p) (void)hipFree(p);
-    if (c->h_in) (void)hipHostFree(c->h_in);
-    if (c->h_in2) (void)hipHostFree(c->h_in2);
-    for (int i = 0; i < 2; ++i) {
-        if (c->h_win[i]) (void)hipHostFree(c->h_win[i]);
-        if (c->ev_wh2d[i]) (void)hipEventDestroy(c->ev_wh2d[i]);
-        if (c->ev_wfree[i]) (void)hipEventDestroy(c->ev_wfree[i]);
-    }
     for_each_graph(c, -1, graph_drop);
-    for (int i = 0; i < 2; ++i) {
-        if (c->h_blk[i]) (void)hipHostFree(c->h_blk[i]);
-        if (c->ev_blk[i]) (void)hipEventDestroy(c->ev_blk[i]);
-        if (c->ev_p1[i]) (void)hipEventDestroy(c->ev_p1[i]);
-    }
-    if (c->s2) (void)hipStreamDestroy(c->s2);
-    if (c->h_back) (void)hipHostFree(c->h_back);
-    if (c->h_pick) (void)hipHostFree(c->h_pick);
-    if (c->h_seed) (void)hipHostFree(c->h_seed);
-    if (c->h_X) (void)hipHostFree(c->h_X);
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    if (c->in_stream) {
-        (void)hipStreamSynchronize(c->in_stream);
-        (void)hipStreamDestroy(c->in_stream);
-    }
-    for (int i = 0; i < 2; ++i) {
-        if (c->ev_h2d[i]) (void)hipEventDestroy(c->ev_h2d[i]);
-        if (c->ev_xfree[i]) (void)hipEventDestroy(c->ev_xfree[i]);
-    }
-    if (c->ev_fft) (void)hipEventDestroy(c->ev_fft);
-    if (c->ev_X) (void)hipEventDestroy(c->ev_X);
-    for (auto &v : c->ev)
-        for (auto e : v) (void)hipEventDestroy(e);
-    for (auto e : c->ev_pool) (void)hipEventDestroy(e);
-    if (c->t0) (void)hipEventDestroy(c->t0);
-    if (c->t1) (void)hipEventDestroy(c->t1);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    if (c->d_Gs) (void)hipFree(c->d_Gs);
-    if (c->d_Qs) (void)hipFree(c->d_Qs);
-    if (c->d_Wb) (void)hipFree(c->d_Wb);
-    if (c->d_Wexp) (void)hipFree(c->d_Wexp);
-    for (int i = 0; i < 2; ++i) {
-        if (c->d_clipx[i]) (void)hipFree(c->d_clipx[i]);
-        if (c->d_clipi[i]) (void)hipFree(c->d_clipi[i]);
-        if (c->d_cliph[i]) (void)hipFree(c->d_cliph[i]);
-        if (c->h_cliph[i]) (void)hipHostFree(c->h_cliph[i]);
-    }
-    if (c->d_clips) (void)hipFree(c->d_clips);
-    if (c->d_clipw) (void)hipFree(c->d_clipw);
-    if (c->d_ctail) (void)hipFree(c->d_ctail);
-    for (void *p : c->d_raw)
-        if (p) (void)hipFree(p);
-    delete c->bank;
-    delete c;
+    delete c;       // ~mfb_ctx: every buffer and event, then the streams (see the struct)
     return MFB_OK;
 }
 
@@ -756,9 +703,9 @@ extern "C" int mfb_set_cu_share(mfb_ctx *c, int part, int parts) {
         if (c->flight[s].active) return MFB_ERR_STATE;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(sync_streams(c));
-    hipStream_t fresh = nullptr;
+    Stream fresh;
     if (parts == 1) {
-        HIPCHK(hipStreamCreateWithFlags(&fresh, hipStreamNonBlocking));
+        HIPCHK(hipStreamCreateWithFlags(out(fresh), hipStreamNonBlocking));
     } else {
         const int words = (c->num_cus + 31) / 32;
         std::vector<uint32_t> mask((size_t)words, 0u);
@@ -769,15 +716,15 @@ extern "C" int mfb_set_cu_share(mfb_ctx *c, int part, int parts) {
                 ++mine;
             }
         if (!mine) return MFB_ERR_ARG;
-        HIPCHK(hipExtStreamCreateWithCUMask(&fresh, (uint32_t)words, mask.data()));
+        HIPCHK(hipExtStreamCreateWithCUMask(out(fresh), (uint32_t)words, mask.data()));
     }
     const bool was_own = c->stream == c->own_stream;
-    if (c->own_stream) HIPCHK(hipStreamDestroy(c->own_stream));
-    c->own_stream = fresh;
-    if (was_own) c->stream = fresh;
+    std::swap(c->own_stream, fresh);
+    if (was_own) c->stream = c->own_stream;
     c->cu_part = part;
     c->cu_parts = parts;
     ++c->epoch;
+    HIPCHK(fresh.reset());        // (the old one; the handle is whole whatever this says)
     return MFB_OK;
 }
 
@@ -847,13 +794,9 @@ static int resolve_path(mfb_ctx *c) {
         if (c->segl != l || !c->d_G) {
             std::vector<float> G;
             taps::segment_spectra(*c->bank, L, sg.T, &G, seg_ppl(L));
-            if (c->d_G) HIPCHK(hipFree(c->d_G));
-            c->d_G = nullptr;
-            HIPCHK(dev_alloc((void **)&c->d_G, G.size() * sizeof(float)));
+            HIPCHK(c->d_G.alloc(G.size() * sizeof(float), dev_alloc));
             HIPCHK(hipMemcpy(c->d_G, G.data(), G.size() * sizeof(float), hipMemcpyHostToDevice));
             if (c->twL_len != L) {
-                if (c->d_twL) HIPCHK(hipFree(c->d_twL));
-                c->d_twL = nullptr;
                 c->twL_len = 0;
                 std::vector<cf> t;
                 make_twiddles(t, L, (double)L, 1.0);
@@ -870,11 +813,10 @@ static int resolve_path(mfb_ctx *c) {
                 c->MB = taps::span_basis(*c->bank, &sb);
                 std::vector<float> G;
                 if (c->MB > 0) taps::segment_spectra(sb, L, sg.T, &G, seg_ppl(L));
-                if (c->d_Gb) HIPCHK(hipFree(c->d_Gb));
-                c->d_Gb = nullptr;
+                HIPCHK(c->d_Gb.reset());
                 c->gb_l = 0;
                 if (c->MB > 0) {
-                    HIPCHK(dev_alloc((void **)&c->d_Gb, G.size() * sizeof(float)));
+                    HIPCHK(c->d_Gb.alloc(G.size() * sizeof(float), dev_alloc));
                     HIPCHK(hipMemcpy(c->d_Gb, G.data(), G.size() * sizeof(float), hipMemcpyHostToDevice));
                     c->gb_l = l;
                 }
@@ -894,9 +836,8 @@ static int resolve_path(mfb_ctx *c) {
         int rc = reserve_partials(c, (size_t)c->Dtot * c->M * c->N1);
         if (rc) return rc;
     } else if (c->d_Z && c->z_rows > 1) {   // give the big intermediate back
-        HIPCHK(hipFree(c->d_Z));
-        c->d_Z = nullptr;
         c->z_rows = 0;
+        HIPCHK(c->d_Z.reset());
     }
     int rc = alloc_Z(c);
     if (rc) return rc;
@@ -1029,8 +970,8 @@ static int set_filters_body(mfb_ctx *c, const float *masks, int M, int N) {
     HIPCHK(hipMemcpyAsync(c->d_uniq, uniq.data(), uniq.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->d_rep, rep.data(), (size_t)M * sizeof(int), hipMemcpyHostToDevice, c->stream));
     // impulse-response window and taps of every filter (double precision, host threads)
-    if (!c->bank) c->bank = new taps::Bank();
-    taps::analyse(masks, M, N, c->bank);
+    if (!c->bank) c->bank.reset(new taps::Bank());
+    taps::analyse(masks, M, N, c->bank.get());
     HIPCHK(sync_streams(c));
     c->have_filters = true;
     c->have_xc = false;
@@ -1079,38 +1020,38 @@ extern "C" int mfb_set_shifts(mfb_ctx *c, const int32_t *shifts, int count) {
 extern "C" int mfb_input_buffer(mfb_ctx *c, float **p) {
     if (!c || !p) return MFB_ERR_ARG;
     if (c->fmt != MFB_SAMPLES_CF32) return MFB_ERR_STATE;      // the buffer holds integers: mfb_input_buffer_raw
-    *p = (float *)c->h_in;
+    *p = (float *)c->h_in.get();
     return MFB_OK;
 }
 
 // ---- launch helpers ------------------------------------------------------------------------------
 static int fin_threads(int rows) { return 64 * (rows < 1 ? 1 : (rows > 16 ? 16 : rows)); }   // k_finalize: one wave per row
-static hipEvent_t get_event(mfb_ctx *c) {
+static Event get_event(mfb_ctx *c) {
+    Event e;
     if (!c->ev_pool.empty()) {
-        hipEvent_t e = c->ev_pool.back();
+        e = std::move(c->ev_pool.back());
         c->ev_pool.pop_back();
-        return e;
+    } else {
+        (void)hipEventCreate(out(e));      // (empty when that fails)
     }
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
     return e;
 }
 // Profiling marks come in pairs (begin, end); a mark that cannot be created or recorded switches profiling off and drops
 // the marks taken so far, so that mfb_profile_read never pairs events of different launches.
 static void prof_mark(mfb_ctx *c, int which) {
     if (!c->prof) return;
-    hipEvent_t e = get_event(c);
+    Event e = get_event(c);
     if (!e || hipEventRecord(e, c->stream) != hipSuccess) {
         fprintf(stderr, "mfbank: profiling event unavailable, profiling disabled\n");
-        if (e) c->ev_pool.push_back(e);
+        if (e) c->ev_pool.push_back(std::move(e));
         for (auto &v : c->ev) {
-            for (auto q : v) c->ev_pool.push_back(q);
+            for (auto &q : v) c->ev_pool.push_back(std::move(q));
             v.clear();
         }
         c->prof = false;
         return;
     }
-    c->ev[which].push_back(e);
+    c->ev[which].push_back(std::move(e));
 }
 
 template <int L1, int KIND>
@@ -1282,10 +1223,10 @@ static int after_fft(mfb_ctx *c) {
 }
 static int enable_mirror(mfb_ctx *c) {
     if (c->mirror || c->N > MIRROR_MAX_N) return MFB_OK;
-    if (!c->h_X) HIPCHK(hipHostMalloc((void **)&c->h_X, (size_t)c->N * sizeof(cf), hipHostMallocDefault));
-    if (!c->copy_stream) HIPCHK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    if (!c->ev_fft) HIPCHK(hipEventCreateWithFlags(&c->ev_fft, hipEventDisableTiming));
-    if (!c->ev_X) HIPCHK(hipEventCreateWithFlags(&c->ev_X, hipEventDisableTiming));
+    if (!c->h_X) HIPCHK(c->h_X.alloc((size_t)c->N * sizeof(cf), hip_host_malloc));
+    if (!c->copy_stream) HIPCHK(hipStreamCreateWithFlags(out(c->copy_stream), hipStreamNonBlocking));
+    if (!c->ev_fft) HIPCHK(hipEventCreateWithFlags(out(c->ev_fft), hipEventDisableTiming));
+    if (!c->ev_X) HIPCHK(hipEventCreateWithFlags(out(c->ev_X), hipEventDisableTiming));
     c->mirror = true;
     return MFB_OK;
 }
@@ -1317,12 +1258,9 @@ static int raw_copy_unpack(mfb_ctx *c, const void *src, cf *dst, size_t samples,
         if (c->d_raw[rawslot]) {
             HIPCHK(sync_streams(c));
             if (c->in_stream) HIPCHK(hipStreamSynchronize(c->in_stream));
-            HIPCHK(hipFree(c->d_raw[rawslot]));
-            c->d_raw[rawslot] = nullptr;
-            c->raw_cap[rawslot] = 0;
         }
-        HIPCHK(dev_alloc(&c->d_raw[rawslot], need));
-        c->raw_cap[rawslot] = need;
+        const int rc = grow_buffers(&c->raw_cap[rawslot], need, {{&c->d_raw[rawslot], need}});
+        if (rc) return rc;
     }
     HIPCHK(hipMemcpyAsync(c->d_raw[rawslot], src, bytes, hipMemcpyHostToDevice, s));
     return launch_unpack(c->fmt, c->d_raw[rawslot], dst, samples, c->fmt_scale, s);
@@ -1399,26 +1337,22 @@ static int fsm_prepare(mfb_ctx *c, const SearchPlan &plan) {
         if (wkt) taps::wrap_taps_shifted(*c->bank, c->h_uniq.data(), rows, c->h_shifts.data(), c->Dtot, wkt, &W, &Wexp);
     }
     HIPCHK(sync_streams(c));
-    if (c->d_Gs) HIPCHK(hipFree(c->d_Gs));
-    c->d_Gs = nullptr;
     c->gs_rows = 0;
-    if (c->d_Qs) HIPCHK(hipFree(c->d_Qs));
-    c->d_Qs = nullptr;
-    if (c->d_Wb) HIPCHK(hipFree(c->d_Wb));
-    c->d_Wb = nullptr;
-    if (c->d_Wexp) HIPCHK(hipFree(c->d_Wexp));
-    c->d_Wexp = nullptr;
     c->wb_kt = 0;
-    HIPCHK(dev_alloc((void **)&c->d_Gs, G.size() * sizeof(float)));
+    HIPCHK(c->d_Gs.reset());
+    HIPCHK(c->d_Qs.reset());
+    HIPCHK(c->d_Wb.reset());
+    HIPCHK(c->d_Wexp.reset());
+    HIPCHK(c->d_Gs.alloc(G.size() * sizeof(float), dev_alloc));
     HIPCHK(hipMemcpy(c->d_Gs, G.data(), G.size() * sizeof(float), hipMemcpyHostToDevice));
     if (q) {
-        HIPCHK(dev_alloc((void **)&c->d_Qs, Q.size() * sizeof(float)));
+        HIPCHK(c->d_Qs.alloc(Q.size() * sizeof(float), dev_alloc));
         HIPCHK(hipMemcpy(c->d_Qs, Q.data(), Q.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     if (wkt) {
-        HIPCHK(dev_alloc((void **)&c->d_Wb, W.size() * sizeof(uint16_t)));
+        HIPCHK(c->d_Wb.alloc(W.size() * sizeof(uint16_t), dev_alloc));
         HIPCHK(hipMemcpy(c->d_Wb, W.data(), W.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        HIPCHK(dev_alloc((void **)&c->d_Wexp, Wexp.size() * sizeof(int)));
+        HIPCHK(c->d_Wexp.alloc(Wexp.size() * sizeof(int), dev_alloc));
         HIPCHK(hipMemcpy(c->d_Wexp, Wexp.data(), Wexp.size() * sizeof(int), hipMemcpyHostToDevice));
         c->wb_kt = wkt;
     }
@@ -1535,8 +1469,8 @@ extern "C" int mfb_search_async(mfb_ctx *c) {
         const int parts = c->N / EN_CHUNK;
         int rc = reserve_partials(c, (size_t)c->Dtot * R * parts);
         if (rc) return rc;
-        if (!c->d_pow) HIPCHK(dev_alloc((void **)&c->d_pow, (size_t)c->N * sizeof(float)));
-        if (!c->d_W) HIPCHK(dev_alloc((void **)&c->d_W, (size_t)c->N * (c->sum_all ? 1 : c->M) * sizeof(float)));
+        if (!c->d_pow) HIPCHK(c->d_pow.alloc((size_t)c->N * sizeof(float), dev_alloc));
+        if (!c->d_W) HIPCHK(c->d_W.alloc((size_t)c->N * (c->sum_all ? 1 : c->M) * sizeof(float), dev_alloc));
         if (!c->W_valid) {
             hipLaunchKernelGGL(k_filter_energy, dim3(c->N / 256, R), dim3(256), 0, c->stream, (const cf *)c->d_masks, c->d_W, c->N, c->M,
                                c->sum_all);
@@ -1893,45 +1827,28 @@ static int clip_reserve(mfb_ctx *c, int slot, int nb) {
     if (nb > c->clip_cap[slot]) {
         HIPCHK(sync_streams(c));
         ++c->epoch;
-        if (c->d_clipx[slot]) HIPCHK(hipFree(c->d_clipx[slot]));
-        if (c->d_clipi[slot]) HIPCHK(hipFree(c->d_clipi[slot]));
-        if (c->d_cliph[slot]) HIPCHK(hipFree(c->d_cliph[slot]));
-        if (c->h_cliph[slot]) HIPCHK(hipHostFree(c->h_cliph[slot]));
-        c->d_clipx[slot] = nullptr;
-        c->d_clipi[slot] = c->d_cliph[slot] = nullptr;
-        c->h_cliph[slot] = nullptr;
-        c->clip_cap[slot] = 0;
-        const size_t nbN = (size_t)nb * c->N;
-        HIPCHK(dev_alloc((void **)&c->d_clipx[slot], nbN * sizeof(cf)));
-        HIPCHK(dev_alloc((void **)&c->d_clipi[slot], nbN * sizeof(int)));
-        HIPCHK(dev_alloc((void **)&c->d_cliph[slot], (size_t)nb * CLIP_HEAD * sizeof(int)));
-        HIPCHK(hipHostMalloc((void **)&c->h_cliph[slot], (size_t)nb * CLIP_HEAD * sizeof(int), hipHostMallocDefault));
-        memset(c->h_cliph[slot], 0, (size_t)nb * CLIP_HEAD * sizeof(int));
-        c->clip_cap[slot] = nb;
+        const size_t nbN = (size_t)nb * c->N, heads = (size_t)nb * CLIP_HEAD * sizeof(int);
+        const int rc = grow_buffers(&c->clip_cap[slot], 0, {{&c->d_clipx[slot], nbN * sizeof(cf)}, {&c->d_clipi[slot], nbN * sizeof(int)}, {&c->d_cliph[slot], heads}});
+        if (rc) return rc;
+        HIPCHK(c->h_cliph[slot].alloc(heads, hip_host_malloc));
+        memset(c->h_cliph[slot], 0, heads);
+        c->clip_cap[slot] = nb;        // (device and host side exist)
     }
     if (nb > c->clip_ws_cap) {       // part 1 only, on the handle's stream: nothing in flight reads it after the wait
         HIPCHK(sync_streams(c));
         ++c->epoch;
-        if (c->d_clips) HIPCHK(hipFree(c->d_clips));
-        if (c->d_clipw) HIPCHK(hipFree(c->d_clipw));
-        c->d_clips = nullptr;
-        c->d_clipw = nullptr;
-        c->clip_ws_cap = 0;
         const size_t nbN = (size_t)nb * c->N;
-        HIPCHK(dev_alloc((void **)&c->d_clips, (2 * nbN / CLIP_LEAF + 2 * (size_t)nb) * sizeof(float)));
-        HIPCHK(dev_alloc((void **)&c->d_clipw, 2 * nbN / CLIP_WAVE * sizeof(int)));
-        c->clip_ws_cap = nb;
+        const int rc = grow_buffers(&c->clip_ws_cap, nb, {{&c->d_clips, (2 * nbN / CLIP_LEAF + 2 * (size_t)nb) * sizeof(float)}, {&c->d_clipw, 2 * nbN / CLIP_WAVE * sizeof(int)}});
+        if (rc) return rc;
     }
     if (c->clip_ov > c->ctail_cap) {
         HIPCHK(sync_streams(c));
         ++c->epoch;
-        if (c->d_ctail) HIPCHK(hipFree(c->d_ctail));
-        c->d_ctail = nullptr;
-        c->ctail_cap = 0;
         const size_t bytes = sizeof(ClipTail) + (size_t)c->clip_ov * sizeof(cf);
-        HIPCHK(dev_alloc((void **)&c->d_ctail, bytes));
+        const int rc = grow_buffers(&c->ctail_cap, 0, {{&c->d_ctail, bytes}});
+        if (rc) return rc;
         HIPCHK(hipMemset(c->d_ctail, 0, bytes));
-        c->ctail_cap = c->clip_ov;
+        c->ctail_cap = c->clip_ov;     // (and cleared)
     }
     return MFB_OK;
 }
@@ -1944,7 +1861,7 @@ static int clip_prepare(mfb_ctx *c, int slot, const cf *raw, long long xstride, 
     const size_t nbN = (size_t)c->clip_ws_cap * c->N;
     a.x = (const float2 *)raw;
     a.xstride = xstride;
-    a.y = (float2 *)c->d_clipx[slot];
+    a.y = (float2 *)c->d_clipx[slot].get();
     a.idx = c->d_clipi[slot];
     a.head = c->d_cliph[slot];
     a.s1 = c->d_clips;
@@ -2138,13 +2055,13 @@ static int block_enqueue(mfb_ctx *c, const mfb_block_params *p, const BlkBufs &b
 // Under an integer sample format (mfb_set_sample_format) the raw bytes go to the input's staging buffer `rawslot` and k_unpack
 // writes the complex64 device copy right behind the copy, on the input stream too: whatever waits for the event reads what it
 // always read.  (Copy and unpack stay outside the recorded graphs, which begin behind that event.)
-static int input_copy(mfb_ctx *c, const cf *src, cf *dst, size_t samples, hipEvent_t *ev_h2d, hipEvent_t *ev_free, int which, int rawslot) {
+static int input_copy(mfb_ctx *c, const cf *src, cf *dst, size_t samples, Event *ev_h2d, Event *ev_free, int which, int rawslot) {
     if (!src || !dst) return MFB_ERR_STATE;
-    if (!c->in_stream) HIPCHK(hipStreamCreateWithFlags(&c->in_stream, hipStreamNonBlocking));
+    if (!c->in_stream) HIPCHK(hipStreamCreateWithFlags(out(c->in_stream), hipStreamNonBlocking));
     for (int i = 0; i < 2; ++i) {
-        if (!ev_h2d[i]) HIPCHK(hipEventCreateWithFlags(&ev_h2d[i], hipEventDisableTiming));
+        if (!ev_h2d[i]) HIPCHK(hipEventCreateWithFlags(out(ev_h2d[i]), hipEventDisableTiming));
         if (!ev_free[i]) {
-            HIPCHK(hipEventCreateWithFlags(&ev_free[i], hipEventDisableTiming));
+            HIPCHK(hipEventCreateWithFlags(out(ev_free[i]), hipEventDisableTiming));
             HIPCHK(hipEventRecord(ev_free[i], c->stream));
         }
     }
@@ -2247,11 +2164,7 @@ static int staging_reserve(mfb_ctx *c, int slot, size_t need) {
     if (need <= c->blk_cap[slot]) return MFB_OK;
     for_each_graph(c, slot, graph_drop);
     if (c->s2) HIPCHK(hipStreamSynchronize(c->s2));
-    if (c->h_blk[slot]) HIPCHK(hipHostFree(c->h_blk[slot]));
-    c->h_blk[slot] = nullptr;
-    c->blk_cap[slot] = 0;
-    HIPCHK(hipHostMalloc((void **)&c->h_blk[slot], need, hipHostMallocDefault));
-    c->blk_cap[slot] = need;
+    HIPCHK(reserve(c->h_blk[slot], c->blk_cap[slot], need, need, hip_host_malloc));
     return MFB_OK;
 }
 
@@ -2330,7 +2243,7 @@ static int block_begin(mfb_ctx *c, const mfb_block_params *p, int slot) {
     if ((rc = blkout_reserve(c, geo.bcap > c->band_cap ? geo.bcap : c->band_cap))) return rc;
     const RecordLayout lay = rec_layout(geo.bcap, geo.nthreads);
     if ((rc = staging_reserve(c, slot, lay.bytes))) return rc;
-    if (!c->ev_blk[slot]) HIPCHK(hipEventCreateWithFlags(&c->ev_blk[slot], hipEventDisableTiming));
+    if (!c->ev_blk[slot]) HIPCHK(hipEventCreateWithFlags(out(c->ev_blk[slot]), hipEventDisableTiming));
     const bool pinned_in = p->input == MFB_INPUT_PINNED || p->input == MFB_INPUT_PINNED2;
     const int which = p->input == MFB_INPUT_PINNED2 ? 1 : 0;
     if (pinned_in && (rc = block_input_copy(c, which))) return rc;
@@ -2353,7 +2266,7 @@ static int block_begin(mfb_ctx *c, const mfb_block_params *p, int slot) {
         if ((rc = second_stream(c, slot))) return rc;
         if (c->z2_rows < 1) {
             HIPCHK(sync_streams(c));
-            HIPCHK(dev_alloc((void **)&c->d_Z2, (size_t)c->N * sizeof(cf)));
+            HIPCHK(c->d_Z2.alloc((size_t)c->N * sizeof(cf), dev_alloc));
             c->z2_rows = 1;
         }
     }
@@ -2362,7 +2275,7 @@ static int block_begin(mfb_ctx *c, const mfb_block_params *p, int slot) {
     if (clip) bb.clip = &cl;
     // (ev_xfree: this device copy of the input may be overwritten once the block has read it)
     rc = flight_launch(c, c->bgraph[which][slot], c->bgraph2[which][slot], bb, p, geo, split ? -1 : 0, allowed, split, slot,
-                       pinned_in ? c->ev_xfree[which] : nullptr);
+                       pinned_in ? c->ev_xfree[which].get() : nullptr);
     if (rc) return rc;
     flight_fill(c, f, p, geo, lay, 0, clip);
     c->have_xc = true;
@@ -2467,9 +2380,9 @@ static int second_stream(mfb_ctx *c, int slot) {
         // (the highest priority: part 2 is a latency chain whose workgroups should get the slots the big kernel frees first)
         int least = 0, greatest = 0;
         HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIPCHK(hipStreamCreateWithPriority(&c->s2, hipStreamNonBlocking, greatest));
+        HIPCHK(hipStreamCreateWithPriority(out(c->s2), hipStreamNonBlocking, greatest));
     }
-    if (!c->ev_p1[slot]) HIPCHK(hipEventCreateWithFlags(&c->ev_p1[slot], hipEventDisableTiming));
+    if (!c->ev_p1[slot]) HIPCHK(hipEventCreateWithFlags(out(c->ev_p1[slot]), hipEventDisableTiming));
     return MFB_OK;
 }
 // A batch on two streams (mfb_set_batch_overlap; include/mfbank.h): the handle's setting, or -- every handle -- MFB_BATCH_SPLIT=0/1 in
@@ -2514,47 +2427,31 @@ extern "C" int mfb_get_block_snr(mfb_ctx *c, int slot, int block, float means[2]
     lens[1] = hs.band_len[1];
     return MFB_OK;
 }
-// Device buffers whose addresses recorded graphs hold grow as a group: wait for what uses them, drop the graphs (epoch), free, allocate.
-// The capacity is 0 -- and the pointers of whatever is missing null -- until all of the group exist again.
-struct GrowBuf {
-    void **p;
-    size_t bytes;
-};
-template <class Cap>
-static int grow_buffers(mfb_ctx *c, Cap *cap, Cap want, std::initializer_list<GrowBuf> bufs) {
-    HIPCHK(sync_streams(c));
-    ++c->epoch;
-    for (const GrowBuf &b : bufs) {
-        if (*b.p) HIPCHK(hipFree(*b.p));
-        *b.p = nullptr;
-    }
-    *cap = 0;
-    for (const GrowBuf &b : bufs) HIPCHK(dev_alloc(b.p, b.bytes));
-    *cap = want;
-    return MFB_OK;
-}
+// Device buffers of the batch path, whose addresses recorded graphs hold: each group waits for what uses it and drops the graphs (epoch)
 static int batch_reserve(mfb_ctx *c, int nb, size_t rec) {
     int rc;
     const size_t nbN = (size_t)nb * c->N;
+    auto grow = [c](auto *cap, auto want, std::initializer_list<GrowBuf> bufs) -> int {
+        HIPCHK(sync_streams(c));
+        ++c->epoch;
+        return grow_buffers(cap, want, bufs);
+    };
     if (nb > c->bat_cap &&
-        (rc = grow_buffers(c, &c->bat_cap, nb,
-                           {{(void **)&c->d_Xb, nbN * sizeof(cf)},
-                            {(void **)&c->d_xcb, nbN * c->M * sizeof(cf)},
-                            {(void **)&c->d_Pb, nbN * sizeof(cf)},
-                            {(void **)&c->d_envb, nbN * sizeof(float)},
-                            {(void **)&c->d_sumb, (size_t)nb * c->Dtot * c->M * sizeof(float)},
-                            {(void **)&c->d_resb, (size_t)nb * 2 * sizeof(float)},
-                            {(void **)&c->d_crb, (size_t)nb * 3 * sizeof(float)}})))
+        (rc = grow(&c->bat_cap, nb,
+                   {{&c->d_Xb, nbN * sizeof(cf)},
+                    {&c->d_xcb, nbN * c->M * sizeof(cf)},
+                    {&c->d_Pb, nbN * sizeof(cf)},
+                    {&c->d_envb, nbN * sizeof(float)},
+                    {&c->d_sumb, (size_t)nb * c->Dtot * c->M * sizeof(float)},
+                    {&c->d_resb, (size_t)nb * 2 * sizeof(float)},
+                    {&c->d_crb, (size_t)nb * 3 * sizeof(float)}})))
         return rc;
     // the plain forward transforms of the batch take one row of the intermediate each
-    if ((size_t)nb > c->z_rows && (rc = grow_buffers(c, &c->z_rows, (size_t)nb, {{(void **)&c->d_Z, nbN * sizeof(cf)}}))) return rc;
+    if ((size_t)nb > c->z_rows && (rc = grow(&c->z_rows, (size_t)nb, {{&c->d_Z, nbN * sizeof(cf)}}))) return rc;
     // the two flights' records (the next batch's search writes its picks while this one's records are still read)
-    if (rec * nb > c->batout_cap &&
-        (rc = grow_buffers(c, &c->batout_cap, rec * nb, {{(void **)&c->d_batout, rec * nb}, {(void **)&c->d_batout2, rec * nb}})))
-        return rc;
+    if (rec * nb > c->batout_cap && (rc = grow(&c->batout_cap, rec * nb, {{&c->d_batout, rec * nb}, {&c->d_batout2, rec * nb}}))) return rc;
     // part 2's transforms (the envelopes' spectra) get an intermediate of their own
-    if (batch_split(c) && (size_t)nb > c->z2_rows && (rc = grow_buffers(c, &c->z2_rows, (size_t)nb, {{(void **)&c->d_Z2, nbN * sizeof(cf)}})))
-        return rc;
+    if (batch_split(c) && (size_t)nb > c->z2_rows && (rc = grow(&c->z2_rows, (size_t)nb, {{&c->d_Z2, nbN * sizeof(cf)}}))) return rc;
     return MFB_OK;
 }
 
@@ -2569,22 +2466,19 @@ static int window_buffer(mfb_ctx *c, int which, int max_blocks, int block_stride
         if (c->in_stream) HIPCHK(hipStreamSynchronize(c->in_stream));
         ++c->epoch;
         for (int i = 0; i < 2; ++i) {
-            if (c->h_win[i]) HIPCHK(hipHostFree(c->h_win[i]));
-            if (c->d_win[i]) HIPCHK(hipFree(c->d_win[i]));
-            if (c->d_raw[2 + i]) HIPCHK(hipFree(c->d_raw[2 + i]));
-            c->h_win[i] = nullptr;
-            c->d_win[i] = nullptr;
-            c->d_raw[2 + i] = nullptr;
             c->raw_cap[2 + i] = 0;
+            HIPCHK(c->h_win[i].reset());
+            HIPCHK(c->d_win[i].reset());
+            HIPCHK(c->d_raw[2 + i].reset());
         }
         c->win_blocks = max_blocks;
         c->win_stride = block_stride;
     }
     if (!c->h_win[which]) {
         const size_t bytes = (size_t)window_samples(c, c->win_blocks) * sizeof(cf);
-        HIPCHK(hipHostMalloc((void **)&c->h_win[which], bytes, hipHostMallocDefault));
+        HIPCHK(c->h_win[which].alloc(bytes, hip_host_malloc));
         memset(c->h_win[which], 0, bytes);
-        HIPCHK(dev_alloc((void **)&c->d_win[which], bytes));
+        HIPCHK(c->d_win[which].alloc(bytes, dev_alloc));
     }
     *host_c64 = c->h_win[which];
     return MFB_OK;
@@ -2630,7 +2524,7 @@ extern "C" int mfb_receive_blocks_begin(mfb_ctx *c, const mfb_block_params *p, i
     const size_t rec = lay.bytes;
     if ((rc = batch_reserve(c, nblocks > c->win_blocks ? nblocks : (c->win_blocks > 0 ? c->win_blocks : nblocks), rec))) return rc;
     if ((rc = staging_reserve(c, slot, rec * nblocks))) return rc;
-    if (!c->ev_blk[slot]) HIPCHK(hipEventCreateWithFlags(&c->ev_blk[slot], hipEventDisableTiming));
+    if (!c->ev_blk[slot]) HIPCHK(hipEventCreateWithFlags(out(c->ev_blk[slot]), hipEventDisableTiming));
     if (win_in && (rc = input_copy(c, c->h_win[which], c->d_win[which], (size_t)(nblocks * stride + (c->N - stride)), c->ev_wh2d, c->ev_wfree, which, 2 + which)))
         return rc;
     const int parity = c->carry_cur;
@@ -2655,7 +2549,7 @@ extern "C" int mfb_receive_blocks_begin(mfb_ctx *c, const mfb_block_params *p, i
     const bool split = batch_split(c);
     if (split && (rc = second_stream(c, slot))) return rc;
     rc = flight_launch(c, c->wgraph[which][slot][parity][gi], c->wgraph2[which][slot][parity][gi], bb, &q, geo, nblocks, allowed, split, slot,
-                       win_in ? c->ev_wfree[which] : nullptr);
+                       win_in ? c->ev_wfree[which].get() : nullptr);
     if (rc) return rc;
     if (stages) c->carry_cur = 1 - parity;        // this batch's tail and ring are the next batch's start
     flight_fill(c, f, p, geo, lay, nblocks, clip);
@@ -2770,17 +2664,15 @@ extern "C" int mfb_set_stream_stages(mfb_ctx *c, const mfb_stream_params *p) {
     a.mode = p->lut_mode;
     a.rows = p->lut_rows;
     a.succ = p->lut_mode == 2 ? p->lut_successors : 0;
-    void **olds[] = {(void **)&c->d_lut8, (void **)&c->d_lut3, (void **)&c->d_sttmpl};
-    for (void **q : olds) {
-        if (*q) HIPCHK(hipFree(*q));
-        *q = nullptr;
-    }
+    HIPCHK(c->d_lut8.reset());
+    HIPCHK(c->d_lut3.reset());
+    HIPCHK(c->d_sttmpl.reset());
     if (a.mode == 1) {
-        HIPCHK(dev_alloc((void **)&c->d_lut8, (size_t)a.rows));
+        HIPCHK(c->d_lut8.alloc((size_t)a.rows, dev_alloc));
         HIPCHK(hipMemcpy(c->d_lut8, p->lut, (size_t)a.rows, hipMemcpyHostToDevice));
     } else {
         const size_t n = (size_t)a.rows * 2 * a.succ * sizeof(int);
-        HIPCHK(dev_alloc((void **)&c->d_lut3, n));
+        HIPCHK(c->d_lut3.alloc(n, dev_alloc));
         HIPCHK(hipMemcpy(c->d_lut3, p->lut, n, hipMemcpyHostToDevice));
     }
     a.lut8 = c->d_lut8;
@@ -2811,15 +2703,15 @@ extern "C" int mfb_set_stream_stages(mfb_ctx *c, const mfb_stream_params *p) {
         }
     }
     if (taps) {
-        HIPCHK(dev_alloc((void **)&c->d_sttmpl, taps));
+        HIPCHK(c->d_sttmpl.alloc(taps, dev_alloc));
         HIPCHK(hipMemcpy(c->d_sttmpl, p->templates, taps, hipMemcpyHostToDevice));
     }
     a.tmpls = c->d_sttmpl;
     for (int i = 0; i < 2; ++i) {
-        if (!c->d_carry[i]) HIPCHK(dev_alloc((void **)&c->d_carry[i], sizeof(StreamCarry)));
+        if (!c->d_carry[i]) HIPCHK(c->d_carry[i].alloc(sizeof(StreamCarry), dev_alloc));
         HIPCHK(hipMemset(c->d_carry[i], 0, sizeof(StreamCarry)));       // valid = 0: nothing known until mfb_stream_seed
     }
-    if (!c->h_seed) HIPCHK(hipHostMalloc((void **)&c->h_seed, sizeof(StreamCarry), hipHostMallocDefault));
+    if (!c->h_seed) HIPCHK(c->h_seed.alloc(sizeof(StreamCarry), hip_host_malloc));
     c->carry_cur = 0;
     c->st_on = true;
     return MFB_OK;
@@ -2898,28 +2790,21 @@ extern "C" int mfb_debug_block_scalars(mfb_ctx *c, int n, const float *picks, co
     if (!c || n < 1 || !picks || !triples || !results || spsym_min < 2 || snr_window < 0 || max_symbols < 1) return MFB_ERR_ARG;
     if (!c->have_shifts) return MFB_ERR_STATE;
     HIPCHK(hipSetDevice(c->device));
-    float *d_in = nullptr;
-    BlockScalars *d_out = nullptr;
+    DevBuf<float> d_in;
+    DevBuf<BlockScalars> d_out;
     std::vector<BlockScalars> h((size_t)n);
-    int rc = MFB_OK;
     const size_t in_bytes = (size_t)n * 5 * sizeof(float);
-    if (hipMalloc((void **)&d_in, in_bytes) != hipSuccess || hipMalloc((void **)&d_out, (size_t)n * sizeof(BlockScalars)) != hipSuccess) {
-        rc = MFB_ERR_ALLOC;
-    } else if (hipMemcpy(d_in, picks, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-               hipMemcpy(d_in + 2 * (size_t)n, triples, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-        rc = MFB_ERR_HIP;
-    } else {
-        const int capacity = max_symbols < c->cap ? max_symbols : c->cap;
-        hipLaunchKernelGGL(k_block_scalars_debug, dim3((n + 63) / 64), dim3(64), 0, c->stream, n, (const float *)d_in,
-                           (const float *)(d_in + 2 * (size_t)n), (const int *)c->d_shifts, c->Dtot, c->N, snr_window, spsym_min, capacity,
-                           d_out);
-        if (hipGetLastError() != hipSuccess || sync_streams(c) != hipSuccess ||
-            hipMemcpy(h.data(), d_out, (size_t)n * sizeof(BlockScalars), hipMemcpyDeviceToHost) != hipSuccess)
-            rc = MFB_ERR_HIP;
-    }
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    if (rc) return rc;
+    if (d_in.alloc(in_bytes, hip_malloc) != hipSuccess || d_out.alloc((size_t)n * sizeof(BlockScalars), hip_malloc) != hipSuccess) return MFB_ERR_ALLOC;
+    if (hipMemcpy(d_in, picks, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_in + 2 * (size_t)n, triples, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+        return MFB_ERR_HIP;
+    const int capacity = max_symbols < c->cap ? max_symbols : c->cap;
+    hipLaunchKernelGGL(k_block_scalars_debug, dim3((n + 63) / 64), dim3(64), 0, c->stream, n, (const float *)d_in,
+                       (const float *)(d_in + 2 * (size_t)n), (const int *)c->d_shifts, c->Dtot, c->N, snr_window, spsym_min, capacity,
+                       d_out);
+    if (hipGetLastError() != hipSuccess || sync_streams(c) != hipSuccess ||
+        hipMemcpy(h.data(), d_out, (size_t)n * sizeof(BlockScalars), hipMemcpyDeviceToHost) != hipSuccess)
+        return MFB_ERR_HIP;
     for (int i = 0; i < n; ++i) {
         const BlockScalars &hs = h[(size_t)i];
         mfb_block_result &r = results[i];
@@ -2951,9 +2836,9 @@ extern "C" int mfb_debug_block_scalars(mfb_ctx *c, int n, const float *picks, co
 static int input_buffer2(mfb_ctx *c) {
     if (!c->h_in2) {
         HIPCHK(hipSetDevice(c->device));
-        HIPCHK(hipHostMalloc((void **)&c->h_in2, (size_t)c->N * sizeof(cf), hipHostMallocDefault));
+        HIPCHK(c->h_in2.alloc((size_t)c->N * sizeof(cf), hip_host_malloc));
         memset(c->h_in2, 0, (size_t)c->N * sizeof(cf));
-        if (!c->d_x2) HIPCHK(dev_alloc((void **)&c->d_x2, (size_t)c->N * sizeof(cf)));
+        if (!c->d_x2) HIPCHK(c->d_x2.alloc((size_t)c->N * sizeof(cf), dev_alloc));
     }
     return MFB_OK;
 }
@@ -2962,7 +2847,7 @@ extern "C" int mfb_input_buffer2(mfb_ctx *c, float **p) {
     if (c->fmt != MFB_SAMPLES_CF32) return MFB_ERR_STATE;      // the buffer holds integers: mfb_input_buffer_raw
     const int rc = input_buffer2(c);
     if (rc) return rc;
-    *p = (float *)c->h_in2;
+    *p = (float *)c->h_in2.get();
     return MFB_OK;
 }
 extern "C" int mfb_input_buffer_raw(mfb_ctx *c, int which, void **host, size_t *bytes) {
@@ -3012,61 +2897,39 @@ extern "C" int mfb_debug_unpack(int device, int format, float scale, const void 
         return MFB_ERR_ARG;
     const float sc = fmt_scale_checked(format, scale);
     if (sc == 0.f) return MFB_ERR_ARG;
-    int ndev = 0;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return MFB_ERR_ARG;
-    HIPCHK(hipSetDevice(device));
+    const int rc = device_ok(device);
+    if (rc) return rc;
     const size_t bytes = nsamples * (size_t)fmt_bytes(format);
-    void *d_in = nullptr;
-    cf *d_out = nullptr;
-    int rc = MFB_OK;
-    auto body = [&]() -> int {
-        HIPCHK(hipMalloc(&d_in, (bytes + 15) & ~(size_t)15));
-        HIPCHK(hipMalloc((void **)&d_out, nsamples * sizeof(cf)));
-        HIPCHK(hipMemcpy(d_in, raw, bytes, hipMemcpyHostToDevice));
-        const int r = launch_unpack(format, d_in, d_out, nsamples, sc, nullptr);
-        if (r) return r;
-        HIPCHK(hipMemcpy(out_c64, d_out, nsamples * sizeof(cf), hipMemcpyDeviceToHost));
-        return MFB_OK;
-    };
-    rc = body();
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    return rc;
+    DevBuf<void> d_in;
+    DevBuf<cf> d_out;
+    HIPCHK(d_in.alloc((bytes + 15) & ~(size_t)15, hip_malloc));
+    HIPCHK(d_out.alloc(nsamples * sizeof(cf), hip_malloc));
+    HIPCHK(hipMemcpy(d_in, raw, bytes, hipMemcpyHostToDevice));
+    const int r = launch_unpack(format, d_in, d_out, nsamples, sc, nullptr);
+    if (r) return r;
+    HIPCHK(hipMemcpy(out_c64, d_out, nsamples * sizeof(cf), hipMemcpyDeviceToHost));
+    return MFB_OK;
 }
 
 // Test seams of the demodulation tail: k_envelope, k_code_rate / k_code_rate_block and k_centres, launched as the product launches
 // them, on INJECTED inputs.  Handle-less: buffers of their own on the null stream, a synchronous copy back.
 #define DBG_TAIL_MAX_ELEMS ((size_t)1 << 26)      // complex64 elements a seam takes (512 MiB)
-static int debug_device_ok(int device) {
-    int ndev = 0;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return MFB_ERR_ARG;
-    HIPCHK(hipSetDevice(device));
-    return MFB_OK;
-}
 extern "C" int mfb_debug_envelope(int device, const float *xc_c64, int nb, int M, int N, int off, float *env) {
     if (!xc_c64 || !env || nb < 1 || M < 1 || N < 1 || off < 0 || 2 * off >= M) return MFB_ERR_ARG;
     if (nb > 65535 || (size_t)nb * (size_t)M * (size_t)N > DBG_TAIL_MAX_ELEMS) return MFB_ERR_UNSUPPORTED;
-    int rc = debug_device_ok(device);
+    int rc = device_ok(device);
     if (rc) return rc;
     const size_t nin = (size_t)nb * M * N, nout = (size_t)nb * N;
-    cf *d_xc = nullptr;
-    float *d_env = nullptr;
-    auto run = [&]() -> int {
-        HIPCHK(hipMalloc((void **)&d_xc, nin * sizeof(cf)));
-        HIPCHK(hipMalloc((void **)&d_env, nout * sizeof(float)));
-        HIPCHK(hipMemcpy(d_xc, xc_c64, nin * sizeof(cf), hipMemcpyHostToDevice));
-        HIPCHK(hipMemset(d_env, 0x5a, nout * sizeof(float)));
-        hipLaunchKernelGGL(k_envelope, dim3(1024, nb), dim3(256), 0, nullptr, (const cf *)d_xc, d_env, N, M, off);     // as demod_enqueue
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpy(env, d_env, nout * sizeof(float), hipMemcpyDeviceToHost));
-        return MFB_OK;
-    };
-    rc = run();
-    if (d_xc) (void)hipFree(d_xc);
-    if (d_env) (void)hipFree(d_env);
-    return rc;
+    DevBuf<cf> d_xc;
+    DevBuf<float> d_env;
+    HIPCHK(d_xc.alloc(nin * sizeof(cf), hip_malloc));
+    HIPCHK(d_env.alloc(nout * sizeof(float), hip_malloc));
+    HIPCHK(hipMemcpy(d_xc, xc_c64, nin * sizeof(cf), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_env, 0x5a, nout * sizeof(float)));
+    hipLaunchKernelGGL(k_envelope, dim3(1024, nb), dim3(256), 0, nullptr, (const cf *)d_xc, d_env, N, M, off);     // as demod_enqueue
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(env, d_env, nout * sizeof(float), hipMemcpyDeviceToHost));
+    return MFB_OK;
 }
 
 // k_band_means on an injected spectrum X[N] and n injected windows, one launch
@@ -3079,29 +2942,22 @@ extern "C" int mfb_debug_band_means(int device, const float *X_c64, int N, int n
             (long long)q[1] + q[3] > N)
             return MFB_ERR_ARG;
     }
-    int rc = debug_device_ok(device);
+    int rc = device_ok(device);
     if (rc) return rc;
-    cf *d_X = nullptr;
-    int *d_p = nullptr;
-    float *d_m = nullptr;
-    auto run = [&]() -> int {
-        HIPCHK(hipMalloc((void **)&d_X, (size_t)N * sizeof(cf)));
-        HIPCHK(hipMalloc((void **)&d_p, (size_t)n * 4 * sizeof(int)));
-        HIPCHK(hipMalloc((void **)&d_m, (size_t)n * sizeof(float)));
-        HIPCHK(hipMemcpy(d_X, X_c64, (size_t)N * sizeof(cf), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_p, pieces, (size_t)n * 4 * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(hipMemset(d_m, 0x5a, (size_t)n * sizeof(float)));
-        hipLaunchKernelGGL(k_band_means, dim3(1, n), dim3(SNR_THREADS), 0, nullptr, (const float2 *)d_X, (size_t)0, N, (const int *)d_p,
-                           4 * sizeof(int), d_m, sizeof(float));
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpy(means, d_m, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-        return MFB_OK;
-    };
-    rc = run();
-    if (d_X) (void)hipFree(d_X);
-    if (d_p) (void)hipFree(d_p);
-    if (d_m) (void)hipFree(d_m);
-    return rc;
+    DevBuf<cf> d_X;
+    DevBuf<int> d_p;
+    DevBuf<float> d_m;
+    HIPCHK(d_X.alloc((size_t)N * sizeof(cf), hip_malloc));
+    HIPCHK(d_p.alloc((size_t)n * 4 * sizeof(int), hip_malloc));
+    HIPCHK(d_m.alloc((size_t)n * sizeof(float), hip_malloc));
+    HIPCHK(hipMemcpy(d_X, X_c64, (size_t)N * sizeof(cf), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_p, pieces, (size_t)n * 4 * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_m, 0x5a, (size_t)n * sizeof(float)));
+    hipLaunchKernelGGL(k_band_means, dim3(1, n), dim3(SNR_THREADS), 0, nullptr, (const float2 *)d_X.get(), (size_t)0, N, (const int *)d_p,
+                       4 * sizeof(int), d_m, sizeof(float));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(means, d_m, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return MFB_OK;
 }
 
 #define DBG_REC_STRIDE 256       // bytes from one window's BlockScalars to the next (static_assert: sizeof(BlockScalars) <= 256)
@@ -3110,37 +2966,29 @@ extern "C" int mfb_debug_code_rate(int device, const float *P_c64, int nb, int n
     if (!P_c64 || !triples || !block_triples || !rate || !launch_args || !counts || nb < 1 || n < 1) return MFB_ERR_ARG;
     if (offset < 0 || len < 0 || (long long)offset + len > n) return MFB_ERR_ARG;          // as mfb_demodulate
     if (nb > 65535 || (size_t)nb * (size_t)n > DBG_TAIL_MAX_ELEMS) return MFB_ERR_UNSUPPORTED;
-    int rc = debug_device_ok(device);
+    int rc = device_ok(device);
     if (rc) return rc;
     const size_t nin = (size_t)nb * n;
-    cf *d_P = nullptr;
-    float *d_cr = nullptr;           // [2][nb][3]: k_code_rate's triples, then k_code_rate_block's
-    uint8_t *d_sc = nullptr;
+    DevBuf<cf> d_P;
+    DevBuf<float> d_cr;              // [2][nb][3]: k_code_rate's triples, then k_code_rate_block's
+    DevBuf<uint8_t> d_sc;
     std::vector<uint8_t> recs((size_t)nb * DBG_REC_STRIDE);
-    auto run = [&]() -> int {
-        HIPCHK(hipMalloc((void **)&d_P, nin * sizeof(cf)));
-        HIPCHK(hipMalloc((void **)&d_cr, (size_t)6 * nb * sizeof(float)));
-        HIPCHK(hipMalloc((void **)&d_sc, recs.size()));
-        HIPCHK(hipMemcpy(d_P, P_c64, nin * sizeof(cf), hipMemcpyHostToDevice));
-        HIPCHK(hipMemset(d_cr, 0x5a, (size_t)6 * nb * sizeof(float)));
-        HIPCHK(hipMemset(d_sc, 0, recs.size()));
-        for (int b = 0; b < nb; ++b)
-            hipLaunchKernelGGL(k_code_rate, dim3(1), dim3(1024), 0, nullptr, (const cf *)(d_P + (size_t)b * n), d_cr + 3 * (size_t)b, offset,
-                               len);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_code_rate_block, dim3(nb), dim3(1024), 0, nullptr, (const cf *)d_P, d_cr + 3 * (size_t)nb, offset, len, n,
-                           spsym_min, capacity, reinterpret_cast<BlockScalars *>(d_sc), (size_t)DBG_REC_STRIDE);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpy(triples, d_cr, (size_t)3 * nb * sizeof(float), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(block_triples, d_cr + 3 * (size_t)nb, (size_t)3 * nb * sizeof(float), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(recs.data(), d_sc, recs.size(), hipMemcpyDeviceToHost));
-        return MFB_OK;
-    };
-    rc = run();
-    if (d_P) (void)hipFree(d_P);
-    if (d_cr) (void)hipFree(d_cr);
-    if (d_sc) (void)hipFree(d_sc);
-    if (rc) return rc;
+    HIPCHK(d_P.alloc(nin * sizeof(cf), hip_malloc));
+    HIPCHK(d_cr.alloc((size_t)6 * nb * sizeof(float), hip_malloc));
+    HIPCHK(d_sc.alloc(recs.size(), hip_malloc));
+    HIPCHK(hipMemcpy(d_P, P_c64, nin * sizeof(cf), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_cr, 0x5a, (size_t)6 * nb * sizeof(float)));
+    HIPCHK(hipMemset(d_sc, 0, recs.size()));
+    for (int b = 0; b < nb; ++b)
+        hipLaunchKernelGGL(k_code_rate, dim3(1), dim3(1024), 0, nullptr, (const cf *)(d_P + (size_t)b * n), d_cr + 3 * (size_t)b, offset,
+                           len);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_code_rate_block, dim3(nb), dim3(1024), 0, nullptr, (const cf *)d_P, d_cr + 3 * (size_t)nb, offset, len, n,
+                       spsym_min, capacity, reinterpret_cast<BlockScalars *>(d_sc.get()), (size_t)DBG_REC_STRIDE);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(triples, d_cr, (size_t)3 * nb * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(block_triples, d_cr + 3 * (size_t)nb, (size_t)3 * nb * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(recs.data(), d_sc, recs.size(), hipMemcpyDeviceToHost));
     for (int b = 0; b < nb; ++b) {
         BlockScalars sc;
         memcpy(&sc, recs.data() + (size_t)b * DBG_REC_STRIDE, sizeof(sc));
@@ -3160,29 +3008,23 @@ extern "C" int mfb_debug_centres(int device, const float *sig_c64, int M, int le
         return MFB_ERR_ARG;
     if (!(spSym >= 2.0f) || !(offset >= 0.f) || !(offset < 2147483648.f)) return MFB_ERR_ARG;       // as mfb_find_centres; a code phase is >= 0
     if (nthreads > (1 << 20) || lenSig > (1 << 22) || (size_t)M * (size_t)lenSig > DBG_TAIL_MAX_ELEMS) return MFB_ERR_UNSUPPORTED;
-    int rc = debug_device_ok(device);
+    int rc = device_ok(device);
     if (rc) return rc;
     const int nblk = (nthreads + 255) / 256;
     const size_t nin = (size_t)M * lenSig, nent = (size_t)nblk * 256;
-    cf *d_sig = nullptr;
-    int32_t *d_out = nullptr;        // [3][nent]: sym, cen, mag
-    auto run = [&]() -> int {
-        HIPCHK(hipMalloc((void **)&d_sig, nin * sizeof(cf)));
-        HIPCHK(hipMalloc((void **)&d_out, 3 * nent * sizeof(int32_t)));
-        HIPCHK(hipMemcpy(d_sig, sig_c64, nin * sizeof(cf), hipMemcpyHostToDevice));
-        HIPCHK(hipMemset(d_out, 0x5a, 3 * nent * sizeof(int32_t)));        // the canary: what the kernel leaves alone stays 0x5a5a5a5a
-        hipLaunchKernelGGL(k_centres, dim3(nblk), dim3(256), 0, nullptr, (int *)d_out, (int *)(d_out + nent),
-                           reinterpret_cast<float *>(d_out + 2 * nent), (const cf *)d_sig, spSym, offset, lenSig, M, W, op, capacity);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpy(sym, d_out, nent * sizeof(int32_t), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(cen, d_out + nent, nent * sizeof(int32_t), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(mag, d_out + 2 * nent, nent * sizeof(float), hipMemcpyDeviceToHost));
-        return MFB_OK;
-    };
-    rc = run();
-    if (d_sig) (void)hipFree(d_sig);
-    if (d_out) (void)hipFree(d_out);
-    return rc;
+    DevBuf<cf> d_sig;
+    DevBuf<int32_t> d_out;           // [3][nent]: sym, cen, mag
+    HIPCHK(d_sig.alloc(nin * sizeof(cf), hip_malloc));
+    HIPCHK(d_out.alloc(3 * nent * sizeof(int32_t), hip_malloc));
+    HIPCHK(hipMemcpy(d_sig, sig_c64, nin * sizeof(cf), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_out, 0x5a, 3 * nent * sizeof(int32_t)));        // the canary: what the kernel leaves alone stays 0x5a5a5a5a
+    hipLaunchKernelGGL(k_centres, dim3(nblk), dim3(256), 0, nullptr, (int *)d_out, (int *)(d_out + nent),
+                       reinterpret_cast<float *>(d_out + 2 * nent), (const cf *)d_sig, spSym, offset, lenSig, M, W, op, capacity);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(sym, d_out, nent * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(cen, d_out + nent, nent * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(mag, d_out + 2 * nent, nent * sizeof(float), hipMemcpyDeviceToHost));
+    return MFB_OK;
 }
 
 extern "C" int mfb_find_centres(mfb_ctx *c, float spSym, float offset, int op, int count, int32_t *sym, int32_t *cen,
@@ -3229,16 +3071,17 @@ extern "C" int mfb_get_envelope(mfb_ctx *c, float *host) {
 // concurrent callers (two decoder threads, two demodulator instances on one device) never share
 // buffers or serialise on the null stream.  The pool itself is guarded by a mutex.
 struct SyncWs {
-    hipStream_t stream = nullptr;
-    uint8_t *bits = nullptr;
-    int8_t *tmpl = nullptr;
-    int32_t *out = nullptr;
-    int *seg = nullptr;     // segcnt | segoff | counts
-    int32_t *hits = nullptr;  // hit_idx | hit_score
+    Stream stream;            // (first: it goes last)
+    DevBuf<uint8_t> bits;
+    DevBuf<int8_t> tmpl;
+    DevBuf<int32_t> out;
+    DevBuf<int> seg;        // segcnt | segoff | counts
+    DevBuf<int32_t> hits;   // hit_idx | hit_score
     size_t cap_bits = 0, cap_tmpl = 0, cap_out = 0, cap_seg = 0, cap_hits = 0;
     // small calls (one block's bit stream, a few templates): inputs and results each travel as ONE packed copy
     // through page-locked staging -- every separate copy of pageable memory costs a round trip of its own
-    uint8_t *h_stage = nullptr, *d_stage = nullptr;
+    HostBuf<uint8_t> h_stage;
+    DevBuf<uint8_t> d_stage;
     size_t cap_hstage = 0, cap_dstage = 0;
 };
 #define SYNC_STAGE_MAX ((size_t)1 << 20)
@@ -3256,15 +3099,12 @@ static SyncWs *ws_acquire(int device) {
             return w;
         }
     }
-    SyncWs *w = new SyncWs();
+    std::unique_ptr<SyncWs> w(new SyncWs());
     // highest priority: the decoder's small searches run while the demodulator's stream has the next block's kernels queued
     int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    if (hipStreamCreateWithPriority(&w->stream, hipStreamNonBlocking, hi) != hipSuccess) {
-        delete w;
-        return nullptr;
-    }
-    return w;
+    if (hipStreamCreateWithPriority(out(w->stream), hipStreamNonBlocking, hi) != hipSuccess) return nullptr;
+    return w.release();      // (the pool keeps its workspaces until the process exits)
 }
 static void ws_release(int device, SyncWs *w) {
     std::lock_guard<std::mutex> lk(g_sync_mu);
@@ -3278,28 +3118,14 @@ struct WsLease {   // returns the workspace on every exit path
     }
 };
 
-template <class T>
-static int ws_reserve(T **p, size_t *cap, size_t need) {
-    if (*cap >= need) return MFB_OK;
-    if (*p) HIPCHK(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    HIPCHK(hipMalloc((void **)p, need));
-    *cap = need;
-    return MFB_OK;
-}
-
-static int sync_device_ok(int device) {
-    int ndev = 0;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev || device >= SYNC_MAX_DEVICES) return MFB_ERR_ARG;
-    HIPCHK(hipSetDevice(device));
+static int ws_reserve(Mem<DevFree> *p, size_t *cap, size_t need) {
+    HIPCHK(reserve(*p, *cap, need, need, hip_malloc));
     return MFB_OK;
 }
 
 extern "C" int mfb_sync_correlate(int device, const uint8_t *bits, int B, int L, const int8_t *tmpl, int T, int32_t *scores) {
     if (!bits || !tmpl || !scores || B < 1 || L < 1 || T < 1 || T > 4096) return MFB_ERR_ARG;
-    int rc = sync_device_ok(device);
+    int rc = device_ok(device, SYNC_MAX_DEVICES);
     if (rc) return rc;
     const int outLen = L + T - 1;
     WsLease lease{device, ws_acquire(device)};
@@ -3333,7 +3159,7 @@ static int sync_find_impl(int device, const uint8_t *bits, int B, int L, const i
         taps += (size_t)T[t];
         if (T[t] > Tmax) Tmax = T[t];
     }
-    int rc = sync_device_ok(device);
+    int rc = device_ok(device, SYNC_MAX_DEVICES);
     if (rc) return rc;
     const int nseg = (L + Tmax - 1 + SYNC_SEG - 1) / SYNC_SEG;      // segments of the longest output
     WsLease lease{device, ws_acquire(device)};
@@ -3350,18 +3176,12 @@ static int sync_find_impl(int device, const uint8_t *bits, int B, int L, const i
     if (packed) {
         const size_t in_bytes = align16(taps) + nbits;
         const size_t hneed = in_bytes > res_ints * sizeof(int32_t) ? in_bytes : res_ints * sizeof(int32_t);
-        if (w.cap_hstage < hneed) {
-            if (w.h_stage) HIPCHK(hipHostFree(w.h_stage));
-            w.h_stage = nullptr;
-            w.cap_hstage = 0;
-            HIPCHK(hipHostMalloc((void **)&w.h_stage, hneed, hipHostMallocDefault));
-            w.cap_hstage = hneed;
-        }
+        HIPCHK(reserve(w.h_stage, w.cap_hstage, hneed, hneed, hip_host_malloc));
         if ((rc = ws_reserve(&w.d_stage, &w.cap_dstage, in_bytes))) return rc;
         memcpy(w.h_stage, tmpls, taps);
         memcpy(w.h_stage + align16(taps), bits, nbits);
         HIPCHK(hipMemcpyAsync(w.d_stage, w.h_stage, in_bytes, hipMemcpyHostToDevice, w.stream));
-        d_tmpl = (const int8_t *)w.d_stage;
+        d_tmpl = (const int8_t *)w.d_stage.get();
         d_bits = w.d_stage + align16(taps);
     } else {
         if ((rc = ws_reserve(&w.bits, &w.cap_bits, nbits))) return rc;
@@ -3404,7 +3224,7 @@ static int sync_find_impl(int device, const uint8_t *bits, int B, int L, const i
     if (packed) {
         HIPCHK(hipMemcpyAsync(w.h_stage, w.hits, res_ints * sizeof(int32_t), hipMemcpyDeviceToHost, w.stream));
         HIPCHK(hipStreamSynchronize(w.stream));
-        const int32_t *r = (const int32_t *)w.h_stage;
+        const int32_t *r = (const int32_t *)w.h_stage.get();
         memcpy(counts, r, nc * sizeof(int32_t));
         memcpy(hit_idx, r + nc, nh * sizeof(int32_t));
         memcpy(hit_score, r + nc + nh, nh * sizeof(int32_t));
@@ -3433,30 +3253,29 @@ extern "C" int mfb_sync_find_multi(int device, const uint8_t *bits, int B, int L
 // device together with a stream, page-locked staging and result buffers of its own, and splits the search into begin
 // (copy in, enqueue, return) and end (wait, copy out): the caller overlaps the round trip with its other work.
 struct mfb_syncfinder {
-    int device, K, max_hits, Tmax;
+    Stream stream;                 // (first: it goes last)
+    int device = 0, K = 0, max_hits = 0, Tmax = 0;
     std::vector<int> T, thr;
-    hipStream_t stream;
-    hipEvent_t done;
-    int8_t *d_tmpl;
-    uint8_t *d_bits, *h_bits;
-    int cap_bits;
-    int32_t *d_res, *h_res;        // counts[K] | idx[K][max_hits] | score[K][max_hits]
-    int *d_seg;                    // segcnt | segoff of the multi-pass form (long streams)
-    size_t cap_seg;
-    SyncSmallArgs sa;
-    bool busy;
+    Event done;
+    DevBuf<int8_t> d_tmpl;
+    DevBuf<uint8_t> d_bits;
+    HostBuf<uint8_t> h_bits;
+    int cap_bits = 0;
+    DevBuf<int32_t> d_res;         // counts[K] | idx[K][max_hits] | score[K][max_hits]
+    HostBuf<int32_t> h_res;
+    DevBuf<int> d_seg;             // segcnt | segoff of the multi-pass form (long streams)
+    size_t cap_seg = 0;
+    SyncSmallArgs sa = {};
+    bool busy = false;
 };
 
 static int sf_reserve_bits(mfb_syncfinder *f, int L) {
     if (L <= f->cap_bits) return MFB_OK;
     HIPCHK(hipStreamSynchronize(f->stream));
-    if (f->d_bits) HIPCHK(hipFree(f->d_bits));
-    if (f->h_bits) HIPCHK(hipHostFree(f->h_bits));
-    f->d_bits = f->h_bits = nullptr;
     f->cap_bits = 0;
     const int cap = L + L / 2 + 1024;
-    HIPCHK(hipMalloc((void **)&f->d_bits, (size_t)cap));
-    HIPCHK(hipHostMalloc((void **)&f->h_bits, (size_t)cap, hipHostMallocDefault));
+    HIPCHK(f->d_bits.alloc((size_t)cap, hip_malloc));
+    HIPCHK(f->h_bits.alloc((size_t)cap, hip_host_malloc));
     f->cap_bits = cap;
     return MFB_OK;
 }
@@ -3465,23 +3284,18 @@ extern "C" int mfb_syncfinder_destroy(mfb_syncfinder *f) {
     if (!f) return MFB_ERR_ARG;
     (void)hipSetDevice(f->device);
     if (f->stream) (void)hipStreamSynchronize(f->stream);
-    if (f->d_tmpl) (void)hipFree(f->d_tmpl);
-    if (f->d_bits) (void)hipFree(f->d_bits);
-    if (f->h_bits) (void)hipHostFree(f->h_bits);
-    if (f->d_res) (void)hipFree(f->d_res);
-    if (f->h_res) (void)hipHostFree(f->h_res);
-    if (f->d_seg) (void)hipFree(f->d_seg);
-    if (f->done) (void)hipEventDestroy(f->done);
-    if (f->stream) (void)hipStreamDestroy(f->stream);
     delete f;
     return MFB_OK;
 }
 
+struct SfDestroy {
+    void operator()(mfb_syncfinder *f) const { (void)mfb_syncfinder_destroy(f); }
+};
 static int sf_create_impl(mfb_syncfinder *f, const int8_t *tmpls, int max_bits) {
     int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    HIPCHK(hipStreamCreateWithPriority(&f->stream, hipStreamNonBlocking, hi));
-    HIPCHK(hipEventCreateWithFlags(&f->done, hipEventDisableTiming));
+    HIPCHK(hipStreamCreateWithPriority(out(f->stream), hipStreamNonBlocking, hi));
+    HIPCHK(hipEventCreateWithFlags(out(f->done), hipEventDisableTiming));
     size_t taps = 0;
     for (int t = 0; t < f->K; ++t) {
         f->sa.T[t] = f->T[t];
@@ -3489,11 +3303,11 @@ static int sf_create_impl(mfb_syncfinder *f, const int8_t *tmpls, int max_bits) 
         f->sa.toff[t] = (int)taps;
         taps += (size_t)f->T[t];
     }
-    HIPCHK(hipMalloc((void **)&f->d_tmpl, taps));
+    HIPCHK(f->d_tmpl.alloc(taps, hip_malloc));
     HIPCHK(hipMemcpy(f->d_tmpl, tmpls, taps, hipMemcpyHostToDevice));
     const size_t res_bytes = (size_t)f->K * (1 + 2 * (size_t)f->max_hits) * sizeof(int32_t);
-    HIPCHK(hipMalloc((void **)&f->d_res, res_bytes));
-    HIPCHK(hipHostMalloc((void **)&f->h_res, res_bytes, hipHostMallocDefault));
+    HIPCHK(f->d_res.alloc(res_bytes, hip_malloc));
+    HIPCHK(f->h_res.alloc(res_bytes, hip_host_malloc));
     return sf_reserve_bits(f, max_bits);
 }
 
@@ -3504,9 +3318,9 @@ extern "C" int mfb_syncfinder_create(mfb_syncfinder **out, int device, const int
     if (!tmpls || !T || !thresholds || ntmpl < 1 || ntmpl > 16 || max_bits < 1 || max_hits < 1) return MFB_ERR_ARG;
     for (int t = 0; t < ntmpl; ++t)
         if (T[t] < 1 || T[t] > 4096) return MFB_ERR_ARG;
-    int rc = sync_device_ok(device);
+    int rc = device_ok(device, SYNC_MAX_DEVICES);
     if (rc) return rc;
-    mfb_syncfinder *f = new mfb_syncfinder();
+    std::unique_ptr<mfb_syncfinder, SfDestroy> f(new mfb_syncfinder());
     f->device = device;
     f->K = ntmpl;
     f->max_hits = max_hits;
@@ -3514,21 +3328,8 @@ extern "C" int mfb_syncfinder_create(mfb_syncfinder **out, int device, const int
     f->thr.assign(thresholds, thresholds + ntmpl);
     f->Tmax = 0;
     for (int t = 0; t < ntmpl; ++t) f->Tmax = T[t] > f->Tmax ? T[t] : f->Tmax;
-    f->stream = nullptr;
-    f->done = nullptr;
-    f->d_tmpl = nullptr;
-    f->d_bits = f->h_bits = nullptr;
-    f->cap_bits = 0;
-    f->d_res = f->h_res = nullptr;
-    f->d_seg = nullptr;
-    f->cap_seg = 0;
-    f->busy = false;
-    rc = sf_create_impl(f, tmpls, max_bits);
-    if (rc) {
-        (void)mfb_syncfinder_destroy(f);
-        return rc;
-    }
-    *out = f;
+    if ((rc = sf_create_impl(f.get(), tmpls, max_bits))) return rc;
+    *out = f.release();
     return MFB_OK;
 }
 
@@ -3551,11 +3352,7 @@ extern "C" int mfb_syncfinder_begin(mfb_syncfinder *f, const uint8_t *bits, int 
         const size_t need = (size_t)2 * nseg * sizeof(int);
         if (f->cap_seg < need) {
             HIPCHK(hipStreamSynchronize(f->stream));
-            if (f->d_seg) HIPCHK(hipFree(f->d_seg));
-            f->d_seg = nullptr;
-            f->cap_seg = 0;
-            HIPCHK(hipMalloc((void **)&f->d_seg, need));
-            f->cap_seg = need;
+            HIPCHK(reserve(f->d_seg, f->cap_seg, need, need, hip_malloc));
         }
         int *segcnt = f->d_seg, *segoff = f->d_seg + nseg;
         for (int t = 0; t < K; ++t) {
@@ -3599,15 +3396,15 @@ extern "C" int mfb_syncfinder_end(mfb_syncfinder *f, int32_t *counts, int32_t *h
 // and device alike: master bits | master trust | slave 0 bits | slave 0 trust | ...; results: mfb_combine_result | bits | trust.
 #define CMB_MAX_BITS (1 << 20)
 struct mfb_combiner {
+    Stream stream;             // (first: it goes last)
     int device = 0, max_bits = 0, max_slaves = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t done = nullptr;
-    uint8_t *h_in = nullptr, *d_in = nullptr;
-    uint8_t *h_out = nullptr, *d_out = nullptr;
-    uint32_t *d_mw = nullptr, *d_sw = nullptr;
-    int32_t *d_x = nullptr;
-    cmb_key *d_cand = nullptr;
-    uint8_t *d_lut = nullptr;
+    Event done;
+    HostBuf<uint8_t> h_in, h_out;
+    DevBuf<uint8_t> d_in, d_out;
+    DevBuf<uint32_t> d_mw, d_sw;
+    DevBuf<int32_t> d_x;
+    DevBuf<cmb_key> d_cand;
+    DevBuf<uint8_t> d_lut;
     int lut_set = 0;           // bit v: the table for v voters is set
     bool busy = false;
     int Lm = 0;
@@ -3645,36 +3442,28 @@ extern "C" int mfb_combiner_destroy(mfb_combiner *c) {
     if (!c) return MFB_ERR_ARG;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->d_in) (void)hipFree(c->d_in);
-    if (c->h_in) (void)hipHostFree(c->h_in);
-    if (c->d_out) (void)hipFree(c->d_out);
-    if (c->h_out) (void)hipHostFree(c->h_out);
-    if (c->d_mw) (void)hipFree(c->d_mw);
-    if (c->d_sw) (void)hipFree(c->d_sw);
-    if (c->d_x) (void)hipFree(c->d_x);
-    if (c->d_cand) (void)hipFree(c->d_cand);
-    if (c->d_lut) (void)hipFree(c->d_lut);
-    if (c->done) (void)hipEventDestroy(c->done);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return MFB_OK;
 }
 
+struct CmbDestroy {
+    void operator()(mfb_combiner *c) const { (void)mfb_combiner_destroy(c); }
+};
 static int cmb_create_impl(mfb_combiner *c) {
-    HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&c->done, hipEventDisableTiming));
+    HIPCHK(hipStreamCreateWithFlags(out(c->stream), hipStreamNonBlocking));
+    HIPCHK(hipEventCreateWithFlags(out(c->done), hipEventDisableTiming));
     const size_t in_bytes = (size_t)2 * c->max_bits * (1 + c->max_slaves);
     const size_t out_bytes = sizeof(mfb_combine_result) + (size_t)2 * c->max_bits;
     const int N = cmb_pow2ceil(c->max_bits);
-    HIPCHK(hipMalloc((void **)&c->d_in, in_bytes));
-    HIPCHK(hipHostMalloc((void **)&c->h_in, in_bytes, hipHostMallocDefault));
-    HIPCHK(hipMalloc((void **)&c->d_out, out_bytes));
-    HIPCHK(hipHostMalloc((void **)&c->h_out, out_bytes, hipHostMallocDefault));
-    HIPCHK(hipMalloc((void **)&c->d_mw, ((size_t)c->max_bits / 32 + 2) * sizeof(uint32_t)));
-    HIPCHK(hipMalloc((void **)&c->d_sw, ((size_t)N / 32 + 2) * sizeof(uint32_t)));
-    HIPCHK(hipMalloc((void **)&c->d_x, (size_t)N * sizeof(int32_t)));
-    HIPCHK(hipMalloc((void **)&c->d_cand, (size_t)(CMB_MAX_BITS / CMB_SEG) * CMB_TOPK * sizeof(cmb_key)));
-    HIPCHK(hipMalloc((void **)&c->d_lut, (size_t)3 * CMB_LUT_STRIDE));
+    HIPCHK(c->d_in.alloc(in_bytes, hip_malloc));
+    HIPCHK(c->h_in.alloc(in_bytes, hip_host_malloc));
+    HIPCHK(c->d_out.alloc(out_bytes, hip_malloc));
+    HIPCHK(c->h_out.alloc(out_bytes, hip_host_malloc));
+    HIPCHK(c->d_mw.alloc(((size_t)c->max_bits / 32 + 2) * sizeof(uint32_t), hip_malloc));
+    HIPCHK(c->d_sw.alloc(((size_t)N / 32 + 2) * sizeof(uint32_t), hip_malloc));
+    HIPCHK(c->d_x.alloc((size_t)N * sizeof(int32_t), hip_malloc));
+    HIPCHK(c->d_cand.alloc((size_t)(CMB_MAX_BITS / CMB_SEG) * CMB_TOPK * sizeof(cmb_key), hip_malloc));
+    HIPCHK(c->d_lut.alloc((size_t)3 * CMB_LUT_STRIDE, hip_malloc));
     HIPCHK(hipMemset(c->d_lut, 0, (size_t)3 * CMB_LUT_STRIDE));
     return MFB_OK;
 }
@@ -3684,19 +3473,16 @@ extern "C" int mfb_combiner_create(mfb_combiner **out, int device, int max_bits,
     *out = nullptr;
     if (max_bits < 1 || max_slaves < 0) return MFB_ERR_ARG;
     if (max_bits > CMB_MAX_BITS || max_slaves > MFB_COMBINE_MAX_SLAVES) return MFB_ERR_UNSUPPORTED;
-    int rc = sync_device_ok(device);
+    int rc = device_ok(device, SYNC_MAX_DEVICES);
     if (rc) return rc;
     return guarded([&]() {
-        mfb_combiner *c = new mfb_combiner();
+        std::unique_ptr<mfb_combiner, CmbDestroy> c(new mfb_combiner());
         c->device = device;
         c->max_bits = max_bits;
         c->max_slaves = max_slaves;
-        const int rc2 = cmb_create_impl(c);
-        if (rc2) {
-            (void)mfb_combiner_destroy(c);
-            return rc2;
-        }
-        *out = c;
+        const int rc2 = cmb_create_impl(c.get());
+        if (rc2) return rc2;
+        *out = c.release();
         return (int)MFB_OK;
     });
 }
@@ -3738,7 +3524,7 @@ extern "C" int mfb_combiner_begin(mfb_combiner *c, const mfb_combine_params *p, 
         off += 2 * n;
     }
     HIPCHK(hipMemcpyAsync(c->d_in, c->h_in, off, hipMemcpyHostToDevice, c->stream));
-    mfb_combine_result *d_res = (mfb_combine_result *)c->d_out;
+    mfb_combine_result *d_res = (mfb_combine_result *)c->d_out.get();
     hipLaunchKernelGGL(k_cmb_init, dim3(1), dim3(64), 0, c->stream, d_res, Lm, ns);
     const int MW = (Lm + 31) / 32;
     hipLaunchKernelGGL(k_cmb_pack, dim3((MW * 32 + 255) / 256), dim3(256), 0, c->stream, (const uint8_t *)c->d_in, Lm, 0xFFFFFFFFu, c->d_mw, MW);
@@ -3784,34 +3570,25 @@ extern "C" int mfb_combiner_end(mfb_combiner *c, mfb_combine_result *result, uin
 extern "C" int mfb_debug_bit_xcorr(int device, const uint8_t *a_bits, int n, const uint8_t *b_bits, int m, int32_t *out) {
     if (!a_bits || !b_bits || !out || n < 1 || m < 1) return MFB_ERR_ARG;
     if (n > CMB_MAX_BITS || m > CMB_MAX_BITS) return MFB_ERR_UNSUPPORTED;
-    int rc = sync_device_ok(device);
+    int rc = device_ok(device, SYNC_MAX_DEVICES);
     if (rc) return rc;
     const int N = cmb_pow2ceil(n), MW = (m + 31) / 32;
-    uint8_t *d_a = nullptr, *d_b = nullptr;
-    uint32_t *d_mw = nullptr, *d_sw = nullptr;
-    int32_t *d_x = nullptr;
-    auto run = [&]() -> int {
-        HIPCHK(hipMalloc((void **)&d_a, (size_t)n));
-        HIPCHK(hipMalloc((void **)&d_b, (size_t)m));
-        HIPCHK(hipMalloc((void **)&d_mw, ((size_t)MW + 2) * sizeof(uint32_t)));
-        HIPCHK(hipMalloc((void **)&d_sw, ((size_t)N / 32 + 2) * sizeof(uint32_t)));
-        HIPCHK(hipMalloc((void **)&d_x, (size_t)N * sizeof(int32_t)));
-        HIPCHK(hipMemcpy(d_a, a_bits, (size_t)n, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_b, b_bits, (size_t)m, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_cmb_pack, dim3((MW * 32 + 255) / 256), dim3(256), 0, nullptr, (const uint8_t *)d_b, m, 0xFFFFFFFFu, d_mw, MW);
-        int ncand = 0;
-        const int rc2 = cmb_enqueue_xcorr(nullptr, d_a, n, m, d_mw, d_sw, d_x, nullptr, nullptr, m, &ncand);
-        if (rc2) return rc2;
-        HIPCHK(hipMemcpy(out, d_x, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost));
-        return MFB_OK;
-    };
-    rc = run();
-    if (d_a) (void)hipFree(d_a);
-    if (d_b) (void)hipFree(d_b);
-    if (d_mw) (void)hipFree(d_mw);
-    if (d_sw) (void)hipFree(d_sw);
-    if (d_x) (void)hipFree(d_x);
-    return rc;
+    DevBuf<uint8_t> d_a, d_b;
+    DevBuf<uint32_t> d_mw, d_sw;
+    DevBuf<int32_t> d_x;
+    HIPCHK(d_a.alloc((size_t)n, hip_malloc));
+    HIPCHK(d_b.alloc((size_t)m, hip_malloc));
+    HIPCHK(d_mw.alloc(((size_t)MW + 2) * sizeof(uint32_t), hip_malloc));
+    HIPCHK(d_sw.alloc(((size_t)N / 32 + 2) * sizeof(uint32_t), hip_malloc));
+    HIPCHK(d_x.alloc((size_t)N * sizeof(int32_t), hip_malloc));
+    HIPCHK(hipMemcpy(d_a, a_bits, (size_t)n, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_b, b_bits, (size_t)m, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_cmb_pack, dim3((MW * 32 + 255) / 256), dim3(256), 0, nullptr, (const uint8_t *)d_b, m, 0xFFFFFFFFu, d_mw, MW);
+    int ncand = 0;
+    const int rc2 = cmb_enqueue_xcorr(nullptr, d_a, n, m, d_mw, d_sw, d_x, nullptr, nullptr, m, &ncand);
+    if (rc2) return rc2;
+    HIPCHK(hipMemcpy(out, d_x, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return MFB_OK;
 }
 
 // Test seam of the peak stages: what a call runs for slave 0 after its correlation -- init, top-15 per segment, merge and decision,
@@ -3822,52 +3599,39 @@ extern "C" int mfb_debug_combine_peaks(int device, const int32_t *x, int nlags, 
     if (nlags > CMB_MAX_BITS || n > CMB_MAX_BITS || master_len > CMB_MAX_BITS) return MFB_ERR_UNSUPPORTED;
     for (int i = 0; i < nlags; ++i)
         if (x[i] < 0) return MFB_ERR_ARG;
-    int rc = sync_device_ok(device);
+    int rc = device_ok(device, SYNC_MAX_DEVICES);
     if (rc) return rc;
     const int g = (nlags + CMB_SEG - 1) / CMB_SEG;
-    int32_t *d_x = nullptr;
-    cmb_key *d_cand = nullptr;
-    mfb_combine_result *d_res = nullptr;
-    auto run = [&]() -> int {
-        HIPCHK(hipMalloc((void **)&d_x, (size_t)nlags * sizeof(int32_t)));
-        HIPCHK(hipMalloc((void **)&d_cand, (size_t)g * CMB_TOPK * sizeof(cmb_key)));
-        HIPCHK(hipMalloc((void **)&d_res, sizeof(mfb_combine_result)));
-        HIPCHK(hipMemcpy(d_x, x, (size_t)nlags * sizeof(int32_t), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_cmb_init, dim3(1), dim3(64), 0, nullptr, d_res, master_len, 1);
-        hipLaunchKernelGGL(k_cmb_top_seg, dim3(g), dim3(256), 0, nullptr, (const int32_t *)d_x, nlags, (const mfb_combine_result *)d_res, d_cand);
-        hipLaunchKernelGGL(k_cmb_decide, dim3(1), dim3(256), 0, nullptr, (const cmb_key *)d_cand, g * CMB_TOPK, d_res, 0, n, variance_multiplier,
-                           min_length);
-        hipLaunchKernelGGL(k_cmb_finish, dim3(1), dim3(1), 0, nullptr, d_res);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpy(out, d_res, sizeof(mfb_combine_result), hipMemcpyDeviceToHost));
-        return MFB_OK;
-    };
-    rc = run();
-    if (d_x) (void)hipFree(d_x);
-    if (d_cand) (void)hipFree(d_cand);
-    if (d_res) (void)hipFree(d_res);
-    return rc;
+    DevBuf<int32_t> d_x;
+    DevBuf<cmb_key> d_cand;
+    DevBuf<mfb_combine_result> d_res;
+    HIPCHK(d_x.alloc((size_t)nlags * sizeof(int32_t), hip_malloc));
+    HIPCHK(d_cand.alloc((size_t)g * CMB_TOPK * sizeof(cmb_key), hip_malloc));
+    HIPCHK(d_res.alloc(sizeof(mfb_combine_result), hip_malloc));
+    HIPCHK(hipMemcpy(d_x, x, (size_t)nlags * sizeof(int32_t), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_cmb_init, dim3(1), dim3(64), 0, nullptr, d_res, master_len, 1);
+    hipLaunchKernelGGL(k_cmb_top_seg, dim3(g), dim3(256), 0, nullptr, (const int32_t *)d_x, nlags, (const mfb_combine_result *)d_res, d_cand);
+    hipLaunchKernelGGL(k_cmb_decide, dim3(1), dim3(256), 0, nullptr, (const cmb_key *)d_cand, g * CMB_TOPK, d_res, 0, n, variance_multiplier,
+                       min_length);
+    hipLaunchKernelGGL(k_cmb_finish, dim3(1), dim3(1), 0, nullptr, d_res);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out, d_res, sizeof(mfb_combine_result), hipMemcpyDeviceToHost));
+    return MFB_OK;
 }
 
 // ---- packed sync correlation (sync_kernels.hpp, second half) -------------------------------------------------------------
 // One page-locked buffer per device, grown on demand: callers that produce their packed bit streams straight into it
 // (mfb_sync_pinned_buffer) get a true asynchronous host-to-device copy; any other host pointer works too (the runtime stages it).
 static std::mutex g_pin_mu;
-static uint8_t *g_pin[SYNC_MAX_DEVICES];
+static HostBuf<uint8_t> *const g_pin = new HostBuf<uint8_t>[SYNC_MAX_DEVICES];     // never deleted: they live until the process exits, as before
 static size_t g_pin_cap[SYNC_MAX_DEVICES];
 
 extern "C" int mfb_sync_pinned_buffer(int device, size_t bytes, void **host) {
     if (!host || bytes < 1) return MFB_ERR_ARG;
-    int rc = sync_device_ok(device);
+    int rc = device_ok(device, SYNC_MAX_DEVICES);
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(g_pin_mu);
-    if (g_pin_cap[device] < bytes) {
-        if (g_pin[device]) HIPCHK(hipHostFree(g_pin[device]));
-        g_pin[device] = nullptr;
-        g_pin_cap[device] = 0;
-        HIPCHK(hipHostMalloc((void **)&g_pin[device], bytes, hipHostMallocDefault));
-        g_pin_cap[device] = bytes;
-    }
+    HIPCHK(reserve(g_pin[device], g_pin_cap[device], bytes, bytes, hip_host_malloc));
     *host = g_pin[device];
     return MFB_OK;
 }
@@ -3885,7 +3649,7 @@ extern "C" int mfb_sync_find_packed(int device, const uint8_t *packed, int B, in
         else if (tmpl[t] == -1) masks[K + t / 64] |= 1ull << (t % 64);
         else if (tmpl[t] != 0) return MFB_ERR_UNSUPPORTED;       // the packed form takes taps in {-1, 0, +1} only
     }
-    int rc = sync_device_ok(device);
+    int rc = device_ok(device, SYNC_MAX_DEVICES);
     if (rc) return rc;
     WsLease lease{device, ws_acquire(device)};
     if (!lease.w) return MFB_ERR_HIP;
@@ -3900,15 +3664,15 @@ extern "C" int mfb_sync_find_packed(int device, const uint8_t *packed, int B, in
     int *segcnt = w.seg, *segoff = segcnt + (size_t)B * nseg, *d_counts = segoff + (size_t)B * nseg, *d_streamoff = d_counts + B;
     int32_t *d_idx = w.hits, *d_sc = w.hits + max_total;
     uint8_t *d_tcnt = w.d_stage;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    Event e0, e1;
     if (device_ms) {
-        HIPCHK(hipEventCreate(&e0));
-        HIPCHK(hipEventCreate(&e1));
+        HIPCHK(hipEventCreate(out(e0)));
+        HIPCHK(hipEventCreate(out(e1)));
     }
     HIPCHK(hipMemcpyAsync(w.bits, packed, nbytes, hipMemcpyHostToDevice, w.stream));
     HIPCHK(hipMemcpyAsync(w.tmpl, masks.data(), masks.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, w.stream));
     if (e0) HIPCHK(hipEventRecord(e0, w.stream));
-    const unsigned long long *d_masks = (const unsigned long long *)w.tmpl;
+    const unsigned long long *d_masks = (const unsigned long long *)w.tmpl.get();
 #define SYNCP_LAUNCH(WRITE_, KT_)                                                                                                        \
     hipLaunchKernelGGL((k_sync_packed<WRITE_, KT_>), dim3(nseg, B), dim3(SYNCP_THREADS), 0, w.stream, (const uint8_t *)w.bits, row_bytes, L, T, \
                        K, d_masks, threshold, nseg, segcnt, d_tcnt, (const int *)segoff, (const int *)d_streamoff, max_total, d_idx, d_sc)
@@ -3936,11 +3700,7 @@ extern "C" int mfb_sync_find_packed(int device, const uint8_t *packed, int B, in
         HIPCHK(hipMemcpyAsync(hit_score, d_sc, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, w.stream));
         HIPCHK(hipStreamSynchronize(w.stream));
     }
-    if (device_ms) {
-        HIPCHK(hipEventElapsedTime(device_ms, e0, e1));
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-    }
+    if (device_ms) HIPCHK(hipEventElapsedTime(device_ms, e0, e1));
     return MFB_OK;
 }
 
@@ -4038,7 +3798,7 @@ extern "C" int mfb_profile_read(mfb_ctx *c, int counts[2], float total_ms[2]) {
             tot += ms;
         }
         total_ms[w] = (float)tot;
-        for (auto e : c->ev[w]) c->ev_pool.push_back(e);
+        for (auto &e : c->ev[w]) c->ev_pool.push_back(std::move(e));
         c->ev[w].clear();
     }
     return MFB_OK;

@@ -166,6 +166,45 @@ def main():
         assert hip.hipMalloc(ctypes.byref(p), ctypes.c_size_t(40 << 20)) == 0
         assert hip.hipFree(p) == 0
 
+    taps = np.zeros((2, N), np.complex64)
+    taps[:, :32] = np.random.RandomState(0).standard_normal((2, 32))
+    late_masks = np.conj(np.fft.fft(taps, axis=1)).astype(np.complex64)      # a short impulse response: the segment path, where batches run
+
+    def late_allocations():
+        """Everything a handle allocates after mfb_create, once per cycle (the cycle of tests/test_gpu_lifetime.py, at this probe's
+        size): two streams with the clip on a batch, the spectrum mirror and its stream, the energy search, the span basis, the
+        integer-sample staging -- then a sync finder and a combiner."""
+        from pycusdr_amd.mfbank import Combiner, MFBank, SyncFinder
+        b = MFBank(bs, 8, 2)
+        b.set_filters(late_masks)
+        b.set_shifts(list(range(8)))
+        b.set_batch_overlap(True)
+        b.set_peak_clip(4.5, 1024)
+        w = b.windows(4, step)[0]
+        w[:] = np.tile(base, -(-w.size // len(base)))[:w.size]
+        b.begin_blocks(0, 4, 300, 200, 8, source='window')
+        b.end_blocks_record(0)
+        b.set_peak_clip(0)
+        for _ in range(2):
+            b.upload(x0)
+            b.get_spectrum(0, 16)
+        b.set_search_mode('energy')
+        b.find_carrier()
+        b.set_search_mode('transforms')
+        b.set_search_basis('span')
+        b.find_carrier()
+        b.set_sample_format('sc16')
+        b.input[:] = 1
+        b.upload()
+        b.close()
+        bits = (np.arange(6000) % 3 == 0).astype(np.uint8)
+        sf = SyncFinder([np.ones(16, np.int8)], [12], max_bits=1 << 12)
+        sf.find(bits)
+        sf.close()
+        cmb = Combiner(max_bits=1 << 12, max_slaves=0)
+        cmb.combine(bits[:4096], np.ones(4096, np.int8), [], 3.0, 16)
+        cmb.close()
+
     stages = [('hip_streams', hip_streams), ('hip_priority_streams', hip_priority_streams), ('hip_events', hip_events),
               ('hip_pinned', hip_pinned), ('hip_device', hip_device), ('handle_only', handle_only), ('handle_search', handle_search),
               ('handle_blocks', handle_blocks), ('runner_b1', runner(1)), ('runner_b4', runner(4)), ('runner_auto', runner(0)),
@@ -173,7 +212,7 @@ def main():
               ('runner_b16_gc', runner(16, collect=True)), ('runner_b16_48', runner(16, blocks=48)), ('decoder_only', decoder_only), ('runner_b32', runner(32)), ('handle_windows4', handle_windows(4)),
               ('handle_windows32', handle_windows(32)), ('batch_once', batch_handle(False, 1)), ('batch_x3', batch_handle(False, 3)),
               ('batch_stages_once', batch_handle(True, 1)), ('batch_stages_x3', batch_handle(True, 3)), ('host_copy', host_copy),
-              ('pinned_big', pinned_big), ('device_big', device_big)]
+              ('pinned_big', pinned_big), ('device_big', device_big), ('late_allocations', late_allocations)]
     for name, f in stages:
         if only and name not in only:
             continue
