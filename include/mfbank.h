@@ -634,6 +634,53 @@ int mfb_debug_bit_xcorr(int device, const uint8_t *a_bits, int n, const uint8_t 
 int mfb_debug_combine_peaks(int device, const int32_t *x, int nlags, int n, int master_len, double variance_multiplier,
                             int min_length, mfb_combine_result *out);
 
+/* The transmit side: LUT modulation of bit frames on the device (csrc/mod_kernels.hpp).  Replaces Modulator.modulate,
+ * modulator/modulator.py:97-129, with FSKmod.modulate (modulator/modulators/FSK_LUT.py:25-42) or GMSKmod.modulate
+ * (modulator/modulators/GMSK_LUT.py:51-72) inside it.  The phase is a uint64 in turns: an increment of v rad is quantised once, in
+ * double, as t = v / (2 pi); t -= floor(t); q = (uint64)(t * 2^64) (q = 0 should t have rounded up to 1.0); every sum after that is
+ * uint64 and wraps, which is the reference's np.mod(cumsum(...), 2 pi) done exactly and independent of the order of summation.
+ * Limits (MFB_ERR_UNSUPPORTED beyond): 2 <= samples per symbol <= 1024, at most 2^17 bits per frame, 4096 frames, 2^22 bits and 2^24
+ * output samples per batch.
+ *   mfb_modulator_create   a stream, staging and device buffers for batches of up to max_bits bits (all frames together) and
+ *                          max_samples output samples (pads included).  Shaped like mfb_combiner_create.
+ *   mfb_modulator_set_lut  the table of phase increments, rad per sample, double [rows][sps] -- the reference's modulatorCLS.LUT
+ *                          WITHOUT Doppler and offsets (those are per frame, below), uploaded once.  MFB_MOD_FSK: rows = 2, row = the
+ *                          bit, initial phase -(2 b0 - 1) pi / 2 (FSK_LUT.py:31).  MFB_MOD_GMSK3: rows = 8, row of symbol s =
+ *                          4 b[s-1] + 2 b[s] + b[s+1] with the bit before the first and after the last taken as 0 (GMSK_LUT.py:58-62),
+ *                          initial phase 0, frames of at least 2 bits.
+ *   mfb_modulator_set_pad  pad_len samples noise[0 .. pad_len) in front of and behind every frame (modulator.py:117-118); a frame
+ *                          that is then shorter than min_len gets noise[0 .. min_len - length) in front of that (modulator.py:121-123).
+ *                          noise_iq: noise_len complex64, noise_len >= max(pad_len, min_len).  pad_len = 0 and min_len = 0 (the
+ *                          state after create): no padding, noise_iq may be NULL.
+ *   mfb_modulator_begin    B frames: bits uint8 0/1 [bit_off[B]], frame f = bits[bit_off[f] .. bit_off[f+1]), bit_off[0] = 0;
+ *                          dphi_rad[f] = the frame's Doppler + offset increment in rad per sample, dopplerCoef + offsetCoef of
+ *                          modulator.py:103-108 (NULL: all 0).  Copies in, enqueues the three kernels and returns.
+ *   mfb_modulator_end      waits; sample_off int64 [B+1] (may be NULL) receives where each frame starts in the output, sample_off[B]
+ *                          the total; out_iq (may be NULL: the batch stays on the device) receives sample_off[B] complex64 -- a
+ *                          plain DMA when it is the buffer of mfb_modulator_host_buffer.
+ *   mfb_modulator_device_output   the last finished batch on the device (complex64) and its length, valid until the next _begin: a
+ *                          frame of it is what mfb_upload_device takes.
+ *   mfb_modulator_host_buffer     page-locked room for max_samples complex64, owned by the handle.
+ * Misuse is an error code, never a fault.  MFB_ERR_ARG: NULL where not allowed, B < 1, offsets not increasing (a frame of 0 bits),
+ * a GMSK frame of < 2 bits, more bits or samples than the handle was created for; MFB_ERR_STATE: no LUT set, _begin or a setter
+ * while a call is in flight, _end without _begin, an accessor before the first batch has ended. */
+#define MFB_MOD_FSK   0
+#define MFB_MOD_GMSK3 1
+typedef struct mfb_modulator mfb_modulator;
+int mfb_modulator_create(mfb_modulator **out, int device, int max_bits, int max_samples);
+int mfb_modulator_destroy(mfb_modulator *m);
+int mfb_modulator_set_lut(mfb_modulator *m, int kind, const double *lut_rad, int rows, int sps);
+int mfb_modulator_set_pad(mfb_modulator *m, const float *noise_iq, int noise_len, int pad_len, int min_len);
+int mfb_modulator_begin(mfb_modulator *m, const uint8_t *bits, const int32_t *bit_off, const double *dphi_rad, int B);
+int mfb_modulator_end(mfb_modulator *m, float *out_iq, int64_t *sample_off);
+int mfb_modulator_device_output(mfb_modulator *m, const void **dev_c64, int64_t *nsamples);
+int mfb_modulator_host_buffer(mfb_modulator *m, float **host_iq);
+/* Test seam: the uint64 phase word of every output sample of the last finished batch (0 in the pads), words [capacity >=
+ * sample_off[B]].  The words come from the production kernels on the production grids: the sample kernel is launched once more on
+ * the batch's rows and scan, and writes them out beside the samples.  No reference counterpart (its phase is a float64 cumsum,
+ * FSK_LUT.py:31, and is never handed out). */
+int mfb_debug_mod_phase(mfb_modulator *m, uint64_t *words, int64_t capacity);
+
 /* HIP-event stopwatch on the handle's stream (bench.py's live kernel timing).  The reference times blocks with time.time()
  * around the whole call (DP:324-333). */
 int mfb_timer_start(mfb_ctx *ctx);

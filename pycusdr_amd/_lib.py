@@ -181,6 +181,15 @@ PROTOTYPES = {
     'mfb_combiner_end': (_i, [_vp, C.POINTER(CombineResult), _vp, _vp]),
     'mfb_debug_bit_xcorr': (_i, [_i, _vp, _i, _vp, _i, _vp]),
     'mfb_debug_combine_peaks': (_i, [_i, _vp, _i, _i, _i, C.c_double, _i, C.POINTER(CombineResult)]),
+    'mfb_modulator_create': (_i, [C.POINTER(_vp), _i, _i, _i]),
+    'mfb_modulator_destroy': (_i, [_vp]),
+    'mfb_modulator_set_lut': (_i, [_vp, _i, _vp, _i, _i]),
+    'mfb_modulator_set_pad': (_i, [_vp, _vp, _i, _i, _i]),
+    'mfb_modulator_begin': (_i, [_vp, _vp, _vp, _vp, _i]),
+    'mfb_modulator_end': (_i, [_vp, _vp, _vp]),
+    'mfb_modulator_device_output': (_i, [_vp, C.POINTER(_vp), C.POINTER(C.c_int64)]),
+    'mfb_modulator_host_buffer': (_i, [_vp, C.POINTER(_fp)]),
+    'mfb_debug_mod_phase': (_i, [_vp, _vp, C.c_int64]),
     'mfb_timer_start': (_i, [_vp]),
     'mfb_timer_stop': (_i, [_vp, _fp]),
     'mfb_profile_enable': (_i, [_vp, _i]),

@@ -1,6 +1,7 @@
-"""CC11xx (TI sub-GHz transceiver framing) receive plugin: 2-FSK (or Gaussian 2-FSK) filters,
+"""CC11xx (TI sub-GHz transceiver framing) plugin: 2-FSK (or Gaussian 2-FSK) filters,
 centre-bit LUT, preamble+sync template, and the packet class with the length-byte cut, PN9
-de-whitening and the CRC flag (reference protocol/CC11xx.py:42-146, 216-300).
+de-whitening and the CRC flag (reference protocol/CC11xx.py:42-146, 216-300); for the transmit side the
+framer, the modulator and the frame's header (reference protocol/CC11xx.py:164-207).
 
 Two things the reference fixes at import time are selectable here:
   * modulation (reference ``modIDX``, CC11xx.py:30-32,42): ``CC11xx`` is FSK-2, ``CC11xx_GFSK2`` the
@@ -62,7 +63,7 @@ def crc16_cc11xx(data):
 def frame_bits(payload, preamble=(0xAA,) * 4, sync=(0xD6, 0xBA, 0xD6, 0xBA), whiten=True):
     """Bits of one CC11xx frame as the reference's TX framer builds it (modulator/encoders/CC11xx.py
     :64-118): preamble | sync | whiten([len = n+2 | payload | CRC low byte | CRC high byte]), MSB first.
-    Test stimulus for the receive path; the transmit chain itself is out of scope."""
+    Stimulus for the receive path's tests; the transmit chain frames through modulator/encoders.py (getFramer below)."""
     payload = np.asarray(payload, dtype=np.uint8)
     body = np.r_[len(payload) + 2, payload].astype(np.uint8)
     crc = crc16_cc11xx(body)
@@ -128,6 +129,24 @@ class _CC11xxFraming:
 
     def Packet(self, *args, **kwargs):
         return PacketCC11xx(self, *args, **kwargs)
+
+    # ---- transmit side (reference CC11xx.py:164-207) ----
+    def getFramer(self, confRadio):
+        from ..modulator import encoders
+        return encoders.CC11xx
+
+    def getModulator(self, confRadio):
+        from ..modulator import modulators
+        return modulators.FSKmod
+
+    def initTxHeader(self):
+        """(preamble bits, sync bits) of a transmitted frame."""
+        preamble = np.unpackbits(np.array([self.tx_preamble] * self.tx_num_preambles, dtype=np.uint8))
+        return preamble, np.unpackbits(np.array([self.tx_sync_seq], dtype=np.uint8))
+
+    def initTxTail(self):
+        """No tail."""
+        return np.array([], dtype=np.uint8), np.array([], dtype=np.uint8)
 
 
 class CC11xx(_CC11xxFraming, FSK2):

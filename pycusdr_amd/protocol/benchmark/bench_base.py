@@ -54,6 +54,12 @@ class Bench_base(ProtocolBase):
     def Packet(self, *args, **kwargs):
         return Packet_bench(self, *args, **kwargs, packetLen=self.packetLen, randSeed=self.randSeed)
 
+    def getModulator(self, confRadio):
+        """The GMSK LUT modulator (reference bench_base.py:115-120).  There is no getFramer: the reference's names an
+        encoder class that its tree does not have."""
+        from ...modulator import modulators
+        return modulators.GMSKmod
+
 
 class Packet_bench(Packet):
     """Known-payload packet: bit errors are counted against the seeded sequence."""
