@@ -681,6 +681,71 @@ int mfb_modulator_host_buffer(mfb_modulator *m, float **host_iq);
  * FSK_LUT.py:31, and is never handed out). */
 int mfb_debug_mod_phase(mfb_modulator *m, uint64_t *words, int64_t capacity);
 
+typedef struct mfb_channel mfb_channel;
+typedef struct mfb_channel_params {
+    int64_t base;             /* absolute position of the window's first sample */
+    int64_t mute_before;      /* absolute positions below it are +0 (0: none) */
+    uint64_t seed;
+    int32_t count;
+    int32_t buffer;           /* 0 or 1 */
+    float sigma;              /* standard deviation per component */
+    float adc_scale;
+    int32_t adc_bits;
+    int32_t reserved;
+} mfb_channel_params;
+typedef struct mfb_channel_frame {
+    int64_t start;            /* absolute position of the frame's first sample */
+    int64_t src;              /* its first sample in the source */
+    int32_t length;
+    float gain;
+    uint64_t phase0;          /* carrier phase at its first sample, turns * 2^64 */
+    uint64_t freq;            /* turns * 2^64 per sample at its first sample */
+    uint64_t rate;            /* turns * 2^64 per sample, per sample */
+} mfb_channel_frame;
+/* The channel between the two ends, on the device (csrc/channel_kernels.hpp): frames placed at their arrival times in one
+ * continuous stream, each on its own carrier with a linear frequency drift, white Gaussian noise underneath, optionally an ADC's
+ * grid.  Restates awgn (examples/benchmark/create_signals.py:115-141) and the zero pad and mix of get_padded_packet
+ * (create_signals.py:197-198); the "N copies of one packet, fresh noise each" of the reference's bench_modem.py is N descriptors
+ * that name the same source span.  One call renders `count` samples, the absolute positions base .. base + count, and the stream
+ * is a pure function of (seed, frames, source, parameters, absolute position): a span rendered in one call equals the same span
+ * rendered in any number of calls, bit for bit.  Per absolute sample n:
+ *     out[n] = adc(gain_f src[src_f + k] e^{2 pi i phi_f(k) / 2^64} + sigma (gI(n) + i gQ(n)))   k = n - start_f, frame f covers n
+ *     out[n] = adc(sigma (gI(n) + i gQ(n)))                                                      no frame covers n
+ *     out[n] = +0 + 0i                                                                           n < mute_before
+ * phi_f(k) = phase0 + k freq + (k (k - 1) / 2) rate in uint64 turns modulo 2^64 (the modulator's convention above; the caller
+ * quantises the three values once by the same rule, a negative one as the two's complement of its magnitude); a phase word of 0 is
+ * exactly (1, 0).
+ * Noise: Philox4x32-10, key = the halves of seed, counter = (n >> 1, 0, 0), sample n taking words 2 (n & 1) and 2 (n & 1) + 1;
+ * u = ((w >> 8) + 1) 2^-24, radius sqrt(-2 ln u) <= 5.77, the second word the angle.  adc_bits 0 (none), 8 or 16 with adc_scale a
+ * power of two: rint(x / scale) to even, saturated, times scale -- what MFB_SAMPLES_SC8 / _SC16 compute from the integers.
+ *   mfb_channel_create     a stream, two output windows of max_samples complex64, device room for max_source source samples and
+ *                          max_frames descriptors, page-locked staging.  Shaped like mfb_modulator_create.
+ *   mfb_channel_set_source what the frames read: nsamples complex64.  on_device = 0: host samples, copied in (at most max_source);
+ *                          1: a device pointer used in place, for example mfb_modulator_device_output's -- the caller keeps it
+ *                          alive and unchanged while renders use it.
+ *   mfb_channel_begin      enqueues one window into buffer params->buffer (0 or 1) and returns.  frames[nframes] sorted by start,
+ *                          not overlapping, each reading source[src .. src + length); a frame may begin before base or end after
+ *                          base + count (it is clipped); nframes = 0: noise alone, frames may be NULL.
+ *   mfb_channel_end        waits; out_iq (may be NULL: the window stays on the device) receives count complex64.
+ *   mfb_channel_device_output   the window rendered last into `buffer`: what mfb_receive_blocks_begin takes with MFB_INPUT_DEVICE.
+ *                          Valid until the next _begin on that buffer.  The pointer is 16-byte aligned for an even base, 8-byte
+ *                          aligned for an odd one.
+ * Misuse is an error code, never a fault.  MFB_ERR_ARG: NULL where not allowed, count < 1, a negative base or start, a length < 1,
+ * frames not sorted by start or overlapping, a frame reading outside the source, a sigma or gain that is not finite, an
+ * adc_bits or adc_scale outside the above, more samples, source or frames than the handle was created for; MFB_ERR_STATE: _begin
+ * or _set_source while a call is in flight, _end without _begin, frames given while no source is set, _device_output of a buffer
+ * never rendered.  Limits (MFB_ERR_UNSUPPORTED beyond): 2^24 samples per window, 2^26 source samples, 2^20 frames, base < 2^62. */
+int mfb_channel_create(mfb_channel **out, int device, int max_samples, int max_source, int max_frames);
+int mfb_channel_destroy(mfb_channel *c);
+int mfb_channel_set_source(mfb_channel *c, const void *samples_c64, int64_t nsamples, int on_device);
+int mfb_channel_begin(mfb_channel *c, const mfb_channel_params *params, const mfb_channel_frame *frames, int nframes);
+int mfb_channel_end(mfb_channel *c, float *out_iq);
+int mfb_channel_device_output(mfb_channel *c, int buffer, const void **dev_c64, int64_t *nsamples);
+/* Test seam of the noise: npairs pairs of 32-bit words (first word -> radius, second -> angle) through the production device
+ * function, out = npairs (gI, gQ) float pairs.  Reaches the ends of the uniform without a search for seeds.  No reference
+ * counterpart (the reference draws from numpy's generator, create_signals.py:115-141). */
+int mfb_debug_channel_normals(int device, const uint32_t *words, int npairs, float *out);
+
 /* HIP-event stopwatch on the handle's stream (bench.py's live kernel timing).  The reference times blocks with time.time()
  * around the whole call (DP:324-333). */
 int mfb_timer_start(mfb_ctx *ctx);

@@ -103,6 +103,18 @@ class SearchPlan(C.Structure):
                [(k, C.c_int32) for k in ('need_tables', 'need_rows', 'need_span', 'need_segl', 'need_wkt')]
 
 
+class ChannelParams(C.Structure):
+    """mfb_channel_params of include/mfbank.h."""
+    _fields_ = [('base', C.c_int64), ('mute_before', C.c_int64), ('seed', C.c_uint64), ('count', C.c_int32), ('buffer', C.c_int32),
+                ('sigma', C.c_float), ('adc_scale', C.c_float), ('adc_bits', C.c_int32), ('reserved', C.c_int32)]
+
+
+class ChannelFrame(C.Structure):
+    """mfb_channel_frame of include/mfbank.h."""
+    _fields_ = [('start', C.c_int64), ('src', C.c_int64), ('length', C.c_int32), ('gain', C.c_float), ('phase0', C.c_uint64),
+                ('freq', C.c_uint64), ('rate', C.c_uint64)]
+
+
 # name -> (restype, argtypes); exactly the prototypes of include/mfbank.h
 PROTOTYPES = {
     'mfb_strerror': (C.c_char_p, [_i]),
@@ -190,6 +202,13 @@ PROTOTYPES = {
     'mfb_modulator_device_output': (_i, [_vp, C.POINTER(_vp), C.POINTER(C.c_int64)]),
     'mfb_modulator_host_buffer': (_i, [_vp, C.POINTER(_fp)]),
     'mfb_debug_mod_phase': (_i, [_vp, _vp, C.c_int64]),
+    'mfb_channel_create': (_i, [C.POINTER(_vp), _i, _i, _i, _i]),
+    'mfb_channel_destroy': (_i, [_vp]),
+    'mfb_channel_set_source': (_i, [_vp, _vp, C.c_int64, _i]),
+    'mfb_channel_begin': (_i, [_vp, C.POINTER(ChannelParams), _vp, _i]),
+    'mfb_channel_end': (_i, [_vp, _vp]),
+    'mfb_channel_device_output': (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(C.c_int64)]),
+    'mfb_debug_channel_normals': (_i, [_i, _vp, _i, _vp]),
     'mfb_timer_start': (_i, [_vp]),
     'mfb_timer_stop': (_i, [_vp, _fp]),
     'mfb_profile_enable': (_i, [_vp, _i]),

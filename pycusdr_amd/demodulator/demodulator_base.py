@@ -455,8 +455,9 @@ class Demodulator:
         stream, block b at ``b * (N - overlap)`` (neighbours share their overlap samples)."""
         return self.bank.windows(int(blocks_per_call), self.sigLen - self.sigOverlap)
 
-    def beginBlocks(self, slot, nblocks, source='window'):
-        """``beginBlock`` for the first ``nblocks`` blocks of window ``source`` ('window' / 'window2'): the device side of all of
+    def beginBlocks(self, slot, nblocks, source='window', device_ptr=None):
+        """``beginBlock`` for the first ``nblocks`` blocks of window ``source`` ('window' / 'window2', or 'device': a window of
+        complex64 samples already in device memory at ``device_ptr``, block b at ``b * (N - overlap)``): the device side of all of
         them as one set of launches (mfb_receive_blocks_begin); ``endBlocks(slot)`` collects.  UHF back end, one-call path -- or STX
         with the device clip: the blocks at the IF-offset shift, clipped on the device and chained from block to block."""
         fixed_shift = None
@@ -465,7 +466,8 @@ class Demodulator:
             fixed_shift = int(self.doppOffsetIdx)
         self.bank.begin_blocks(slot, nblocks, self.codeRateAndPhaseOffsetHigh,
                                self.codeRateAndPhaseOffsetLow - self.codeRateAndPhaseOffsetHigh, self.spsymMin,
-                               op=Operations.CENTRES_ABS.value, snr_window=5, fixed_shift=fixed_shift, source=source)
+                               op=Operations.CENTRES_ABS.value, snr_window=5, fixed_shift=fixed_shift, source=source,
+                               device_ptr=device_ptr, block_stride=(self.sigLen - self.sigOverlap) if source == 'device' else 0)
 
     # ---- A12 / A13 / A14 of a batch on the device (stream_kernels.hpp) -----------------------------
     def enableStreamStages(self, decoder=None):

@@ -484,24 +484,8 @@ class DemodulatorRunner:
         self._apply_batch_overlap()
         names = ('window', 'window2')
         cur = 0
-        # the integer stages behind the symbol decisions (bit lookup, block-overlap alignment, the decoder's searches on the
-        # stream without a stash) on the device too, unless "HIP": {"stream_stages": false}: same results, bit for bit; blocks
-        # the device flags as irregular go through the host code, and the device's state is then seeded again
         confGPU = self.conf['GPU'][self.confRadio['CUDA_settings']]
-        stages = bool(confGPU.get('HIP', {}).get('stream_stages', True)) and hasattr(self.demod, 'enableStreamStages')
-        if stages and B > 64:
-            # the library runs the stream stages for batches of up to 64 blocks (include/mfbank.h): with more, every block would
-            # come back without them, the chain would be marked dirty and re-seeded once per batch -- the host code does all of it
-            log.info('[%s]: %d blocks per call: the integer stages stay on the host (the device takes them for batches of <= 64 blocks)',
-                     self.radioName, B)
-            stages = False
-        if stages:
-            key = id(decoder) if decoder is not None else None
-            if getattr(self, '_stages_for', ()) != (key,):
-                stages = self.demod.enableStreamStages(decoder if hasattr(decoder, 'findFrames_batch') else None)
-                self._stages_for = (key,) if stages else ()
-            if stages:
-                stages = self.demod.seedStreamStages()
+        stages = self._prepare_stream_stages(decoder, B)
         wins[cur][:self.overlap] = self.raw[:self.overlap]      # goes on behind the overlap the last call left
         # the chunk -> window copies run on the library's copy thread (mfb_hostcopy_*) while this thread does the host stages of
         # the previous batch -- for chunks that cannot change under it: read-only arrays (np.frombuffer of a received message; a
@@ -517,70 +501,14 @@ class DemodulatorRunner:
             copier = self._copier
         asm = WindowAssembler(wins[cur], self.overlap, self.samplesPerSlice, B, copier=None if copier is _NoCopier else copier,
                               copy_all_async=mode is True)
-        results, packets = [], []
-        searching = []
-        split = decoder is not None and hasattr(decoder, 'findFrames_begin')
-        if split and hasattr(decoder, 'prepare'):
-            decoder.prepare()
-        last = [None]
-
-        def deliver(d):
-            if sink is not None:
-                sink(d)
-            else:
-                results.append(d)
+        st = self._batch_state(sink, decoder, stages)
+        results, packets, batch_dec = st.results, st.packets, st.batch_dec
 
         def finish_search():
-            if searching:
-                d = searching.pop()
-                pk, _, nsync = decoder.findFrames_end()
-                d['numSyncSig'] = nsync
-                packets.extend(pk)
-                deliver(d)
-
-        batch_dec = decoder is not None and hasattr(decoder, 'findFrames_batch')
+            self._finish_search(st)
 
         def host_stages(fl, record):
-            """The host side of a finished batch: per-block estimates, A12 / A13 (the device's, or the host code for irregular
-            blocks), the result dicts, the decoder."""
-            slot, count0, nb, stamp, arrived = fl
-            # (clips=False: a block's clip indices are fetched only where the host tags it -- before this slot is begun again)
-            recs = self.demod.endBlocks(slot, record, clips=False)
-            now = time.time()
-            per_block = ((now - last[0]) if last[0] is not None else (now - stamp)) / nb
-            last[0] = now
-            ds, ahead, edges = [], [], []
-            for i, ((doppler, doppler_std, _, snr), rec) in enumerate(recs):
-                part = {'count': count0 + i, 'timestamp': arrived[i], 'doppler': doppler, 'doppler_std': doppler_std, 'SNR': snr,
-                        'rec': rec, 'time_device': per_block}
-                d = self.feed_host(part, timed=False)
-                d['latency_ms'] = (now - arrived[i]) * 1e3
-                self.report(d)
-                ds.append(d)
-                # the hits of the decoder's searches came with the block -- valid while every block since the last seed took
-                # the device's bits
-                ahead.append(rec.get('_sync') if stages and not self.demod._stream_dirty else None)
-                edges.append(rec.get('_edges') if ahead[-1] is not None else None)
-            if batch_dec:
-                # the decoder's searches of all blocks of the batch: delivered with the blocks, or one device round trip for
-                # those that were not (Decoder.findFrames_batch)
-                for d, (pk, _, nsync) in zip(ds, decoder.findFrames_batch([d['data'] for d in ds], 0, ahead=ahead if stages else None,
-                                                                         edges=edges if stages else None)):
-                    d['numSyncSig'] = nsync
-                    packets.extend(pk)
-                    deliver(d)
-                return
-            for d in ds:
-                if split:
-                    finish_search()
-                    decoder.findFrames_begin(d['data'], 0)
-                    searching.append(d)
-                    continue
-                if decoder is not None:
-                    pk, _, nsync = decoder.findFrames(d['data'], 0)
-                    d['numSyncSig'] = nsync
-                    packets.extend(pk)
-                deliver(d)
+            self._host_stages(st, fl, record)
 
         END = object()
         it = iter(chunk_source)
@@ -673,7 +601,7 @@ class DemodulatorRunner:
                     self.demod.bank.end_blocks(slot)
                 except Exception:       # noqa: BLE001 -- nothing was in flight in this slot
                     pass
-            if searching:
+            if st.searching:
                 try:
                     decoder.findFrames_end()
                 except Exception:       # noqa: BLE001
@@ -687,6 +615,168 @@ class DemodulatorRunner:
             finally:
                 self.raw[:self.overlap] = asm.buf[:self.overlap]
         return results, packets
+
+    def _prepare_stream_stages(self, decoder, B):
+        """Whether the device runs the integer stages for the batches of this call (enabled and seeded here); batches of B blocks."""
+        # the integer stages behind the symbol decisions (bit lookup, block-overlap alignment, the decoder's searches on the
+        # stream without a stash) on the device too, unless "HIP": {"stream_stages": false}: same results, bit for bit; blocks
+        # the device flags as irregular go through the host code, and the device's state is then seeded again
+        confGPU = self.conf['GPU'][self.confRadio['CUDA_settings']]
+        stages = bool(confGPU.get('HIP', {}).get('stream_stages', True)) and hasattr(self.demod, 'enableStreamStages')
+        if stages and B > 64:
+            # the library runs the stream stages for batches of up to 64 blocks (include/mfbank.h): with more, every block would
+            # come back without them, the chain would be marked dirty and re-seeded once per batch -- the host code does all of it
+            log.info('[%s]: %d blocks per call: the integer stages stay on the host (the device takes them for batches of <= 64 blocks)',
+                     self.radioName, B)
+            stages = False
+        if stages:
+            key = id(decoder) if decoder is not None else None
+            if getattr(self, '_stages_for', ()) != (key,):
+                stages = self.demod.enableStreamStages(decoder if hasattr(decoder, 'findFrames_batch') else None)
+                self._stages_for = (key,) if stages else ()
+            if stages:
+                stages = self.demod.seedStreamStages()
+        return stages
+
+    def _batch_state(self, sink, decoder, stages):
+        """What the host side of the batched loops carries from batch to batch: where results and packets go, the decoder and
+        how it is driven, the result whose bits the decoder is searching, when the previous batch was collected."""
+        from types import SimpleNamespace
+        split = decoder is not None and hasattr(decoder, 'findFrames_begin')
+        if split and hasattr(decoder, 'prepare'):
+            decoder.prepare()
+        return SimpleNamespace(sink=sink, decoder=decoder, stages=stages, results=[], packets=[], searching=[], split=split,
+                               batch_dec=decoder is not None and hasattr(decoder, 'findFrames_batch'), last=None)
+
+    @staticmethod
+    def _deliver(st, d):
+        if st.sink is not None:
+            st.sink(d)
+        else:
+            st.results.append(d)
+
+    def _finish_search(self, st):
+        if st.searching:
+            d = st.searching.pop()
+            pk, _, nsync = st.decoder.findFrames_end()
+            d['numSyncSig'] = nsync
+            st.packets.extend(pk)
+            self._deliver(st, d)
+
+    def _host_stages(self, st, fl, record):
+        """The host side of a finished batch: per-block estimates, A12 / A13 (the device's, or the host code for irregular
+        blocks), the result dicts, the decoder."""
+        slot, count0, nb, stamp, arrived = fl
+        decoder, stages = st.decoder, st.stages
+        # (clips=False: a block's clip indices are fetched only where the host tags it -- before this slot is begun again)
+        recs = self.demod.endBlocks(slot, record, clips=False)
+        now = time.time()
+        per_block = ((now - st.last) if st.last is not None else (now - stamp)) / nb
+        st.last = now
+        ds, ahead, edges = [], [], []
+        for i, ((doppler, doppler_std, _, snr), rec) in enumerate(recs):
+            part = {'count': count0 + i, 'timestamp': arrived[i], 'doppler': doppler, 'doppler_std': doppler_std, 'SNR': snr,
+                    'rec': rec, 'time_device': per_block}
+            d = self.feed_host(part, timed=False)
+            d['latency_ms'] = (now - arrived[i]) * 1e3
+            self.report(d)
+            ds.append(d)
+            # the hits of the decoder's searches came with the block -- valid while every block since the last seed took
+            # the device's bits
+            ahead.append(rec.get('_sync') if stages and not self.demod._stream_dirty else None)
+            edges.append(rec.get('_edges') if ahead[-1] is not None else None)
+        if st.batch_dec:
+            # the decoder's searches of all blocks of the batch: delivered with the blocks, or one device round trip for
+            # those that were not (Decoder.findFrames_batch)
+            for d, (pk, _, nsync) in zip(ds, decoder.findFrames_batch([d['data'] for d in ds], 0, ahead=ahead if stages else None,
+                                                                     edges=edges if stages else None)):
+                d['numSyncSig'] = nsync
+                st.packets.extend(pk)
+                self._deliver(st, d)
+            return
+        for d in ds:
+            if st.split:
+                self._finish_search(st)
+                decoder.findFrames_begin(d['data'], 0)
+                st.searching.append(d)
+                continue
+            if decoder is not None:
+                pk, _, nsync = decoder.findFrames(d['data'], 0)
+                d['numSyncSig'] = nsync
+                st.packets.extend(pk)
+            self._deliver(st, d)
+
+    def run_device_stream(self, windows, sink=None, decoder=None):
+        """The batched loop of ``run_stream`` on windows that are ALREADY in device memory: ``windows`` iterates
+        ``(device_ptr, nblocks)``, each a window of ``nblocks * (N - overlap) + overlap`` complex64 samples whose block b begins
+        at ``b * (N - overlap)`` and whose first ``overlap`` samples are the previous window's last (``channel.LoopbackSource``
+        renders such windows).  The same stream stages with the same seeding, the same host stages and the same decoder handling
+        as ``_run_stream_batched`` on the same samples, so the same result dicts and packets -- without an assembler and without
+        a copy: the samples never pass through host memory.
+
+        The contract on buffers: the loop begins window w, collects window w - 1, and only then pulls window w + 1 from the
+        iterator.  So a source needs two buffers: it may write window w + 1 where window w - 1 was -- a window is never
+        rewritten before its batch has been collected -- and must not touch the buffer of window w, which the device is
+        reading.  What the iterator yields must be complete in device memory (the source has waited for its own stream).
+
+        Refuses (ValueError) integer sample formats (device windows are complex64), sharded handles, and a bank that is not on
+        the segment search path with the default search mode (the batched calls run only there)."""
+        if self._integer:
+            raise ValueError('run_device_stream takes complex64 windows: the sample format of this handle is an integer one')
+        if getattr(self.demod, 'shard', None) is not None or not self._one_block_path():
+            raise ValueError('run_device_stream runs on one device, one library call per batch: this handle is sharded')
+        bank = self.demod.bank
+        if not (hasattr(bank, 'get_search_path') and bank.get_search_path()['path'] == 'segment' and bank.get_search_mode() == 'transforms'):
+            raise ValueError('run_device_stream needs the segment search path and the default search mode (the batched calls)')
+        self._apply_batch_overlap()
+        it = iter(windows)
+        first = next(it, None)
+        if first is None:
+            return [], []
+        stages = self._prepare_stream_stages(decoder, int(first[1]))
+        st = self._batch_state(sink, decoder, stages)
+        cur, flying = 0, None            # the batch on the device: (slot, first count, blocks, begin time, arrival stamps)
+        try:
+            win = first
+            while win is not None:
+                ptr, nb = int(win[0]), int(win[1])
+                if stages and self.demod._stream_dirty:
+                    # a block went through the host code: what is in flight was enqueued behind the stale state (see
+                    # _run_stream_batched)
+                    if flying is not None:
+                        fl, flying = flying, None
+                        self._host_stages(st, fl, self.demod.waitBlocks(fl[0]))
+                    self.demod.seedStreamStages()
+                self.demod.beginBlocks(cur, nb, source='device', device_ptr=ptr)
+                now = time.time()
+                started = (cur, self.count, nb, now, [now] * nb)
+                self.count += nb
+                cur = 1 - cur
+                # window w is begun: collect window w - 1, whose buffer the source may then render window w + 1 into ...
+                waiting = (flying, self.demod.waitBlocks(flying[0])) if flying is not None else None
+                flying = started
+                # ... which it does here, beside the device's work on window w; then the host stages of window w - 1
+                win = next(it, None)
+                if waiting is not None:
+                    self._host_stages(st, *waiting)
+            if flying is not None:
+                fl, flying = flying, None
+                self._host_stages(st, fl, self.demod.waitBlocks(fl[0]))
+            if not st.batch_dec:
+                self._finish_search(st)
+        except BaseException:
+            for slot in (0, 1):
+                try:
+                    self.demod.bank.end_blocks(slot)
+                except Exception:       # noqa: BLE001 -- nothing was in flight in this slot
+                    pass
+            if st.searching:
+                try:
+                    decoder.findFrames_end()
+                except Exception:       # noqa: BLE001
+                    pass
+            raise
+        return st.results, st.packets
 
     def run(self, sample_source, sink=None, decoder=None, pipelined=False):
         """Drive the loop over an iterable of new-sample slices.  With a ``decoder`` every block's
