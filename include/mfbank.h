@@ -795,6 +795,61 @@ int mfb_window_buffer_raw(mfb_ctx *ctx, int which, int max_blocks, int block_str
  * callers convert with numpy on the host). */
 int mfb_debug_unpack(int device, int format, float scale, const void *raw, size_t nsamples, float *out_c64);
 
+typedef struct mfb_channelizer mfb_channelizer;
+enum { MFB_CHZ_INPUT_PINNED0 = 0, MFB_CHZ_INPUT_PINNED1 = 1, MFB_CHZ_INPUT_DEVICE = 2 };
+typedef struct mfb_channelizer_params {
+    int64_t in_base;          /* absolute position of the call's first input sample */
+    int64_t out_base;         /* absolute position, in a channel's output stream, of the call's first output */
+    const void *device_input; /* MFB_CHZ_INPUT_DEVICE: in_count samples of the plan's format in device memory, aligned to one sample */
+    int32_t in_count;
+    int32_t out_count;
+    int32_t input;            /* MFB_CHZ_INPUT_PINNED0 / _PINNED1: the page-locked buffer of mfb_channelizer_input_buffer; _DEVICE */
+    int32_t buffer;           /* output set 0 or 1 */
+} mfb_channelizer_params;
+/* The channeliser in front of the banks, on the device (csrc/channelize_kernels.hpp): one wideband capture, complex64 or the
+ * integers a radio delivers, becomes K channels, each tuned to baseband, low-pass filtered and decimated to the rate a bank is built
+ * for.  No reference counterpart: the reference takes one narrowband stream per radio process (pyCuSDR.py:245-251).
+ * One plan holds a decimation D, real taps h[0..T) and K tuning words freq_k, uint64 turns * 2^64 per input sample (the modulator's
+ * convention above; a negative frequency is the two's complement).  With n the absolute position in the wideband stream and m in a
+ * channel's output stream:
+ *     phi_k(n) = n freq_k                                                   (uint64, modulo 2^64)
+ *     y_k[m]   = sum_{t < T} h[t] x[m D - t] e^{-2 pi i phi_k(m D - t) / 2^64}     x[n] = 0 for n < 0
+ * computed as e^{-2 pi i phi_k(m D) / 2^64} sum_t (h[t] e^{+2 pi i phi_k(t) / 2^64}) x[m D - t], which is the same thing because phi_k
+ * is linear in integers.  x is complex64; for MFB_SAMPLES_SC16 / _SC8 it is float(int) * scale with scale a power of two (0: full
+ * scale 1.0, as mfb_set_sample_format).  y_k[m] is a pure function of (h, D, freq_k, the T samples it reads, m): a span computed in
+ * one call equals the same span computed in any number of calls, from any input window that covers it, beside any other channels,
+ * bit for bit.  freq_k = 0 filters with h itself and rotates nothing; a rotation word of 0 multiplies nothing: h = [1], freq = 0
+ * gives y[m] = x[m D] bit for bit.  The group delay of a symmetric h is (T - 1) / 2 input samples.
+ *   mfb_channelizer_create         a stream, two output sets of max_channels x max_out complex64, a tap table.
+ *   mfb_channelizer_set_plan       D, the taps, the words, the sample format; builds the tap tables on the device and waits.
+ *   mfb_channelizer_input_buffer   page-locked staging `which` (0 or 1) in the plan's sample format, allocated on first use for max_in
+ *                                  samples: *bytes = max_in * bytes per sample.  Needs a plan.
+ *   mfb_channelizer_begin          enqueues one call and returns: inputs [in_base, in_base + in_count) -> outputs [out_base, out_base +
+ *                                  out_count) of every channel, into output set `buffer`.
+ *   mfb_channelizer_end            waits; out_c64 (may be NULL: the outputs stay on the device) receives [nchan][out_count] complex64.
+ *   mfb_channelizer_device_output  channel `channel` of the call that wrote output set `buffer` last: 16-byte aligned complex64, what
+ *                                  mfb_upload_device and MFB_INPUT_DEVICE take.  Valid until the next _begin on that set or _set_plan.
+ *   mfb_channelizer_info           outputs_per_workgroup: the tile of the plan in force (64, 128 or 256); taps_capacity: max_taps.
+ *   mfb_channelizer_elapsed_ms     device time of the call finished last (events around its kernel, copies of pinned input excluded).
+ * Misuse is an error code, never a fault.  MFB_ERR_ARG: NULL where not allowed, counts < 1, negative bases, a buffer outside 0 / 1,
+ * an unknown format or input, a scale that is not a power of two, taps that are not finite, a device pointer not aligned to a
+ * sample, more channels, taps, inputs or outputs than the handle was created for, and an output range whose inputs
+ * [out_base D - (T - 1), (out_base + out_count - 1) D] are not all inside [in_base, in_base + in_count), apart from positions below 0,
+ * which read as zero.  MFB_ERR_STATE: _begin or _set_plan while a call is in flight, _end without _begin, _begin, _info or
+ * _input_buffer without a plan, a pinned input whose buffer was never asked for, _device_output of a set never written or of a
+ * channel outside the plan that wrote it.  Limits (MFB_ERR_UNSUPPORTED beyond): 1..16 channels, D in 2..64, 1..1024 taps, 2^24 input
+ * and 2^22 output samples per channel and call, in_base and out_base D < 2^62. */
+int mfb_channelizer_create(mfb_channelizer **out, int device, int max_channels, int max_taps, int max_in, int max_out);
+int mfb_channelizer_destroy(mfb_channelizer *c);
+int mfb_channelizer_set_plan(mfb_channelizer *c, int decim, const float *taps, int ntaps, const uint64_t *freq_words, int nchan,
+                             int sample_format, float sample_scale);
+int mfb_channelizer_input_buffer(mfb_channelizer *c, int which, void **host, size_t *bytes);
+int mfb_channelizer_begin(mfb_channelizer *c, const mfb_channelizer_params *params);
+int mfb_channelizer_end(mfb_channelizer *c, float *out_c64);
+int mfb_channelizer_device_output(mfb_channelizer *c, int buffer, int channel, const void **dev_c64, int64_t *nsamples);
+int mfb_channelizer_info(mfb_channelizer *c, int *outputs_per_workgroup, int *taps_capacity);
+int mfb_channelizer_elapsed_ms(mfb_channelizer *c, float *ms);
+
 /* Test seams of the demodulation tail: the three kernels between the matched filters and the bit stream, launched as the product
  * launches them, on INJECTED inputs (tests/test_gpu_demod_tail.py).  Handle-less: device buffers of their own, a synchronous copy
  * back; the product paths do not use them.  MFB_ERR_UNSUPPORTED: more than 2^26 complex64 input elements.

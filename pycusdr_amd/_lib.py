@@ -115,6 +115,12 @@ class ChannelFrame(C.Structure):
                 ('freq', C.c_uint64), ('rate', C.c_uint64)]
 
 
+class ChannelizerParams(C.Structure):
+    """mfb_channelizer_params of include/mfbank.h."""
+    _fields_ = [('in_base', C.c_int64), ('out_base', C.c_int64), ('device_input', C.c_void_p), ('in_count', C.c_int32),
+                ('out_count', C.c_int32), ('input', C.c_int32), ('buffer', C.c_int32)]
+
+
 # name -> (restype, argtypes); exactly the prototypes of include/mfbank.h
 PROTOTYPES = {
     'mfb_strerror': (C.c_char_p, [_i]),
@@ -209,6 +215,15 @@ PROTOTYPES = {
     'mfb_channel_end': (_i, [_vp, _vp]),
     'mfb_channel_device_output': (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(C.c_int64)]),
     'mfb_debug_channel_normals': (_i, [_i, _vp, _i, _vp]),
+    'mfb_channelizer_create': (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i]),
+    'mfb_channelizer_destroy': (_i, [_vp]),
+    'mfb_channelizer_set_plan': (_i, [_vp, _i, _vp, _i, _vp, _i, _i, C.c_float]),
+    'mfb_channelizer_input_buffer': (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
+    'mfb_channelizer_begin': (_i, [_vp, C.POINTER(ChannelizerParams)]),
+    'mfb_channelizer_end': (_i, [_vp, _vp]),
+    'mfb_channelizer_device_output': (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(C.c_int64)]),
+    'mfb_channelizer_info': (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
+    'mfb_channelizer_elapsed_ms': (_i, [_vp, _fp]),
     'mfb_timer_start': (_i, [_vp]),
     'mfb_timer_stop': (_i, [_vp, _fp]),
     'mfb_profile_enable': (_i, [_vp, _i]),

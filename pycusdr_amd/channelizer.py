@@ -1,0 +1,304 @@
+"""The channeliser in front of the banks: one wideband capture -- complex64, or the sc16 / sc8 integers a radio delivers -- becomes
+K channels, each tuned to baseband, low-pass filtered with the plan's real taps and decimated by ``decim`` to the
+``baud * samplesPerSym`` rate a bank is built for.  No reference counterpart: the reference takes one narrowband stream per radio
+process (pyCuSDR.py:245-251).
+
+With n the absolute position in the wideband stream, m the absolute position in a channel's output stream and ``freq_k`` the
+channel's tuning word (uint64 turns * 2**64 per input sample, a negative frequency as the two's complement: the convention of
+``modulator/phase.py`` and ``channel.signed_quantise``):
+
+    phi_k(n) = n * freq_k                                                       (uint64, modulo 2**64)
+    y_k[m]   = sum_{t < T} h[t] * x[m * D - t] * exp(-2 pi i phi_k(m * D - t) / 2**64)       x[n] = 0 for n < 0
+
+``y_k[m]`` is a pure function of (h, D, freq_k, the T samples it reads, m): ``process`` gives the same samples whatever the spans it
+is asked for in and whatever input window covers them, bit for bit.  ``backend='hip'`` is the mfb_channelizer_* handle of
+include/mfbank.h (csrc/channelize_kernels.hpp has the rules); ``backend='host'`` is the model: exactly the sum above, mix first, in
+float64 on exact uint64 words, rounded to complex64 at the end -- the yardstick for the device.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .channel import signed_quantise
+from .modulator import phase
+
+_U = np.uint64
+MAX_CHANNELS, MAX_DECIM, MAX_TAPS, MAX_IN, MAX_OUT = 16, 64, 1024, 1 << 24, 1 << 22
+FORMATS = {'cf32': 0, 'sc16': 1, 'sc8': 2}           # MFB_SAMPLES_* of include/mfbank.h
+_RAW = {'sc16': np.int16, 'sc8': np.int8}
+INPUT_PINNED0, INPUT_PINNED1, INPUT_DEVICE = 0, 1, 2
+
+
+def design_taps(decim, taps_per_phase=16, beta=8.0, cutoff=0.4):
+    """A Kaiser-windowed sinc low-pass for a decimation by ``decim``: ``T = decim * taps_per_phase + 1`` taps, float32, cutoff
+    (the -6 dB point) at ``cutoff / decim`` cycles per input sample, unit gain at DC.  The taps are symmetric: the group delay is
+    ``(T - 1) / 2`` input samples, ``taps_per_phase / 2`` output samples."""
+    decim, taps_per_phase = int(decim), int(taps_per_phase)
+    if decim < 1 or taps_per_phase < 1 or not 0 < cutoff <= 0.5:
+        raise ValueError('decim >= 1, taps_per_phase >= 1, 0 < cutoff <= 0.5')
+    T = decim * taps_per_phase + 1
+    fc = cutoff / decim
+    n = np.arange(T, dtype=np.float64) - (T - 1) / 2
+    h = 2 * fc * np.sinc(2 * fc * n) * np.kaiser(T, beta)
+    return (h / h.sum()).astype(np.float32)
+
+
+def check_plan(decim, taps, words, sample_format, sample_scale):
+    """The checks of mfb_channelizer_set_plan, as ValueError: (decim, taps float32, words uint64, scale)."""
+    decim = int(decim)
+    taps = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+    words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    if not 2 <= decim <= MAX_DECIM:
+        raise ValueError(f'2 <= decim <= {MAX_DECIM}')
+    if not 1 <= len(taps) <= MAX_TAPS or not np.all(np.isfinite(taps)):
+        raise ValueError(f'1 .. {MAX_TAPS} finite taps')
+    if not 1 <= len(words) <= MAX_CHANNELS:
+        raise ValueError(f'1 .. {MAX_CHANNELS} channels')
+    if sample_format not in FORMATS:
+        raise ValueError(f'sample_format is one of {sorted(FORMATS)}')
+    scale = float(sample_scale)
+    if sample_format != 'cf32':
+        m, e = np.frexp(np.float32(scale))
+        if not (np.isfinite(scale) and scale > 0 and m == 0.5 and -100 < e < 100):
+            raise ValueError('sample_scale is a power of two')
+    return decim, taps, words, scale
+
+
+def samples_to_c64(samples, sample_format, scale):
+    """What the device makes of raw input: complex64 as it is; int16 / int8 I, Q pairs as ``raw.astype(float32) * scale``."""
+    if sample_format == 'cf32':
+        return np.ascontiguousarray(samples, dtype=np.complex64).reshape(-1)
+    raw = np.ascontiguousarray(samples, dtype=_RAW[sample_format]).reshape(-1, 2)
+    f = raw.astype(np.float32) * np.float32(scale)
+    return (f[:, 0] + 1j * f[:, 1]).astype(np.complex64)
+
+
+class Channelizer:
+    def __init__(self, fs, decim, taps, freqs_hz, sample_format='cf32', sample_scale=1.0, backend='hip', device=0, max_in=1 << 20,
+                 max_out=None):
+        if backend not in ('hip', 'host'):
+            raise ValueError("backend is 'hip' or 'host'")
+        self.fs, self.backend, self.device = float(fs), backend, device
+        freqs = np.atleast_1d(np.asarray(freqs_hz, dtype=np.float64))
+        if not np.all(np.abs(freqs) <= self.fs / 2):
+            raise ValueError('|freq| <= fs / 2')
+        self.freqs_hz = freqs
+        self.decim, self.taps, self.words, self.scale = check_plan(decim, taps, signed_quantise(phase.TWO_PI * freqs / self.fs),
+                                                                   sample_format, sample_scale)
+        self.sample_format, self.T, self.K = sample_format, len(self.taps), len(self.words)
+        self.max_in = int(max_in)
+        self.max_out = int(max_out) if max_out is not None else max(1, -(-self.max_in // self.decim))
+        if not (1 <= self.max_in <= MAX_IN and 1 <= self.max_out <= MAX_OUT):
+            raise ValueError('1 <= max_in <= 2**24, 1 <= max_out <= 2**22')
+        self._buffer, self._which, self._pinned = 1, 1, [None, None]
+        self.h = C.c_void_p()
+        if backend == 'hip':
+            self.lib = _lib.load()
+            _lib.check(self.lib.mfb_channelizer_create(C.byref(self.h), device, self.K, self.T, self.max_in, self.max_out),
+                       'mfb_channelizer_create')
+            _lib.check(self.lib.mfb_channelizer_set_plan(self.h, self.decim, self.taps.ctypes.data, self.T, self.words.ctypes.data, self.K,
+                                                         FORMATS[sample_format], self.scale), 'mfb_channelizer_set_plan')
+
+    def close(self):
+        if self.h:
+            self._pinned = [None, None]
+            self.lib.mfb_channelizer_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """(outputs per workgroup, tap capacity) of the plan in force (hip)."""
+        a, b = C.c_int(), C.c_int()
+        _lib.check(self.lib.mfb_channelizer_info(self.h, C.byref(a), C.byref(b)), 'mfb_channelizer_info')
+        return a.value, b.value
+
+    def elapsed_ms(self):
+        ms = C.c_float()
+        _lib.check(self.lib.mfb_channelizer_elapsed_ms(self.h, C.byref(ms)), 'mfb_channelizer_elapsed_ms')
+        return ms.value
+
+    def needed_input(self, out_base, out_count):
+        """(in_base, in_count): the input positions that outputs out_base .. out_base + out_count read, clipped at 0."""
+        out_base, out_count = int(out_base), int(out_count)
+        if out_base < 0 or out_count < 1:
+            raise ValueError('out_base >= 0, out_count >= 1')
+        first = max(0, out_base * self.decim - (self.T - 1))
+        last = (out_base + out_count - 1) * self.decim
+        return first, last - first + 1
+
+    def _checked(self, in_base, in_count, out_base, out_count):
+        if in_base < 0 or out_base < 0 or in_count < 1 or out_count < 1:
+            raise ValueError('bases >= 0, counts >= 1')
+        if in_base >= 1 << 62 or out_base * self.decim >= 1 << 62:
+            raise ValueError('in_base, out_base * decim < 2**62')
+        if in_count > self.max_in or out_count > self.max_out:
+            raise ValueError(f'at most max_in = {self.max_in} inputs and max_out = {self.max_out} outputs per call')
+        first, n = self.needed_input(out_base, out_count)
+        if first < in_base or first + n > in_base + in_count:
+            raise ValueError(f'outputs {out_base} .. {out_base + out_count} read inputs {first} .. {first + n}: '
+                             f'not inside {in_base} .. {in_base + in_count}')
+
+    def input_buffer(self, which):
+        """The page-locked staging buffer ``which`` (0 or 1) as a numpy array of the plan's sample format: complex64 [max_in], or
+        int16 / int8 [max_in, 2]."""
+        if self._pinned[which] is None:
+            ptr, nbytes = C.c_void_p(), C.c_size_t()
+            _lib.check(self.lib.mfb_channelizer_input_buffer(self.h, which, C.byref(ptr), C.byref(nbytes)), 'mfb_channelizer_input_buffer')
+            raw = (C.c_uint8 * nbytes.value).from_address(ptr.value)
+            if self.sample_format == 'cf32':
+                self._pinned[which] = np.frombuffer(raw, dtype=np.complex64)
+            else:
+                self._pinned[which] = np.frombuffer(raw, dtype=_RAW[self.sample_format]).reshape(-1, 2)
+        return self._pinned[which]
+
+    def process(self, in_base, samples, out_base, out_count, copy=True, buffer=None):
+        """Outputs out_base .. out_base + out_count of every channel from the input that begins at absolute position ``in_base``:
+        host samples of the plan's format (complex, or int16 / int8 [n, 2]), or -- hip -- device memory as ``(device_ptr, count)``
+        (a bare pointer stands for exactly what ``needed_input`` asks for from ``in_base`` on).  ``copy``: complex64
+        [K, out_count]; not ``copy`` (hip): the outputs stay in the handle's output set ``buffer`` (default: the one not written
+        last), ask ``device_output`` for them."""
+        self.begin(in_base, samples, out_base, out_count, buffer)
+        return self.end(copy)
+
+    def begin(self, in_base, samples, out_base, out_count, buffer=None):
+        in_base, out_base, out_count = int(in_base), int(out_base), int(out_count)
+        on_device = isinstance(samples, (int, tuple))
+        if on_device:
+            if self.backend != 'hip':
+                raise ValueError("device memory is an input of the 'hip' back end")
+            if isinstance(samples, tuple):
+                ptr, in_count = int(samples[0]), int(samples[1])
+            else:
+                first, n = self.needed_input(out_base, max(out_count, 1))
+                ptr, in_count = int(samples), first + n - in_base
+        else:
+            if self.sample_format == 'cf32':
+                x = np.ascontiguousarray(samples, dtype=np.complex64).reshape(-1)
+            else:
+                x = np.ascontiguousarray(samples, dtype=_RAW[self.sample_format]).reshape(-1, 2)
+            in_count = len(x)
+        self._checked(in_base, in_count, out_base, out_count)
+        if self.backend == 'host':
+            self._host = self.model(in_base, x, out_base, out_count)[0].astype(np.complex64)
+            return
+        self._buffer = (self._buffer ^ 1) if buffer is None else int(buffer)
+        P = _lib.ChannelizerParams(in_base=in_base, out_base=out_base, in_count=in_count, out_count=out_count, buffer=self._buffer)
+        if on_device:
+            P.input, P.device_input = INPUT_DEVICE, ptr
+        else:
+            self._which ^= 1
+            self.input_buffer(self._which)[:in_count] = x
+            P.input = INPUT_PINNED1 if self._which else INPUT_PINNED0
+        _lib.check(self.lib.mfb_channelizer_begin(self.h, C.byref(P)), 'mfb_channelizer_begin')
+        self._count = out_count
+
+    def end(self, copy=True):
+        if self.backend == 'host':
+            out, self._host = self._host, None
+            return out
+        if copy:
+            out = np.empty((self.K, self._count), dtype=np.complex64)
+            _lib.check(self.lib.mfb_channelizer_end(self.h, out.ctypes.data), 'mfb_channelizer_end')
+            return out
+        _lib.check(self.lib.mfb_channelizer_end(self.h, None), 'mfb_channelizer_end')
+        return None
+
+    def device_output(self, buffer, k):
+        """(device_ptr, count) of channel ``k`` in output set ``buffer``."""
+        ptr, n = C.c_void_p(), C.c_int64()
+        _lib.check(self.lib.mfb_channelizer_device_output(self.h, buffer, k, C.byref(ptr), C.byref(n)), 'mfb_channelizer_device_output')
+        return ptr.value, n.value
+
+    def model(self, in_base, samples, out_base, out_count):
+        """The definition in float64, mix first, before rounding: (y complex128 [K, out_count], S float64 [out_count]) with
+        ``S[m] = sum_t |h[t]| |x[m D - t]|``, the scale of the device's error bound."""
+        in_base, out_base, out_count = int(in_base), int(out_base), int(out_count)
+        x = samples_to_c64(samples, self.sample_format, self.scale).astype(np.complex128)
+        self._checked(in_base, len(x), out_base, out_count)
+        D, T = self.decim, self.T
+        first = out_base * D - (T - 1)                      # may be negative: those positions read as zero
+        span = (out_count - 1) * D + T
+        lo = max(first, 0)
+        seg = np.zeros(span, dtype=np.complex128)
+        seg[lo - first:] = x[lo - in_base:first + span - in_base]
+        n = np.arange(lo, first + span, dtype=np.int64).astype(np.uint64)
+        hrev = self.taps.astype(np.float64)[::-1]
+        win = np.lib.stride_tricks.sliding_window_view
+        y = np.empty((self.K, out_count), dtype=np.complex128)
+        for k, f in enumerate(self.words):
+            z = seg
+            if f != 0:
+                with np.errstate(over='ignore'):
+                    w = _U(0) - n * _U(f)                   # -phi_k(n), exact
+                z = seg.copy()
+                z[lo - first:] = np.where(w == 0, seg[lo - first:], seg[lo - first:] * phase.words_to_iq(w))
+            y[k] = win(z, T)[::D] @ hrev                   # row j: z[j D .. j D + T - 1], tap t at j D + T - 1 - t
+        S = win(np.abs(seg), T)[::D] @ np.abs(hrev)
+        return y, S
+
+
+class ChannelWide:
+    """A ``Channel`` as the wideband capture of a ``ChannelizerSource``: ``render(in_base, in_count)`` renders that span of the
+    channel's stream on the device and returns its device pointer."""
+
+    def __init__(self, channel, frames=(), sigma=0.0, mute_before=0, adc=None):
+        from .channel import check_frames, pack_frames
+        if channel.backend != 'hip':
+            raise ValueError("the wideband capture is rendered with the 'hip' back end")
+        self.channel, self.sigma, self.mute_before, self.adc = channel, sigma, int(mute_before), adc
+        frames = list(frames)
+        check_frames(frames, channel.source_len)
+        self._starts = np.array([f.start for f in frames], dtype=np.int64)
+        self._ends = np.array([f.start + f.length for f in frames], dtype=np.int64)
+        self._packed = pack_frames(frames)
+
+    def render(self, in_base, in_count):
+        lo = int(np.searchsorted(self._ends, in_base, side='right'))
+        hi = int(np.searchsorted(self._starts, in_base + in_count, side='left'))
+        return self.channel.render(in_base, in_count, self._packed[lo:hi], self.sigma, self.mute_before, self.adc, copy=False)[0]
+
+
+class ChannelizerSource:
+    """Windows of channel ``k`` for ``DemodulatorRunner.run_device_stream``: iterates ``(device_ptr, nblocks)``.  Window w covers
+    the channel's outputs ``w * B * stride .. w * B * stride + B * stride + overlap`` with ``stride = N - overlap`` and
+    ``B = blocks_per_call``, and lies in the channeliser's output set ``w & 1`` (the loop's two-buffer contract: window w + 1 is
+    written where window w - 1 was, after that batch has been collected).  ``wide`` is anything with ``render(in_base, in_count) ->
+    device pointer`` of that span of the capture in the plan's sample format (``ChannelWide``).  Consecutive windows recompute
+    the overlap they share -- an output is a function of its absolute position --, nothing is carried.  One source feeds one
+    runner; every window is one channeliser call, which computes all K channels."""
+
+    def __init__(self, channelizer, k, wide, N, overlap, blocks_per_call, nwindows):
+        self.channelizer, self.k, self.wide = channelizer, int(k), wide
+        self.N, self.overlap, self.B, self.nwindows = int(N), int(overlap), int(blocks_per_call), int(nwindows)
+        self.stride = self.N - self.overlap
+        self.count = self.B * self.stride + self.overlap
+        if not 0 <= self.k < channelizer.K:
+            raise ValueError(f'channel {k} of {channelizer.K}')
+        if self.stride < 1 or self.B < 1 or self.nwindows < 0:
+            raise ValueError('0 <= overlap < N, blocks_per_call >= 1, nwindows >= 0')
+        if self.count > channelizer.max_out or channelizer.needed_input(0, self.count)[1] + channelizer.T - 1 > channelizer.max_in:
+            raise ValueError(f'a window has {self.count} outputs: more than the channeliser was created for')
+
+    def window_base(self, w):
+        return w * self.B * self.stride
+
+    def window_input(self, w):
+        return self.channelizer.needed_input(self.window_base(w), self.count)
+
+    def __len__(self):
+        return self.nwindows
+
+    def __iter__(self):
+        if self.channelizer.backend != 'hip':
+            raise ValueError("a ChannelizerSource yields device windows: the channeliser's back end is not 'hip'")
+        for w in range(self.nwindows):
+            in_base, in_count = self.window_input(w)
+            ptr = self.wide.render(in_base, in_count)
+            self.channelizer.process(in_base, (ptr, in_count), self.window_base(w), self.count, copy=False, buffer=w & 1)
+            yield self.channelizer.device_output(w & 1, self.k)[0], self.B

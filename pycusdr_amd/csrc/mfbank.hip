@@ -58,6 +58,7 @@
 #include "combine_kernels.hpp"
 #include "mod_kernels.hpp"
 #include "channel_kernels.hpp"
+#include "channelize_kernels.hpp"
 #include "energy_kernels.hpp"
 #include "stream_kernels.hpp"
 #include "clip_kernels.hpp"
@@ -4052,6 +4053,242 @@ extern "C" int mfb_debug_channel_normals(int device, const uint32_t *words, int 
         HIPCHK(hipMemcpy(out, d_o, (size_t)npairs * 8, hipMemcpyDeviceToHost));
         return (int)MFB_OK;
     });
+}
+
+// ---- the channeliser (channelize_kernels.hpp) -----------------------------------------------------------------------------
+#define CHZ_MAX_IN (1 << 24)
+#define CHZ_MAX_OUT (1 << 22)
+struct mfb_channelizer {
+    Stream stream;             // (first: it goes last)
+    int device = 0, max_channels = 0, max_taps = 0, max_in = 0, max_out = 0;
+    int out_stride = 0;        // float2 between two channels of an output set: max_out made even, so every channel is 16-byte aligned
+    Event done, t0, t1;
+    HostBuf<uint8_t> h_in[2];  // page-locked raw staging, on demand (mfb_channelizer_input_buffer)
+    DevBuf<uint8_t> d_in[2];   // their device copies, on demand
+    DevBuf<float> d_h;
+    DevBuf<ChzPlan> d_plan;
+    DevBuf<float2> d_taps;     // [max_channels][max_taps]
+    DevBuf<float2> d_out[2];   // [max_channels][out_stride]
+    bool have_plan = false, busy = false;
+    int D = 0, T = 0, K = 0, fmt = 0, ncplx = 0, threads = 0, L = 0;
+    float scale = 1.0f;
+    int cur = 0;               // the buffer of the call in flight
+    int count[2] = {0, 0};     // 0: never written
+    int nchan[2] = {0, 0};     // the plan's channels when it was
+};
+
+static size_t chz_sample_bytes(int fmt) { return fmt == MFB_SAMPLES_SC16 ? 4 : fmt == MFB_SAMPLES_SC8 ? 2 : 8; }
+
+extern "C" int mfb_channelizer_destroy(mfb_channelizer *c) {
+    if (!c) return MFB_ERR_ARG;
+    (void)hipSetDevice(c->device);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    delete c;
+    return MFB_OK;
+}
+
+struct ChzDestroy {
+    void operator()(mfb_channelizer *c) const { (void)mfb_channelizer_destroy(c); }
+};
+static int chz_create_impl(mfb_channelizer *c) {
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamCreateWithFlags(out(c->stream), hipStreamNonBlocking));
+    HIPCHK(hipEventCreateWithFlags(out(c->done), hipEventDisableTiming));
+    HIPCHK(hipEventCreate(out(c->t0)));
+    HIPCHK(hipEventCreate(out(c->t1)));
+    HIPCHK(c->d_h.alloc((size_t)c->max_taps * sizeof(float), hip_malloc));
+    HIPCHK(c->d_plan.alloc(sizeof(ChzPlan), hip_malloc));
+    HIPCHK(c->d_taps.alloc((size_t)c->max_channels * c->max_taps * sizeof(float2), hip_malloc));
+    for (int b = 0; b < 2; ++b) HIPCHK(c->d_out[b].alloc((size_t)c->max_channels * c->out_stride * sizeof(float2), hip_malloc));
+    return MFB_OK;
+}
+
+extern "C" int mfb_channelizer_create(mfb_channelizer **out, int device, int max_channels, int max_taps, int max_in, int max_out) {
+    if (!out) return MFB_ERR_ARG;
+    *out = nullptr;
+    if (max_channels < 1 || max_taps < 1 || max_in < 1 || max_out < 1) return MFB_ERR_ARG;
+    if (max_channels > CHZ_MAX_CHANNELS || max_taps > CHZ_MAX_TAPS || max_in > CHZ_MAX_IN || max_out > CHZ_MAX_OUT) return MFB_ERR_UNSUPPORTED;
+    int rc = device_ok(device, SYNC_MAX_DEVICES);
+    if (rc) return rc;
+    return guarded([&]() {
+        std::unique_ptr<mfb_channelizer, ChzDestroy> c(new mfb_channelizer());
+        c->device = device;
+        c->max_channels = max_channels;
+        c->max_taps = max_taps;
+        c->max_in = max_in;
+        c->max_out = max_out;
+        c->out_stride = (max_out + 1) & ~1;
+        const int rc2 = chz_create_impl(c.get());
+        if (rc2) return rc2;
+        *out = c.release();
+        return (int)MFB_OK;
+    });
+}
+
+static int chz_set_plan_body(mfb_channelizer *c, int decim, const float *taps, int ntaps, const uint64_t *freq_words, int nchan, int fmt,
+                             float scale) {
+    HIPCHK(hipSetDevice(c->device));
+    ChzPlan P;
+    memset(&P, 0, sizeof(P));
+    int ncplx = 0, at = 0;
+    for (int k = 0; k < nchan; ++k) {
+        P.freq[k] = freq_words[k];
+        if (freq_words[k] != 0) P.order[ncplx++] = k;
+    }
+    at = ncplx;
+    for (int k = 0; k < nchan; ++k)
+        if (freq_words[k] == 0) P.order[at++] = k;
+    c->have_plan = false;
+    HIPCHK(hipMemcpyAsync(c->d_h, taps, (size_t)ntaps * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_plan, &P, sizeof(P), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_chz_taps, dim3((ntaps + 255) / 256, nchan), dim3(256), 0, c->stream, (const float *)c->d_h, (const ChzPlan *)c->d_plan,
+                       ntaps, c->max_taps, c->d_taps.get());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));       // (taps and P are the caller's and this frame's)
+    c->D = decim;
+    c->T = ntaps;
+    c->K = nchan;
+    c->fmt = fmt;
+    c->scale = scale;
+    c->ncplx = ncplx;
+    c->threads = chz_threads(decim, ntaps);
+    c->L = chz_row_len(c->threads, decim, ntaps);
+    c->count[0] = c->count[1] = 0;                 // what the buffers hold belongs to the plan before
+    c->have_plan = true;
+    return MFB_OK;
+}
+
+extern "C" int mfb_channelizer_set_plan(mfb_channelizer *c, int decim, const float *taps, int ntaps, const uint64_t *freq_words, int nchan,
+                                        int sample_format, float sample_scale) {
+    if (!c || !taps || !freq_words || ntaps < 1 || nchan < 1) return MFB_ERR_ARG;
+    if (sample_format != MFB_SAMPLES_CF32 && sample_format != MFB_SAMPLES_SC16 && sample_format != MFB_SAMPLES_SC8) return MFB_ERR_ARG;
+    if (decim < 2 || decim > CHZ_MAX_DECIM || ntaps > CHZ_MAX_TAPS || nchan > CHZ_MAX_CHANNELS) return MFB_ERR_UNSUPPORTED;
+    if (ntaps > c->max_taps || nchan > c->max_channels) return MFB_ERR_ARG;
+    float scale = 1.0f;
+    if (sample_format != MFB_SAMPLES_CF32) {
+        scale = sample_scale == 0.0f ? (sample_format == MFB_SAMPLES_SC16 ? 0x1p-15f : 0x1p-7f) : sample_scale;
+        if (!chan_scale_ok(scale)) return MFB_ERR_ARG;
+    }
+    for (int t = 0; t < ntaps; ++t)
+        if (!std::isfinite(taps[t])) return MFB_ERR_ARG;
+    if (c->busy) return MFB_ERR_STATE;
+    return guarded([&] { return chz_set_plan_body(c, decim, taps, ntaps, freq_words, nchan, sample_format, scale); });
+}
+
+extern "C" int mfb_channelizer_input_buffer(mfb_channelizer *c, int which, void **host, size_t *bytes) {
+    if (!c || !host || (which != 0 && which != 1)) return MFB_ERR_ARG;
+    if (!c->have_plan) return MFB_ERR_STATE;
+    return guarded([&]() {          // (also while a call is in flight: the other buffer is being filled)
+        HIPCHK(hipSetDevice(c->device));
+        if (!c->h_in[which]) HIPCHK(c->h_in[which].alloc((size_t)c->max_in * sizeof(float2), hip_host_malloc));
+        *host = c->h_in[which].get();
+        if (bytes) *bytes = (size_t)c->max_in * chz_sample_bytes(c->fmt);
+        return (int)MFB_OK;
+    });
+}
+
+extern "C" int mfb_channelizer_info(mfb_channelizer *c, int *outputs_per_workgroup, int *taps_capacity) {
+    if (!c) return MFB_ERR_ARG;
+    if (!c->have_plan) return MFB_ERR_STATE;
+    if (outputs_per_workgroup) *outputs_per_workgroup = c->threads;
+    if (taps_capacity) *taps_capacity = c->max_taps;
+    return MFB_OK;
+}
+
+static int chz_begin_body(mfb_channelizer *c, const mfb_channelizer_params *p) {
+    HIPCHK(hipSetDevice(c->device));
+    const size_t sb = chz_sample_bytes(c->fmt);
+    const void *raw = p->device_input;
+    if (p->input != MFB_CHZ_INPUT_DEVICE) {
+        const int w = p->input == MFB_CHZ_INPUT_PINNED1;
+        if (!c->d_in[w]) HIPCHK(c->d_in[w].alloc((size_t)c->max_in * sizeof(float2), hip_malloc));
+        HIPCHK(hipMemcpyAsync(c->d_in[w], c->h_in[w], (size_t)p->in_count * sb, hipMemcpyHostToDevice, c->stream));
+        raw = c->d_in[w].get();
+    }
+    ChzArgs A;
+    A.in_base = p->in_base;
+    A.in_end = p->in_base + p->in_count;
+    A.out_base = p->out_base;
+    A.out_count = p->out_count;
+    A.D = c->D;
+    A.T = c->T;
+    A.L = c->L;
+    A.rD = 1.0f / (float)c->D;
+    A.tap_stride = c->max_taps;
+    A.out_stride = c->out_stride;
+    A.ncplx = c->ncplx;
+    A.nreal = c->K - c->ncplx;
+    A.scale = c->scale;
+    const dim3 grid((unsigned)((p->out_count + c->threads - 1) / c->threads)), block(c->threads);
+    const size_t lds = (size_t)c->D * c->L * sizeof(float2);
+    c->count[p->buffer] = 0;
+    HIPCHK(hipEventRecord(c->t0, c->stream));
+#define CHZ_LAUNCH(FMT_)                                                                                                              \
+    hipLaunchKernelGGL(k_chz<FMT_>, grid, block, lds, c->stream, A, (const ChzPlan *)c->d_plan, raw, (const float2 *)c->d_taps, \
+                       c->d_out[p->buffer].get())
+    if (c->fmt == MFB_SAMPLES_SC16) CHZ_LAUNCH(CHZ_FMT_SC16);
+    else if (c->fmt == MFB_SAMPLES_SC8) CHZ_LAUNCH(CHZ_FMT_SC8);
+    else CHZ_LAUNCH(CHZ_FMT_CF32);
+#undef CHZ_LAUNCH
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->t1, c->stream));
+    HIPCHK(hipEventRecord(c->done, c->stream));
+    c->cur = p->buffer;
+    c->count[p->buffer] = p->out_count;
+    c->nchan[p->buffer] = c->K;
+    c->busy = true;
+    return MFB_OK;
+}
+
+extern "C" int mfb_channelizer_begin(mfb_channelizer *c, const mfb_channelizer_params *p) {
+    if (!c || !p) return MFB_ERR_ARG;
+    if (p->in_count < 1 || p->out_count < 1 || p->in_base < 0 || p->out_base < 0 || (p->buffer != 0 && p->buffer != 1)) return MFB_ERR_ARG;
+    if (p->input != MFB_CHZ_INPUT_PINNED0 && p->input != MFB_CHZ_INPUT_PINNED1 && p->input != MFB_CHZ_INPUT_DEVICE) return MFB_ERR_ARG;
+    if (p->input == MFB_CHZ_INPUT_DEVICE && !p->device_input) return MFB_ERR_ARG;
+    if (p->in_count > CHZ_MAX_IN || p->out_count > CHZ_MAX_OUT || p->in_base >= ((int64_t)1 << 62)) return MFB_ERR_UNSUPPORTED;
+    if (p->in_count > c->max_in || p->out_count > c->max_out) return MFB_ERR_ARG;
+    if (c->busy) return MFB_ERR_STATE;
+    if (!c->have_plan) return MFB_ERR_STATE;
+    if (p->out_base >= (((int64_t)1 << 62) + c->D - 1) / c->D) return MFB_ERR_UNSUPPORTED;       // out_base * D < 2^62
+    if (p->input == MFB_CHZ_INPUT_DEVICE && ((uintptr_t)p->device_input & (chz_sample_bytes(c->fmt) - 1))) return MFB_ERR_ARG;
+    if (p->input != MFB_CHZ_INPUT_DEVICE && !c->h_in[p->input == MFB_CHZ_INPUT_PINNED1]) return MFB_ERR_STATE;
+    // every input an output reads, apart from the positions below 0, lies inside the call's input
+    const int64_t first = p->out_base * c->D - (c->T - 1), last = (p->out_base + p->out_count - 1) * c->D;
+    if ((first > 0 ? first : 0) < p->in_base || last >= p->in_base + p->in_count) return MFB_ERR_ARG;
+    return guarded([&] { return chz_begin_body(c, p); });
+}
+
+extern "C" int mfb_channelizer_end(mfb_channelizer *c, float *out_c64) {
+    if (!c) return MFB_ERR_ARG;
+    if (!c->busy) return MFB_ERR_STATE;
+    HIPCHK(hipSetDevice(c->device));
+    const int b = c->cur;
+    if (out_c64) {
+        const size_t row = (size_t)c->count[b] * sizeof(float2);
+        HIPCHK(hipMemcpy2DAsync(out_c64, row, c->d_out[b].get(), (size_t)c->out_stride * sizeof(float2), row, (size_t)c->nchan[b],
+                                hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    } else {
+        HIPCHK(hipEventSynchronize(c->done));
+    }
+    c->busy = false;
+    return MFB_OK;
+}
+
+extern "C" int mfb_channelizer_device_output(mfb_channelizer *c, int buffer, int channel, const void **dev_c64, int64_t *nsamples) {
+    if (!c || !dev_c64 || (buffer != 0 && buffer != 1) || channel < 0) return MFB_ERR_ARG;
+    if ((c->busy && c->cur == buffer) || !c->count[buffer] || channel >= c->nchan[buffer]) return MFB_ERR_STATE;
+    *dev_c64 = c->d_out[buffer].get() + (size_t)channel * c->out_stride;
+    if (nsamples) *nsamples = c->count[buffer];
+    return MFB_OK;
+}
+
+extern "C" int mfb_channelizer_elapsed_ms(mfb_channelizer *c, float *ms) {
+    if (!c || !ms) return MFB_ERR_ARG;
+    if (c->busy || !(c->count[0] || c->count[1])) return MFB_ERR_STATE;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipEventElapsedTime(ms, c->t0, c->t1));
+    return MFB_OK;
 }
 
 // ---- packed sync correlation (sync_kernels.hpp, second half) -------------------------------------------------------------
