@@ -33,6 +33,8 @@ struct StreamDestroy {
 using AllocFn = hipError_t (*)(void **, size_t);
 inline hipError_t hip_malloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
 inline hipError_t hip_host_malloc(void **p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+// ... for memory the host reads while the kernel that writes it still runs
+inline hipError_t hip_host_malloc_coherent(void **p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocCoherent); }
 
 // The untyped part (what a group of buffers of different element types has in common: grow_buffers in mfbank.hip).
 template <class Del>

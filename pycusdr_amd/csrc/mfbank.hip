@@ -8,7 +8,10 @@
 //                                Dc Doppler bins x MU unique filters: Z[row][n1][k2], already multiplied
 //                                by the inter-pass twiddle W_N^(k2*n1).  Never holds the D*M*N cube.
 //   d_part  float32 [D][MU][PARTS] per-workgroup partial |.|^2 sums (fixed-order second reduction,
-//                                no float atomics -> bit-reproducible)
+//                                no float atomics -> bit-reproducible).  Searches that sum a bin's rows in
+//                                registers (k_segw, k_segf's SUMQ = 2 form) write row 0 of the complete slots only:
+//                                rows >= 1 are defined from the masked tail's first partial on, stale below it, and
+//                                k_finalize is told so (presum, tail0)
 //   d_sum   float32 [D][M]       doppSum, same meaning/layout as the reference's GPU_bufDoppSum
 //   d_xc    complex64 [M][N]     matched-filter outputs at the chosen shift (natural order)
 //
@@ -39,6 +42,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
 #include <deque>
 #include <memory>
@@ -111,10 +115,12 @@ struct mfb_ctx {
     // copy into pageable memory is staged by the runtime with a round trip of its own per copy
     HostBuf<uint8_t> h_back;
     size_t back_cap = 0;
-    // the pick's own page-locked slot: k_pick stores its two floats there itself (h_pick_dev: the slot as the device addresses it),
-    // so that no copy -- a blit kernel and its dispatch gap for 8 bytes -- stands between the kernel and the host's read
-    HostBuf<float> h_pick;
-    float *h_pick_dev = nullptr;
+    // the pick's own page-locked slot, 16 bytes, coherent: k_pick stores {two floats, the pick's number, a check word} there itself
+    // (h_pick_dev: the slot as the device addresses it), so that no copy -- a blit kernel and its dispatch gap for 8 bytes -- stands
+    // between the kernel and the host's read, and the host takes the pick when it arrives (read_pick); picks: picks asked for so far
+    HostBuf<uint32_t> h_pick;
+    u32x4 *h_pick_dev = nullptr;
+    uint32_t picks = 0;
     // Host mirror of the spectrum for small blocks.  The reference keeps the spectrum in host-mapped memory and reads
     // its SNR windows straight from there (DB:456-457, 651-661); here the first mfb_get_spectrum on a handle turns on
     // an asynchronous copy of every new spectrum (own stream, beside the search), so that later window reads cost no
@@ -555,7 +561,8 @@ static int create_impl(mfb_ctx *c) {
     c->back_cap = (size_t)3 * (c->N / 2) * sizeof(int) + ((size_t)256 << 10);
     if (c->back_cap < ((size_t)64 << 10)) c->back_cap = (size_t)64 << 10;
     HIPCHK(c->h_back.alloc(c->back_cap, hip_host_malloc));
-    HIPCHK(c->h_pick.alloc(2 * sizeof(float), hip_host_malloc));
+    HIPCHK(c->h_pick.alloc(4 * sizeof(uint32_t), hip_host_malloc_coherent));
+    memset(c->h_pick, 0, 4 * sizeof(uint32_t));          // pick 0 is never asked for
     HIPCHK(hipHostGetDevicePointer((void **)&c->h_pick_dev, c->h_pick, 0));
     HIPCHK(c->d_x.alloc(nb, dev_alloc));
     HIPCHK(c->d_X.alloc(nb, dev_alloc));
@@ -1455,8 +1462,10 @@ static int seg_search_enqueue(mfb_ctx *c, int nb, const cf *x, int xstride, floa
     if (!rc && p.ntotal > p.nfull) rc = launch_seg(c, seg_args(p.tail, p.nfull, p.ntotal - p.nfull), p.tail, SEG_REDUCE, -1);
     if (rc) return rc;
     prof_mark(c, 0);
+    // the forms that sum a bin's rows in registers store row 0 alone: rows >= 1 hold the masked tail's partials and nothing else
+    const int row0_only = p.need_tables && p.sumq == 2;
     hipLaunchKernelGGL(k_finalize, dim3(rows), dim3(fin_threads(MU)), 0, c->stream, c->d_part, dsum, rows, c->M, MU,
-                       span ? (const int *)nullptr : (const int *)c->d_rep, p.parts, c->sum_all);
+                       span ? (const int *)nullptr : (const int *)c->d_rep, p.parts, c->sum_all, row0_only, p.nfull * seg_geom(p.segl).WPT);
     HIPCHK(hipGetLastError());
     return MFB_OK;
 }
@@ -1487,7 +1496,7 @@ extern "C" int mfb_search_async(mfb_ctx *c) {
         HIPCHK(hipGetLastError());
         prof_mark(c, 0);
         hipLaunchKernelGGL(k_finalize, dim3(c->Dtot), dim3(fin_threads(R)), 0, c->stream, c->d_part, c->d_sum, c->Dtot, c->M, R, (const int *)nullptr,
-                           parts, c->sum_all);
+                           parts, c->sum_all, 0, 0);
         HIPCHK(hipGetLastError());
         return MFB_OK;
     }
@@ -1521,7 +1530,7 @@ extern "C" int mfb_search_async(mfb_ctx *c) {
         if (rc) return rc;
     }
     hipLaunchKernelGGL(k_finalize, dim3(c->Dtot), dim3(fin_threads(MU)), 0, c->stream, c->d_part, c->d_sum, c->Dtot, c->M, MU,
-                       (const int *)c->d_rep, c->parts, c->sum_all);
+                       (const int *)c->d_rep, c->parts, c->sum_all, 0, 0);
     HIPCHK(hipGetLastError());
     return MFB_OK;
 }
@@ -1584,20 +1593,46 @@ extern "C" int mfb_export_rows_async(mfb_ctx *c, void *dst, int dst_row, int fir
     return MFB_OK;
 }
 
-// the pick k_pick has just been asked for, from the handle's page-locked slot: the kernel stored it there itself, and a kernel's
-// stores to page-locked host memory are the host's to read once its stream has been synchronised (as read_back synchronises)
+// The pick k_pick has just been asked for (pick number c->picks), from the handle's page-locked slot: the kernel stores it there
+// itself, and the host takes it when it arrives -- hipStreamSynchronize returns only after the end-of-kernel release, the completion
+// signal and the runtime's wake-up, and the device stands empty meanwhile.  The slot is the pick's when its number is c->picks and its
+// check word fits the two floats (k_pick): the pick before, or a store seen in pieces, is waited out.  The wait is bounded: after
+// PICK_SPIN_US, or as soon as the stream is anything but busy (finished without the store having been seen, or failed), it ends in
+// the synchronise it always ended in, with that call's errors; so does a pick with work on the batch path's second stream, which
+// that synchronise waits for too.  The stream is in order, so a pick that has arrived says that everything ahead of k_pick is
+// complete; only k_pick's own end may still be pending, and nothing the host does next depends on that (mfb_destroy, the reserve
+// paths, mfb_set_stream, the timer and every other read-back synchronise for themselves).
+static constexpr int PICK_SPIN_US = 800;
 static int read_pick(mfb_ctx *c, float res[2]) {
+    const uint32_t want = c->picks;
+    const volatile uint32_t *slot = c->h_pick.get();
+    auto arrived = [&] {
+        const uint32_t w0 = slot[0], w1 = slot[1], w2 = slot[2], w3 = slot[3];
+        if (w2 != want || w3 != (want ^ w0 ^ w1)) return false;
+        memcpy(&res[0], &w0, sizeof(float));
+        memcpy(&res[1], &w1, sizeof(float));
+        return true;
+    };
+    if (!(c->s2 && c->s2_busy)) {
+        const auto t0 = std::chrono::steady_clock::now();
+        for (unsigned spin = 1;; ++spin) {
+            if (arrived()) return MFB_OK;
+            mfb_cpu_relax();
+            if ((spin & 255u) == 0u) {
+                if (hipStreamQuery(c->stream) != hipErrorNotReady) break;
+                if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(PICK_SPIN_US)) break;
+            }
+        }
+    }
     HIPCHK(sync_streams(c));
-    res[0] = c->h_pick[0];
-    res[1] = c->h_pick[1];
-    return MFB_OK;
+    return arrived() ? MFB_OK : MFB_ERR_HIP;       // (a kernel that ended without its store: never seen; not a pick to hand out)
 }
 
 extern "C" int mfb_pick_column(mfb_ctx *c, const void *column, int num, int offset, float res[2]) {
     if (!c || !column || !res || num < 1 || offset < 0) return MFB_ERR_ARG;
     if (!c->sum_all) return MFB_ERR_STATE;   // a single column is the whole table only under SUM_ALL_MASKS
     HIPCHK(hipSetDevice(c->device));
-    hipLaunchKernelGGL(k_pick, dim3(1), dim3(64), 0, c->stream, (const float *)column, c->d_res, c->h_pick_dev, num, offset, 1, 1);
+    hipLaunchKernelGGL(k_pick, dim3(1), dim3(64), 0, c->stream, (const float *)column, c->d_res, c->h_pick_dev, ++c->picks, num, offset, 1, 1);
     HIPCHK(hipGetLastError());
     return read_pick(c, res);
 }
@@ -1607,7 +1642,7 @@ extern "C" int mfb_pick(mfb_ctx *c, const void *scores, int num, int offset, flo
     if (!scores && (num != c->D || offset != c->Doff)) return MFB_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
     const float *in = scores ? (const float *)scores : c->d_sum;
-    hipLaunchKernelGGL(k_pick, dim3(1), dim3(64), 0, c->stream, in, c->d_res, c->h_pick_dev, num, offset, c->M, c->sum_all);
+    hipLaunchKernelGGL(k_pick, dim3(1), dim3(64), 0, c->stream, in, c->d_res, c->h_pick_dev, ++c->picks, num, offset, c->M, c->sum_all);
     HIPCHK(hipGetLastError());
     return read_pick(c, res);
 }

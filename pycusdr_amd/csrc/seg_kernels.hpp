@@ -785,9 +785,8 @@ DEVI void segf_body(const SegFArgs &a, const int blk) {
                 const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sv), 32));
                 const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sv), 48));
                 const float total = (r0 + r1) + (r2 + r3);
-                // row 0 carries the bin's sum, the other rows zero: k_finalize adds the rows as it always did
-                if (lane < MU)
-                    a.partials[((size_t)(a.part_row0 + bk * a.dper + jb) * MU + lane) * a.parts + slot] = lane == 0 ? total * a.scale : 0.f;
+                // row 0 carries the bin's sum; the other rows count as zeros and are not written (k_finalize, presum: it does not read them)
+                if (lane == 0) a.partials[((size_t)(a.part_row0 + bk * a.dper + jb) * MU) * a.parts + slot] = total * a.scale;
                 continue;
             }
             // the wave's lanes in seg_body's fixed order: lane (f, j) adds elements j, j + 4, ... of filter f's row, two quad steps

@@ -19,27 +19,39 @@
 // (cuda_kernels.cu:453-464); else per mask (472-475).
 // The partials hold MU <= M rows per bin (filters that are exact copies or exact negatives of an
 // earlier filter are transformed once: |.|^2 is identical bit for bit); rep[m] names filter m's row.
+// presum (the searches that sum a bin's rows in registers: segf_body's SUMQ = 2 form, k_segw): row 0 carries the (bin, slot) sums, and
+// rows >= 1 were written by the masked tail launch alone -- partials tail0 ... parts - 1.  Below tail0 they count as zeros and are NOT
+// read (they may hold anything, an earlier search's sums included).  A chain that adds +0 to a sum that began at +0 leaves it as it
+// is, so the row's sum is the sequence of additions it would be over stored zeros: whole rounds of the four chains below tail0 are
+// skipped, the partials of the round that straddles it are tested one by one.
 #define FIN_MAX_ROWS 64
+template <bool SKIP>
+DEVI float fin_row(const float *p, int parts, int lane, int lo) {
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    int q = lane + (SKIP ? (lo & ~255) : 0);
+    for (; q + 192 < parts; q += 256) {
+        if (!SKIP || q >= lo) a0 += p[q];
+        if (!SKIP || q + 64 >= lo) a1 += p[q + 64];
+        if (!SKIP || q + 128 >= lo) a2 += p[q + 128];
+        if (!SKIP || q + 192 >= lo) a3 += p[q + 192];
+    }
+    for (; q < parts; q += 64) {
+        if (!SKIP || q >= lo) a0 += p[q];
+    }
+    float s = (a0 + a1) + (a2 + a3);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    return s;
+}
 __global__ void __launch_bounds__(1024) k_finalize(const float *partials, float *dsum, int D, int M, int MU, const int *rep, int parts,
-                                                   int sum_all) {
+                                                   int sum_all, int presum, int tail0) {
     __shared__ float srow[FIN_MAX_ROWS];
     const int j = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     if (j >= D) return;
     for (int u = wave; u < MU; u += nw) {
         const float *p = partials + ((size_t)j * MU + u) * parts;
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-        int q = lane;
-        for (; q + 192 < parts; q += 256) {
-            a0 += p[q];
-            a1 += p[q + 64];
-            a2 += p[q + 128];
-            a3 += p[q + 192];
-        }
-        for (; q < parts; q += 64) a0 += p[q];
-        float s = (a0 + a1) + (a2 + a3);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        const float s = (presum && u > 0) ? fin_row<true>(p, parts, lane, tail0) : fin_row<false>(p, parts, lane, 0);
         if (lane == 0) srow[u] = s;
     }
     __syncthreads();
@@ -227,15 +239,19 @@ DEVI void pick_body(const float *in, float *res, int num, int offset, int M, int
         res[1] = 10.f * log10f(__fdiv_rn(sVal[0], (float)M));
     }
 }
-// res: the pick on the device, for the kernels behind it; hres: the same two floats in page-locked host memory (the device's address
-// of it), for the host, which reads them after synchronising the stream -- no copy behind the kernel
-__global__ void __launch_bounds__(64) k_pick(const float *in, float *res, float *hres, int num, int offset, int M, int sum_all) {
+// res: the pick on the device, for the kernels behind it; hres: the handle's 16-byte slot in page-locked, coherent host memory (the
+// device's address of it), for the host -- no copy behind the kernel.  The slot takes {res[0], res[1], count, check} in ONE 16-byte store:
+// count is the number of this pick on the handle, check = count ^ bits(res[0]) ^ bits(res[1]).  The host may read the slot while the
+// kernel still runs (read_pick in mfbank.hip): it takes the two floats when count is the pick it asked for and check fits them, so
+// neither the pick before nor a store seen in pieces passes for this one.
+__global__ void __launch_bounds__(64) k_pick(const float *in, float *res, u32x4 *hres, unsigned count, int num, int offset, int M, int sum_all) {
     __shared__ float sIdx[64], sVal[64];
     __shared__ float scol[PICK_LDS];
     pick_body(in, res, num, offset, M, sum_all, sIdx, sVal, scol);
     if (threadIdx.x == 0) {         // lane 0 wrote res[0..1]: its own stores, read back in program order
-        hres[0] = res[0];
-        hres[1] = res[1];
+        const unsigned b0 = __float_as_uint(res[0]), b1 = __float_as_uint(res[1]);
+        const u32x4 v = {b0, b1, count, count ^ b0 ^ b1};
+        *hres = v;
     }
 }
 

@@ -19,7 +19,7 @@
 // data, scaling the input by 2^k leaves the fp16 operands and the accumulators bit for bit the same and the score scales exactly.
 //
 // Everything else is segf_body's: the XCD-aware groups of the grid, the unmixed forward transform (via the inverse one on swapped
-// samples), the Parseval total from pp = |A|^2 and Q, and the PRESUM store (row 0 carries the (bin, slot) sum, the other rows zero).
+// samples), the Parseval total from pp = |A|^2 and Q, and the PRESUM store (row 0 carries the (bin, slot) sum, the other rows are not written).
 // A bin's number depends on its own tables and the slot's samples only, summed in one fixed order: the same bits whichever bins share
 // the rectangle, whatever the grid or the batch.
 //
@@ -31,6 +31,13 @@
 // then walk the same bins on four slots and share the table fetches in the CU's vector cache, which four chunks of one slot do not.  The loads
 // of a slot are not carried into the next: 32 registers of samples across the bin loop cost more than their latency (r12).
 //
+// The window in LDS (profiles/segw_fixed_costs.md).  A segment's window is 96 samples x 2 components, and a wave's 160 fragment
+// registers read each of them 13 times over.  So the split is made once: when the segment's scale is known (the 16-lane maximum), each
+// lane scales and splits its own 12 components -- ldexp, hi = fp16(v), lo = fp16(v - hi), the operations and the order the fragments
+// always had -- and stores each as one word {hi, lo} into planes [segment][re | im][window index], the bytes the complex window took.
+// A fragment is then eight consecutive words of the lane's plane (ds_read2_b32: word alignment only; the 32 lanes of an access touch 24
+// consecutive words, no bank twice) and one v_perm_b32 per register: the low halves of two neighbours for hi, the high halves for lo.
+//
 // Where the values live and how a step of the bin loop issues (profiles/r13_wrap_issue.md).  With one wave on the SIMD a 16x16x32 MFMA
 // holds the vector issue for 8 of its 16 cycles and every other instruction costs about 4, so a gap between two MFMAs hides two
 // instructions and pays for every further one.  The library is compiled with -mllvm -amdgpu-mfma-vgpr-form (k_segw is its only kernel
@@ -40,7 +47,7 @@
 // step's 108 gaps are then filled by sched_group_barrier: scalar address arithmetic and the row of the bin before (carried as a
 // value and stored ahead of the table fetches, so that no wait at the head of a step covers a store just issued) in the first four,
 // the ten table fetches of the bin after next one to a gap, and the squares, the reduction, the lane sums and the Parseval total of
-// the bins at hand one or two to a gap through all the others.  The row store is a buffer store with the lanes >= MU out of range,
+// the bins at hand one or two to a gap through all the others.  The row store is a buffer store with the lanes >= 1 out of range,
 // in place of a branch; packed fp32 instructions, which cost a gap more than the two they replace, are kept apart by "v" constraints.
 // No operation on a score changed: the same operands in the same order.
 #pragma once
@@ -94,7 +101,8 @@ DEVI void segw_body(const SegWArgs &w, const int blk) {
     const int g = lane % NT;
     const int col = lane / NT;
     cf *mylds = lds + wave * Cfg::LDS_PER_TEAM + col * padlen(L);
-    cf *wlds = lds + Cfg::LDS_ELEMS + wave * CT * WSTR;          // this wave's segment windows
+    // this wave's segment windows, split: [segment][re | im][window index] words {hi, lo} (the bytes of CT * WSTR complex samples)
+    unsigned *wpl = reinterpret_cast<unsigned *>(lds + Cfg::LDS_ELEMS + wave * CT * WSTR);
     F256Regs f256;
     f256_setup(f256, a.twL + L, g);
 
@@ -136,15 +144,19 @@ DEVI void segw_body(const SegWArgs &w, const int blk) {
     const int i16 = lane & 15, q = lane >> 4;
     const bool im_half = q >= 2;
     const int qo = 8 * (q & 1);
+    // ... and the lowest word of its plane that it reads: element 7 of Toeplitz block 0 (window index i16 - qo + 8 with OFF = 16 KT - 1)
+    static_assert(OFF - 16 * (KT - 1) - 7 - 8 >= 0 && 16 * (ND - 1) + 7 + 15 + OFF - 16 * (KT - 1) - 7 < WSTR, "the fragments stay inside a plane");
+    const unsigned *wfrag = wpl + (im_half ? WSTR : 0) + (i16 - qo + OFF - 16 * (KT - 1) - 7);
 
     // the bins' powers of two of the wrap energy, lane j holding bin jb0 + j's: fetched once (the samples' loads wait for it), so that
     // no bin waits for a load at the head of its products
     const bool one_chunk = jb1 - jb0 <= 64;
     int wexl = jb0 + lane < jb1 ? w.Wexp[jb0 + lane] : 0;
-    // the row store (PRESUM: lane 0 the sum, lanes < MU zeros) as a buffer store: bytes from bin to bin, and each lane's offset in a
-    // bin's rows -- lanes >= MU beyond any buffer size, so that the hardware drops them
+    // the row store (PRESUM: lane 0 the sum into row 0; rows >= 1 are not written, k_finalize counts them as zeros without reading
+    // them) as a buffer store: bytes from bin to bin, and each lane's offset -- lanes >= 1 beyond any buffer size, so that the
+    // hardware drops them
     const int pstep = __builtin_amdgcn_readfirstlane(a.MU * a.parts * (int)sizeof(float));
-    const int pvo = lane < a.MU ? lane * a.parts * (int)sizeof(float) : 0x7FFFFFFF;
+    const int pvo = lane == 0 ? 0 : 0x7FFFFFFF;
 
     for (int slot = s0; slot < s1; ++slot) {
         cf v[PPL];
@@ -167,21 +179,22 @@ DEVI void segw_body(const SegWArgs &w, const int blk) {
             }
         }
         // ---- the segment's wrap window -> LDS: sample offsets t in [-(T - 1), L - V) (register slots < RT and >= PPL - KT), zero below
+        // Every sample of the window is scaled and split ONCE, by the lane that holds it, as soon as the segment's scale is known: the
+        // word {hi, lo} goes into the plane [segment][re | im][window index], and the fragments below are reads of those words.
         int ea;
         {
-            cf *myw = wlds + col * WSTR;
+            cf ws[RT + KT];
             float mx = 0.f;
 #pragma unroll
             for (int i = 0; i < RT; ++i) {
-                const cf s = mkc(v[i].y, v[i].x);
-                myw[g + NT * i + OFF] = s;
-                mx = fmaxf(mx, fmaxf(fabsf(s.x), fabsf(s.y)));
+                ws[i] = mkc(v[i].y, v[i].x);
+                mx = fmaxf(mx, fmaxf(fabsf(ws[i].x), fabsf(ws[i].y)));
             }
 #pragma unroll
             for (int i = PPL - KT; i < PPL; ++i) {
                 const int t = g + NT * i - L;
                 const cf s = t >= -(T - 1) ? mkc(v[i].y, v[i].x) : mkc(0.f, 0.f);
-                if (t + OFF >= 0) myw[t + OFF] = s;
+                ws[RT + i - (PPL - KT)] = s;
                 mx = fmaxf(mx, fmaxf(fabsf(s.x), fabsf(s.y)));
             }
             // the segment's largest |component| (its 16 lanes): max is exact in any order
@@ -190,6 +203,26 @@ DEVI void segw_body(const SegWArgs &w, const int blk) {
             int e;
             (void)frexpf(mx, &e);             // mx = f 2^e, f in [0.5, 1): mx 2^(15 - e) in [2^14, 2^15)  (mx = 0: e = 0)
             ea = 15 - e;
+            auto split = [&](float comp) {
+                const float sv = __builtin_ldexpf(comp, ea);
+                const _Float16 h = (_Float16)sv;
+                const _Float16 l = (_Float16)(sv - (float)h);
+                return (unsigned)__builtin_bit_cast(unsigned short, h) | ((unsigned)__builtin_bit_cast(unsigned short, l) << 16);
+            };
+            unsigned *myw = wpl + col * 2 * WSTR;
+#pragma unroll
+            for (int i = 0; i < RT; ++i) {
+                myw[g + NT * i + OFF] = split(ws[i].x);
+                myw[WSTR + g + NT * i + OFF] = split(ws[i].y);
+            }
+#pragma unroll
+            for (int i = PPL - KT; i < PPL; ++i) {
+                const int t = g + NT * i - L;
+                if (t + OFF >= 0) {
+                    myw[t + OFF] = split(ws[RT + i - (PPL - KT)].x);
+                    myw[WSTR + t + OFF] = split(ws[RT + i - (PPL - KT)].y);
+                }
+            }
         }
         xsync<1>();
         cf A[PPL];
@@ -203,24 +236,26 @@ DEVI void segw_body(const SegWArgs &w, const int blk) {
             const cf p0 = A[2 * j] * A[2 * j], p1 = A[2 * j + 1] * A[2 * j + 1];
             pp[j] = mkc(p0.x + p0.y, p1.x + p1.y);
         }
-        // ---- the A fragments of the CT segments: ND Toeplitz blocks each, scaled by 2^ea of the segment and split into hi / lo ----
+        // ---- the A fragments of the CT segments: ND Toeplitz blocks each, from the split window.  Element j of block di is window
+        // index 16 (di - (KT - 1)) + i16 - qo + OFF - j: eight consecutive words of the lane's plane, a register of the hi fragment the
+        // low halves of two neighbours, a register of the lo fragment their high halves ----
         seg_h8 ahi[CT][ND], alo[CT][ND];
         int eseg[CT];
 #pragma unroll
         for (int c = 0; c < CT; ++c) {
             eseg[c] = __builtin_amdgcn_readlane(ea, NT * c);
-            const cf *wc = wlds + c * WSTR;
+            const unsigned *wc = wfrag + c * 2 * WSTR;
 #pragma unroll
             for (int di = 0; di < ND; ++di) {
-                const int base = 16 * (di - (KT - 1)) + i16 - qo + OFF;      // element j: offset t = base - OFF - j
+                u32x4 fh, fl;
 #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const cf s = wc[base - j];
-                    const float sv = __builtin_ldexpf(im_half ? s.y : s.x, eseg[c]);
-                    const _Float16 h = (_Float16)sv;
-                    ahi[c][di][j] = h;
-                    alo[c][di][j] = (_Float16)(sv - (float)h);
+                for (int r = 0; r < 4; ++r) {
+                    const unsigned e0 = wc[16 * di + 7 - 2 * r], e1 = wc[16 * di + 6 - 2 * r];      // elements j = 2 r, 2 r + 1
+                    fh[r] = __builtin_amdgcn_perm(e1, e0, 0x05040100u);
+                    fl[r] = __builtin_amdgcn_perm(e1, e0, 0x07060302u);
                 }
+                ahi[c][di] = __builtin_bit_cast(seg_h8, fh);
+                alo[c][di] = __builtin_bit_cast(seg_h8, fl);
                 asm("" : "+a"(ahi[c][di]));
                 asm("" : "+a"(alo[c][di]));
             }
