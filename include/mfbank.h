@@ -849,6 +849,33 @@ int mfb_channelizer_end(mfb_channelizer *c, float *out_c64);
 int mfb_channelizer_device_output(mfb_channelizer *c, int buffer, int channel, const void **dev_c64, int64_t *nsamples);
 int mfb_channelizer_info(mfb_channelizer *c, int *outputs_per_workgroup, int *taps_capacity);
 int mfb_channelizer_elapsed_ms(mfb_channelizer *c, float *ms);
+/* Rational resampling in the channeliser (csrc/channelize_rational_kernels.hpp): a plan that resamples every channel by U / D
+ * instead of decimating it by D, for capture rates that are no integer multiple of the bank's.  No reference counterpart: the
+ * reference takes one narrowband stream at the bank's own rate (pyCuSDR.py:245-251).
+ * The plan holds an interpolation U = interp and a decimation D = decim, real taps h[0..T) given at the virtual rate U fs, and K
+ * tuning words freq_k, uint64 turns * 2^64 per INPUT sample.  With n the absolute input position and m the absolute output position:
+ *     q(m) = (m D) div U        r(m) = (m D) mod U
+ *     y_k[m] = sum over j >= 0 with r + jU < T of
+ *              h[r + jU] x[q - j] e^{-2 pi i phi_k(q - j) / 2^64}      phi_k(n) = n freq_k mod 2^64,  x[n] = 0 for n < 0
+ * the zero-stuff, filter, keep-every-D-th definition restricted to the products that are not zero, computed as
+ *     e^{-2 pi i phi_k(q) / 2^64} * sum_j g_k[r + jU] x[q - j]        g_k[t] = h[t] e^{+2 pi i phi_k(t div U) / 2^64}
+ * which is exact because phi_k is linear in integers.  One lane makes one output; the sum starts from (-0, -0); terms are added in
+ * the order j = 0, 1, ...: for each tap the x.re terms, then the x.im terms; freq_k == 0 uses h itself with one real multiply-add
+ * per component and is not rotated; a rotation word of 0 multiplies nothing.  A branch runs its own ceil((T - r) / U) taps and no
+ * padded ones.  y_k[m] is a pure function of (h, U, D, freq_k, the samples it reads, m): any cut of a span, any input window that
+ * covers it, any other channels in the plan and either output set give the same bits.  With U = 1 the definition is
+ * mfb_channelizer_set_plan's and the bits are the same, but this call always selects the rational kernel, also at interp = 1;
+ * mfb_channelizer_set_plan keeps its own.
+ * Every other call of the handle works as above under such a plan, with two differences.  mfb_channelizer_begin: the outputs
+ * [out_base, out_base + out_count) read the inputs [q(out_base) - (ceil(T / U) - 1), q(out_base + out_count - 1)] -- the uniform
+ * bound, one sample generous for short branches -- which must all lie inside [in_base, in_base + in_count), apart from positions
+ * below 0, which read as zero: MFB_ERR_ARG otherwise.  mfb_channelizer_info: outputs_per_workgroup is the number of consecutive
+ * outputs one workgroup makes, U times 64, 128 or 256.
+ * Limits (MFB_ERR_UNSUPPORTED beyond): 1 <= U <= 32, 2 <= D <= 64, T <= 1024, 1..16 channels, 2^24 inputs and 2^22 outputs per call,
+ * in_base and out_base D < 2^62.  MFB_ERR_ARG: a common factor of U and D, U >= D (net rate reduction only), T < U (every branch
+ * has at least one tap), and everything mfb_channelizer_set_plan refuses with it.  Misuse is an error code, never a fault. */
+int mfb_channelizer_set_plan_rational(mfb_channelizer *c, int interp, int decim, const float *taps, int ntaps, const uint64_t *freq_words,
+                                      int nchan, int sample_format, float sample_scale);
 
 /* Test seams of the demodulation tail: the three kernels between the matched filters and the bit stream, launched as the product
  * launches them, on INJECTED inputs (tests/test_gpu_demod_tail.py).  Handle-less: device buffers of their own, a synchronous copy

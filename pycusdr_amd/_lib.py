@@ -224,6 +224,7 @@ PROTOTYPES = {
     'mfb_channelizer_device_output': (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(C.c_int64)]),
     'mfb_channelizer_info': (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     'mfb_channelizer_elapsed_ms': (_i, [_vp, _fp]),
+    'mfb_channelizer_set_plan_rational': (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _i, C.c_float]),
     'mfb_timer_start': (_i, [_vp]),
     'mfb_timer_stop': (_i, [_vp, _fp]),
     'mfb_profile_enable': (_i, [_vp, _i]),

@@ -14,8 +14,30 @@ channel's tuning word (uint64 turns * 2**64 per input sample, a negative frequen
 is asked for in and whatever input window covers them, bit for bit.  ``backend='hip'`` is the mfb_channelizer_* handle of
 include/mfbank.h (csrc/channelize_kernels.hpp has the rules); ``backend='host'`` is the model: exactly the sum above, mix first, in
 float64 on exact uint64 words, rounded to complex64 at the end -- the yardstick for the device.
+
+Rational resampling (``interp = U > 1``; mfb_channelizer_set_plan_rational, csrc/channelize_rational_kernels.hpp).  A plan holds an
+interpolation ``U`` and a decimation ``D`` (1 <= U <= 32, 2 <= D <= 64, gcd(U, D) = 1, U < D: net rate reduction only), real taps
+``h[0..T)`` given at the virtual rate ``U * fs`` (U <= T <= 1024) and the K words, still per INPUT sample:
+
+    q(m) = (m D) div U        r(m) = (m D) mod U
+    y_k[m] = sum over j >= 0 with r + jU < T of
+             h[r + jU] x[q - j] exp(-2 pi i phi_k(q - j) / 2**64)       phi_k(n) = n freq_k mod 2**64,  x[n] = 0 for n < 0
+
+the zero-stuff, filter, keep-every-D-th definition restricted to the products that are not zero.  The device computes it as
+``exp(-2 pi i phi_k(q) / 2**64) * sum_j g_k[r + jU] x[q - j]`` with ``g_k[t] = h[t] exp(+2 pi i phi_k(t div U) / 2**64)``, exact
+because phi_k is linear in integers.  One lane makes one output; the sum starts from (-0, -0); terms are added in the order
+j = 0, 1, ...: for each tap the x.re terms, then the x.im terms; ``freq_k == 0`` uses h itself with one real multiply-add per
+component and is not rotated; a rotation word of 0 multiplies nothing.  A branch runs its own ``ceil((T - r) / U)`` taps and no
+padded ones.  ``y_k[m]`` stays a pure function of (h, U, D, freq_k, the samples it reads, m).  With ``U = 1`` the definition is the
+one above, and ``Channelizer(...)`` without ``interp`` keeps running the integer kernel.  A call's outputs
+``[out_base, out_base + out_count)`` read inputs ``[q(out_base) - (ceil(T / U) - 1), q(out_base + out_count - 1)]``, the uniform
+bound, one sample generous for short branches.  ``factor_rate`` splits a ratio outside the limits into stages; a second stage is an
+ordinary ``Channelizer`` with ``freqs_hz=[0.0]`` fed the first stage's ``device_output`` pointer.
 """
 import ctypes as C
+import functools
+import math
+from fractions import Fraction
 
 import numpy as np
 
@@ -25,28 +47,35 @@ from .modulator import phase
 
 _U = np.uint64
 MAX_CHANNELS, MAX_DECIM, MAX_TAPS, MAX_IN, MAX_OUT = 16, 64, 1024, 1 << 24, 1 << 22
+MAX_INTERP = 32
 FORMATS = {'cf32': 0, 'sc16': 1, 'sc8': 2}           # MFB_SAMPLES_* of include/mfbank.h
 _RAW = {'sc16': np.int16, 'sc8': np.int8}
 INPUT_PINNED0, INPUT_PINNED1, INPUT_DEVICE = 0, 1, 2
 
 
-def design_taps(decim, taps_per_phase=16, beta=8.0, cutoff=0.4):
+def design_taps(decim, taps_per_phase=16, beta=8.0, cutoff=0.4, interp=1):
     """A Kaiser-windowed sinc low-pass for a decimation by ``decim``: ``T = decim * taps_per_phase + 1`` taps, float32, cutoff
     (the -6 dB point) at ``cutoff / decim`` cycles per input sample, unit gain at DC.  The taps are symmetric: the group delay is
-    ``(T - 1) / 2`` input samples, ``taps_per_phase / 2`` output samples."""
-    decim, taps_per_phase = int(decim), int(taps_per_phase)
-    if decim < 1 or taps_per_phase < 1 or not 0 < cutoff <= 0.5:
-        raise ValueError('decim >= 1, taps_per_phase >= 1, 0 < cutoff <= 0.5')
+    ``(T - 1) / 2`` input samples, ``taps_per_phase / 2`` output samples.  With ``interp = U > 1`` the same taps stand at the
+    virtual rate ``U * fs`` of a resampling by U / decim: cutoff at ``cutoff / decim`` cycles per virtual sample, that is ``cutoff``
+    cycles per output sample; they sum to U, so every branch has about unit gain and the pass-band gain is 1; the group delay is
+    ``(T - 1) / (2 U)`` input samples."""
+    decim, taps_per_phase, interp = int(decim), int(taps_per_phase), int(interp)
+    if decim < 1 or taps_per_phase < 1 or interp < 1 or not 0 < cutoff <= 0.5:
+        raise ValueError('decim >= 1, taps_per_phase >= 1, interp >= 1, 0 < cutoff <= 0.5')
     T = decim * taps_per_phase + 1
     fc = cutoff / decim
     n = np.arange(T, dtype=np.float64) - (T - 1) / 2
     h = 2 * fc * np.sinc(2 * fc * n) * np.kaiser(T, beta)
-    return (h / h.sum()).astype(np.float32)
+    if interp == 1:
+        return (h / h.sum()).astype(np.float32)
+    return (h * (interp / h.sum())).astype(np.float32)
 
 
-def check_plan(decim, taps, words, sample_format, sample_scale):
-    """The checks of mfb_channelizer_set_plan, as ValueError: (decim, taps float32, words uint64, scale)."""
-    decim = int(decim)
+def check_plan(decim, taps, words, sample_format, sample_scale, interp=1):
+    """The checks of mfb_channelizer_set_plan and, for ``interp``, of mfb_channelizer_set_plan_rational, as ValueError: (decim,
+    taps float32, words uint64, scale)."""
+    decim, interp = int(decim), int(interp)
     taps = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
     words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
     if not 2 <= decim <= MAX_DECIM:
@@ -55,6 +84,12 @@ def check_plan(decim, taps, words, sample_format, sample_scale):
         raise ValueError(f'1 .. {MAX_TAPS} finite taps')
     if not 1 <= len(words) <= MAX_CHANNELS:
         raise ValueError(f'1 .. {MAX_CHANNELS} channels')
+    if not 1 <= interp <= MAX_INTERP:
+        raise ValueError(f'1 <= interp <= {MAX_INTERP}')
+    if interp >= decim or math.gcd(interp, decim) != 1:
+        raise ValueError('interp < decim, and the two have no common factor')
+    if len(taps) < interp:
+        raise ValueError('at least interp taps: every branch has one')
     if sample_format not in FORMATS:
         raise ValueError(f'sample_format is one of {sorted(FORMATS)}')
     scale = float(sample_scale)
@@ -63,6 +98,39 @@ def check_plan(decim, taps, words, sample_format, sample_scale):
         if not (np.isfinite(scale) and scale > 0 and m == 0.5 and -100 < e < 100):
             raise ValueError('sample_scale is a power of two')
     return decim, taps, words, scale
+
+
+def factor_rate(fs_in, fs_out):
+    """The stages ``[(U_1, D_1), ...]`` that take ``fs_in`` to ``fs_out``: each within a plan's limits (1 <= U <= 32, 2 <= D <= 64,
+    U < D, no common factor; an integer stage is ``(1, D)``), the product of the U_i / D_i exactly ``fs_out / fs_in`` (taken with
+    ``fractions.Fraction``; the U_i multiply to its numerator and the D_i to its denominator).  The fewest stages; among lists of
+    equal length the largest rate reduction goes to the first stage, then to the second, and so on.  ValueError where no such list
+    exists: a ratio >= 1, a prime factor of the denominator above 64 or of the numerator above 32."""
+    ratio = Fraction(fs_out) / Fraction(fs_in)
+    u, d = ratio.numerator, ratio.denominator
+    if not 0 < ratio < 1:
+        raise ValueError('0 < fs_out < fs_in: net rate reduction only')
+
+    def stages_of(u, d):
+        # (U, D) is coprime whenever U | u and D | d, because u / d is in lowest terms
+        return [(a, b) for b in range(2, MAX_DECIM + 1) if d % b == 0 for a in range(1, min(b, MAX_INTERP + 1)) if u % a == 0]
+
+    @functools.lru_cache(maxsize=None)
+    def split(u, d, n):
+        """The best list of exactly n stages for u / d, or None."""
+        if n == 1:
+            return [(u, d)] if u <= MAX_INTERP and 2 <= d <= MAX_DECIM and u < d else None
+        for a, b in sorted(stages_of(u, d), key=lambda s: Fraction(s[0], s[1])):
+            rest = split(u // a, d // b, n - 1)
+            if rest is not None:
+                return [(a, b)] + rest
+        return None
+
+    for n in range(1, d.bit_length() + 1):                  # every stage at least halves the denominator
+        got = split(u, d, n)
+        if got is not None:
+            return got
+    raise ValueError(f'{u}/{d} is no product of stages U / D with U <= {MAX_INTERP}, D <= {MAX_DECIM}, U < D')
 
 
 def samples_to_c64(samples, sample_format, scale):
@@ -76,7 +144,9 @@ def samples_to_c64(samples, sample_format, scale):
 
 class Channelizer:
     def __init__(self, fs, decim, taps, freqs_hz, sample_format='cf32', sample_scale=1.0, backend='hip', device=0, max_in=1 << 20,
-                 max_out=None):
+                 max_out=None, interp=1, force_rational=False):
+        """``interp = U``: resample by U / decim (the module docstring); 1 takes the integer kernel, unless ``force_rational``
+        (the tests' seam) sends that plan through the rational kernel too."""
         if backend not in ('hip', 'host'):
             raise ValueError("backend is 'hip' or 'host'")
         self.fs, self.backend, self.device = float(fs), backend, device
@@ -85,10 +155,13 @@ class Channelizer:
             raise ValueError('|freq| <= fs / 2')
         self.freqs_hz = freqs
         self.decim, self.taps, self.words, self.scale = check_plan(decim, taps, signed_quantise(phase.TWO_PI * freqs / self.fs),
-                                                                   sample_format, sample_scale)
+                                                                   sample_format, sample_scale, interp)
+        self.interp = int(interp)
+        self.rational = self.interp > 1 or bool(force_rational)
         self.sample_format, self.T, self.K = sample_format, len(self.taps), len(self.words)
+        self.Tb = -(-self.T // self.interp)                   # taps of the longest branch
         self.max_in = int(max_in)
-        self.max_out = int(max_out) if max_out is not None else max(1, -(-self.max_in // self.decim))
+        self.max_out = int(max_out) if max_out is not None else max(1, -(-self.max_in * self.interp // self.decim))
         if not (1 <= self.max_in <= MAX_IN and 1 <= self.max_out <= MAX_OUT):
             raise ValueError('1 <= max_in <= 2**24, 1 <= max_out <= 2**22')
         self._buffer, self._which, self._pinned = 1, 1, [None, None]
@@ -97,8 +170,13 @@ class Channelizer:
             self.lib = _lib.load()
             _lib.check(self.lib.mfb_channelizer_create(C.byref(self.h), device, self.K, self.T, self.max_in, self.max_out),
                        'mfb_channelizer_create')
-            _lib.check(self.lib.mfb_channelizer_set_plan(self.h, self.decim, self.taps.ctypes.data, self.T, self.words.ctypes.data, self.K,
-                                                         FORMATS[sample_format], self.scale), 'mfb_channelizer_set_plan')
+            if self.rational:
+                _lib.check(self.lib.mfb_channelizer_set_plan_rational(self.h, self.interp, self.decim, self.taps.ctypes.data, self.T,
+                                                                      self.words.ctypes.data, self.K, FORMATS[sample_format], self.scale),
+                           'mfb_channelizer_set_plan_rational')
+            else:
+                _lib.check(self.lib.mfb_channelizer_set_plan(self.h, self.decim, self.taps.ctypes.data, self.T, self.words.ctypes.data,
+                                                             self.K, FORMATS[sample_format], self.scale), 'mfb_channelizer_set_plan')
 
     def close(self):
         if self.h:
@@ -124,12 +202,13 @@ class Channelizer:
         return ms.value
 
     def needed_input(self, out_base, out_count):
-        """(in_base, in_count): the input positions that outputs out_base .. out_base + out_count read, clipped at 0."""
+        """(in_base, in_count): the input positions that outputs out_base .. out_base + out_count read, clipped at 0: from
+        ``q(out_base) - (ceil(T / U) - 1)`` to ``q(out_base + out_count - 1)`` with ``q(m) = (m D) div U``."""
         out_base, out_count = int(out_base), int(out_count)
         if out_base < 0 or out_count < 1:
             raise ValueError('out_base >= 0, out_count >= 1')
-        first = max(0, out_base * self.decim - (self.T - 1))
-        last = (out_base + out_count - 1) * self.decim
+        first = max(0, out_base * self.decim // self.interp - (self.Tb - 1))
+        last = (out_base + out_count - 1) * self.decim // self.interp
         return first, last - first + 1
 
     def _checked(self, in_base, in_count, out_base, out_count):
@@ -217,10 +296,13 @@ class Channelizer:
 
     def model(self, in_base, samples, out_base, out_count):
         """The definition in float64, mix first, before rounding: (y complex128 [K, out_count], S float64 [out_count]) with
-        ``S[m] = sum_t |h[t]| |x[m D - t]|``, the scale of the device's error bound."""
+        ``S[m] = sum_t |h[t]| |x[m D - t]|`` (``sum_j |h[r + jU]| |x[q - j]|`` when resampling), the scale of the device's error
+        bound."""
         in_base, out_base, out_count = int(in_base), int(out_base), int(out_count)
         x = samples_to_c64(samples, self.sample_format, self.scale).astype(np.complex128)
         self._checked(in_base, len(x), out_base, out_count)
+        if self.interp > 1:
+            return self._model_rational(in_base, x, out_base, out_count)
         D, T = self.decim, self.T
         first = out_base * D - (T - 1)                      # may be negative: those positions read as zero
         span = (out_count - 1) * D + T
@@ -240,6 +322,34 @@ class Channelizer:
                 z[lo - first:] = np.where(w == 0, seg[lo - first:], seg[lo - first:] * phase.words_to_iq(w))
             y[k] = win(z, T)[::D] @ hrev                   # row j: z[j D .. j D + T - 1], tap t at j D + T - 1 - t
         S = win(np.abs(seg), T)[::D] @ np.abs(hrev)
+        return y, S
+
+    def _model_rational(self, in_base, x, out_base, out_count):
+        """``model`` for U > 1: the sum of the definition, tap by tap, over the mixed stream."""
+        U, D, T = self.interp, self.decim, self.T
+        md = (out_base + np.arange(out_count, dtype=np.int64)) * D
+        q, r = md // U, md % U
+        first = int(q[0]) - (self.Tb - 1)                   # may be negative: those positions read as zero
+        lo = max(first, 0)
+        seg = np.zeros(int(q[-1]) - first + 1, dtype=np.complex128)
+        seg[lo - first:] = x[lo - in_base:int(q[-1]) + 1 - in_base]
+        n = np.arange(lo, int(q[-1]) + 1, dtype=np.int64).astype(np.uint64)
+        z = np.empty((self.K, len(seg)), dtype=np.complex128)
+        for k, f in enumerate(self.words):
+            z[k] = seg
+            if f != 0:
+                with np.errstate(over='ignore'):
+                    w = _U(0) - n * _U(f)                   # -phi_k(n), exact
+                z[k, lo - first:] = np.where(w == 0, seg[lo - first:], seg[lo - first:] * phase.words_to_iq(w))
+        h = np.r_[self.taps.astype(np.float64), np.zeros(U)]      # (a branch's taps beyond T count as absent: they add exact zeros)
+        mag = np.abs(seg)
+        at = q - first
+        y = np.zeros((self.K, out_count), dtype=np.complex128)
+        S = np.zeros(out_count, dtype=np.float64)
+        for j in range(self.Tb):
+            t = np.minimum(r + j * U, T)
+            y += h[t] * z[:, at - j]
+            S += np.abs(h[t]) * mag[at - j]
         return y, S
 
 
@@ -282,7 +392,11 @@ class ChannelizerSource:
             raise ValueError(f'channel {k} of {channelizer.K}')
         if self.stride < 1 or self.B < 1 or self.nwindows < 0:
             raise ValueError('0 <= overlap < N, blocks_per_call >= 1, nwindows >= 0')
-        if self.count > channelizer.max_out or channelizer.needed_input(0, self.count)[1] + channelizer.T - 1 > channelizer.max_in:
+        # the longest input a window reads: one whose first output is far enough from 0 that nothing is clipped, in every phase
+        # of its base modulo U (an integer plan has one: (count - 1) D + T)
+        far = channelizer.T
+        need = max(channelizer.needed_input(far + i, self.count)[1] for i in range(channelizer.interp))
+        if self.count > channelizer.max_out or need > channelizer.max_in:
             raise ValueError(f'a window has {self.count} outputs: more than the channeliser was created for')
 
     def window_base(self, w):

@@ -63,6 +63,7 @@
 #include "mod_kernels.hpp"
 #include "channel_kernels.hpp"
 #include "channelize_kernels.hpp"
+#include "channelize_rational_kernels.hpp"
 #include "energy_kernels.hpp"
 #include "stream_kernels.hpp"
 #include "clip_kernels.hpp"
@@ -4103,9 +4104,13 @@ struct mfb_channelizer {
     DevBuf<float> d_h;
     DevBuf<ChzPlan> d_plan;
     DevBuf<float2> d_taps;     // [max_channels][max_taps]
+    DevBuf<float2> d_rtaps;    // a rational plan's tables by branch, [max_channels][rtap_stride], on demand
     DevBuf<float2> d_out[2];   // [max_channels][out_stride]
     bool have_plan = false, busy = false;
     int D = 0, T = 0, K = 0, fmt = 0, ncplx = 0, threads = 0, L = 0;
+    bool rational = false;     // the plan in force runs k_chzr (mfb_channelizer_set_plan_rational), also at U = 1
+    int U = 1, Tb = 0;         // its interpolation and ceil(T / U)
+    int rtap_stride = 0;       // max_taps + CHZR_MAX_INTERP - 1 >= U Tb
     float scale = 1.0f;
     int cur = 0;               // the buffer of the call in flight
     int count[2] = {0, 0};     // 0: never written
@@ -4160,9 +4165,14 @@ extern "C" int mfb_channelizer_create(mfb_channelizer **out, int device, int max
     });
 }
 
-static int chz_set_plan_body(mfb_channelizer *c, int decim, const float *taps, int ntaps, const uint64_t *freq_words, int nchan, int fmt,
-                             float scale) {
+static int chz_set_plan_body(mfb_channelizer *c, bool rational, int interp, int decim, const float *taps, int ntaps, const uint64_t *freq_words,
+                             int nchan, int fmt, float scale) {
     HIPCHK(hipSetDevice(c->device));
+    const int Tb = chzr_branch_taps(interp, ntaps);
+    if (rational && !c->d_rtaps) {
+        c->rtap_stride = c->max_taps + CHZR_MAX_INTERP - 1;
+        HIPCHK(c->d_rtaps.alloc((size_t)c->max_channels * c->rtap_stride * sizeof(float2), hip_malloc));
+    }
     ChzPlan P;
     memset(&P, 0, sizeof(P));
     int ncplx = 0, at = 0;
@@ -4176,8 +4186,12 @@ static int chz_set_plan_body(mfb_channelizer *c, int decim, const float *taps, i
     c->have_plan = false;
     HIPCHK(hipMemcpyAsync(c->d_h, taps, (size_t)ntaps * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->d_plan, &P, sizeof(P), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_chz_taps, dim3((ntaps + 255) / 256, nchan), dim3(256), 0, c->stream, (const float *)c->d_h, (const ChzPlan *)c->d_plan,
-                       ntaps, c->max_taps, c->d_taps.get());
+    if (rational)
+        hipLaunchKernelGGL(k_chzr_taps, dim3((interp * Tb + 255) / 256, nchan), dim3(256), 0, c->stream, (const float *)c->d_h,
+                           (const ChzPlan *)c->d_plan, interp, ntaps, Tb, c->rtap_stride, c->d_rtaps.get());
+    else
+        hipLaunchKernelGGL(k_chz_taps, dim3((ntaps + 255) / 256, nchan), dim3(256), 0, c->stream, (const float *)c->d_h, (const ChzPlan *)c->d_plan,
+                           ntaps, c->max_taps, c->d_taps.get());
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));       // (taps and P are the caller's and this frame's)
     c->D = decim;
@@ -4186,18 +4200,32 @@ static int chz_set_plan_body(mfb_channelizer *c, int decim, const float *taps, i
     c->fmt = fmt;
     c->scale = scale;
     c->ncplx = ncplx;
-    c->threads = chz_threads(decim, ntaps);
-    c->L = chz_row_len(c->threads, decim, ntaps);
+    c->rational = rational;
+    c->U = interp;
+    c->Tb = Tb;
+    c->threads = rational ? chzr_threads(interp, decim, ntaps) : chz_threads(decim, ntaps);
+    c->L = rational ? chzr_row_len(c->threads, interp, decim, ntaps) : chz_row_len(c->threads, decim, ntaps);
     c->count[0] = c->count[1] = 0;                 // what the buffers hold belongs to the plan before
     c->have_plan = true;
     return MFB_OK;
 }
 
-extern "C" int mfb_channelizer_set_plan(mfb_channelizer *c, int decim, const float *taps, int ntaps, const uint64_t *freq_words, int nchan,
-                                        int sample_format, float sample_scale) {
+static int chz_set_plan(mfb_channelizer *c, bool rational, int interp, int decim, const float *taps, int ntaps, const uint64_t *freq_words,
+                        int nchan, int sample_format, float sample_scale) {
     if (!c || !taps || !freq_words || ntaps < 1 || nchan < 1) return MFB_ERR_ARG;
     if (sample_format != MFB_SAMPLES_CF32 && sample_format != MFB_SAMPLES_SC16 && sample_format != MFB_SAMPLES_SC8) return MFB_ERR_ARG;
     if (decim < 2 || decim > CHZ_MAX_DECIM || ntaps > CHZ_MAX_TAPS || nchan > CHZ_MAX_CHANNELS) return MFB_ERR_UNSUPPORTED;
+    if (interp < 1 || interp > CHZR_MAX_INTERP) return MFB_ERR_UNSUPPORTED;
+    if (interp >= decim || ntaps < interp) return MFB_ERR_ARG;
+    for (int a = decim, b = interp;;) {              // gcd(U, D) = 1
+        const int r = a % b;
+        if (!r) {
+            if (b != 1) return MFB_ERR_ARG;
+            break;
+        }
+        a = b;
+        b = r;
+    }
     if (ntaps > c->max_taps || nchan > c->max_channels) return MFB_ERR_ARG;
     float scale = 1.0f;
     if (sample_format != MFB_SAMPLES_CF32) {
@@ -4207,7 +4235,17 @@ extern "C" int mfb_channelizer_set_plan(mfb_channelizer *c, int decim, const flo
     for (int t = 0; t < ntaps; ++t)
         if (!std::isfinite(taps[t])) return MFB_ERR_ARG;
     if (c->busy) return MFB_ERR_STATE;
-    return guarded([&] { return chz_set_plan_body(c, decim, taps, ntaps, freq_words, nchan, sample_format, scale); });
+    return guarded([&] { return chz_set_plan_body(c, rational, interp, decim, taps, ntaps, freq_words, nchan, sample_format, scale); });
+}
+
+extern "C" int mfb_channelizer_set_plan(mfb_channelizer *c, int decim, const float *taps, int ntaps, const uint64_t *freq_words, int nchan,
+                                        int sample_format, float sample_scale) {
+    return chz_set_plan(c, false, 1, decim, taps, ntaps, freq_words, nchan, sample_format, sample_scale);
+}
+
+extern "C" int mfb_channelizer_set_plan_rational(mfb_channelizer *c, int interp, int decim, const float *taps, int ntaps,
+                                                 const uint64_t *freq_words, int nchan, int sample_format, float sample_scale) {
+    return chz_set_plan(c, true, interp, decim, taps, ntaps, freq_words, nchan, sample_format, sample_scale);
 }
 
 extern "C" int mfb_channelizer_input_buffer(mfb_channelizer *c, int which, void **host, size_t *bytes) {
@@ -4225,8 +4263,20 @@ extern "C" int mfb_channelizer_input_buffer(mfb_channelizer *c, int which, void 
 extern "C" int mfb_channelizer_info(mfb_channelizer *c, int *outputs_per_workgroup, int *taps_capacity) {
     if (!c) return MFB_ERR_ARG;
     if (!c->have_plan) return MFB_ERR_STATE;
-    if (outputs_per_workgroup) *outputs_per_workgroup = c->threads;
+    if (outputs_per_workgroup) *outputs_per_workgroup = c->rational ? c->U * c->threads : c->threads;
     if (taps_capacity) *taps_capacity = c->max_taps;
+    return MFB_OK;
+}
+
+// behind the launch of either kernel
+static int chz_begun(mfb_channelizer *c, const mfb_channelizer_params *p) {
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->t1, c->stream));
+    HIPCHK(hipEventRecord(c->done, c->stream));
+    c->cur = p->buffer;
+    c->count[p->buffer] = p->out_count;
+    c->nchan[p->buffer] = c->K;
+    c->busy = true;
     return MFB_OK;
 }
 
@@ -4239,6 +4289,38 @@ static int chz_begin_body(mfb_channelizer *c, const mfb_channelizer_params *p) {
         if (!c->d_in[w]) HIPCHK(c->d_in[w].alloc((size_t)c->max_in * sizeof(float2), hip_malloc));
         HIPCHK(hipMemcpyAsync(c->d_in[w], c->h_in[w], (size_t)p->in_count * sb, hipMemcpyHostToDevice, c->stream));
         raw = c->d_in[w].get();
+    }
+    c->count[p->buffer] = 0;
+    HIPCHK(hipEventRecord(c->t0, c->stream));
+    if (c->rational) {
+        ChzrArgs R;
+        R.in_base = p->in_base;
+        R.in_end = p->in_base + p->in_count;
+        R.out_base = p->out_base;
+        R.out_count = p->out_count;
+        R.U = c->U;
+        R.D = c->D;
+        R.T = c->T;
+        R.Tb = c->Tb;
+        R.L = c->L;
+        R.S = chzr_span(c->threads, c->U, c->D, c->T);
+        R.rD = 1.0f / (float)c->D;
+        R.tap_stride = c->rtap_stride;
+        R.out_stride = c->out_stride;
+        R.ncplx = c->ncplx;
+        R.nreal = c->K - c->ncplx;
+        R.scale = c->scale;
+        const int tile = c->U * c->threads;
+        const dim3 rgrid((unsigned)((p->out_count + tile - 1) / tile)), rblock(c->threads);
+        const size_t rlds = (size_t)c->D * c->L * sizeof(float2);
+#define CHZR_LAUNCH(FMT_)                                                                                                                \
+    hipLaunchKernelGGL(k_chzr<FMT_>, rgrid, rblock, rlds, c->stream, R, (const ChzPlan *)c->d_plan, raw, (const float2 *)c->d_rtaps, \
+                       c->d_out[p->buffer].get())
+        if (c->fmt == MFB_SAMPLES_SC16) CHZR_LAUNCH(CHZ_FMT_SC16);
+        else if (c->fmt == MFB_SAMPLES_SC8) CHZR_LAUNCH(CHZ_FMT_SC8);
+        else CHZR_LAUNCH(CHZ_FMT_CF32);
+#undef CHZR_LAUNCH
+        return chz_begun(c, p);
     }
     ChzArgs A;
     A.in_base = p->in_base;
@@ -4256,8 +4338,6 @@ static int chz_begin_body(mfb_channelizer *c, const mfb_channelizer_params *p) {
     A.scale = c->scale;
     const dim3 grid((unsigned)((p->out_count + c->threads - 1) / c->threads)), block(c->threads);
     const size_t lds = (size_t)c->D * c->L * sizeof(float2);
-    c->count[p->buffer] = 0;
-    HIPCHK(hipEventRecord(c->t0, c->stream));
 #define CHZ_LAUNCH(FMT_)                                                                                                              \
     hipLaunchKernelGGL(k_chz<FMT_>, grid, block, lds, c->stream, A, (const ChzPlan *)c->d_plan, raw, (const float2 *)c->d_taps, \
                        c->d_out[p->buffer].get())
@@ -4265,14 +4345,7 @@ static int chz_begin_body(mfb_channelizer *c, const mfb_channelizer_params *p) {
     else if (c->fmt == MFB_SAMPLES_SC8) CHZ_LAUNCH(CHZ_FMT_SC8);
     else CHZ_LAUNCH(CHZ_FMT_CF32);
 #undef CHZ_LAUNCH
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->t1, c->stream));
-    HIPCHK(hipEventRecord(c->done, c->stream));
-    c->cur = p->buffer;
-    c->count[p->buffer] = p->out_count;
-    c->nchan[p->buffer] = c->K;
-    c->busy = true;
-    return MFB_OK;
+    return chz_begun(c, p);
 }
 
 extern "C" int mfb_channelizer_begin(mfb_channelizer *c, const mfb_channelizer_params *p) {
@@ -4288,7 +4361,8 @@ extern "C" int mfb_channelizer_begin(mfb_channelizer *c, const mfb_channelizer_p
     if (p->input == MFB_CHZ_INPUT_DEVICE && ((uintptr_t)p->device_input & (chz_sample_bytes(c->fmt) - 1))) return MFB_ERR_ARG;
     if (p->input != MFB_CHZ_INPUT_DEVICE && !c->h_in[p->input == MFB_CHZ_INPUT_PINNED1]) return MFB_ERR_STATE;
     // every input an output reads, apart from the positions below 0, lies inside the call's input
-    const int64_t first = p->out_base * c->D - (c->T - 1), last = (p->out_base + p->out_count - 1) * c->D;
+    // (a rational plan: [q(out_base) - (ceil(T / U) - 1), q(out_base + out_count - 1)], q(m) = (m D) div U; U = 1 otherwise)
+    const int64_t first = p->out_base * c->D / c->U - (c->Tb - 1), last = (p->out_base + p->out_count - 1) * c->D / c->U;
     if ((first > 0 ? first : 0) < p->in_base || last >= p->in_base + p->in_count) return MFB_ERR_ARG;
     return guarded([&] { return chz_begin_body(c, p); });
 }
