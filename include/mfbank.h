@@ -876,6 +876,37 @@ int mfb_channelizer_elapsed_ms(mfb_channelizer *c, float *ms);
  * has at least one tap), and everything mfb_channelizer_set_plan refuses with it.  Misuse is an error code, never a fault. */
 int mfb_channelizer_set_plan_rational(mfb_channelizer *c, int interp, int decim, const float *taps, int ntaps, const uint64_t *freq_words,
                                       int nchan, int sample_format, float sample_scale);
+/* The uniform polyphase channeliser (csrc/channelize_uniform_kernels.hpp): the channels of a raster, bin k of M centred on k fs / M,
+ * all made by one M-point transform per output frame instead of one T-tap filter per channel.  No reference counterpart: the
+ * reference takes one narrowband stream per radio process (pyCuSDR.py:245-251).
+ * The definition is mfb_channelizer_set_plan's with the exact words freq_k = k 2^64 / M (M a power of two), for which it collapses:
+ *     y_k[m] = sum_{t < T} h[t] x[m D - t] e^{-2 pi i k (m D - t) / M}                   x[n] = 0 for n < 0
+ *            = sum_{s < M} v_m[s] e^{+2 pi i k s / M}
+ *     u_m[p] = sum_{j : p + j M < T} h[p + j M] x[m D - p - j M]        p = 0 .. M - 1   (M branch sums, real taps)
+ *     v_m[s] = u_m[(s + m D) mod M]                                                      (a circular shift, no multiply)
+ * A branch sum starts from (-0, -0) and adds its terms in the order j = 0, 1, ..., one fused multiply-add per component and tap,
+ * exactly the taps with p + j M < T; the transform's order of operations is a function of M alone.  So y_k[m] is a pure function of
+ * (h, D, M, the T samples it reads, m): any cut of a span, any input window that covers it, any selection of bins and either
+ * output set give the same bits.  Against the float64 definition every component is within (ceil(T / M) + 3 log2 M + 2) 2^-24 S_m,
+ * S_m = sum_t |h[t]| |x[m D - t]|.  Adjacent bins overlap as the taps dictate; D need not divide M, critical sampling is D = M.
+ *   mfb_channelizer_create_uniform    a handle of the same type for nbins = M bins of which at most max_selected are written: a
+ *                                     stream, two output sets of max_selected x max_out complex64, the taps.
+ *   mfb_channelizer_set_plan_uniform  D, the taps, the selected bins (indices in [0, M), in the order of the output's rows, no
+ *                                     duplicates), the sample format and scale as mfb_channelizer_set_plan; waits.
+ * Every other call works on such a handle as above: _input_buffer; _begin with the required-input rule of mfb_channelizer_set_plan,
+ * [out_base D - (T - 1), (out_base + out_count - 1) D]; _end, which returns [nselected][out_count]; _device_output, where `channel`
+ * indexes the selection; _elapsed_ms; _destroy; _info, where outputs_per_workgroup is F, the consecutive frames a workgroup makes
+ * (a multiple of 16 up to 128 wherever 64 KiB of LDS hold them, else 8 or 4), and taps_capacity is max_taps.
+ * The two kinds of plan do not mix, MFB_ERR_STATE: mfb_channelizer_set_plan or _set_plan_rational on a handle of
+ * mfb_channelizer_create_uniform, mfb_channelizer_set_plan_uniform on a handle of mfb_channelizer_create; and _set_plan_uniform while
+ * a call is in flight.  MFB_ERR_ARG: NULL where not allowed, counts < 1, an unknown format, a scale that is not a power of two,
+ * taps that are not finite, a bin outside [0, M) or named twice, more taps or selected bins than the handle was created for.
+ * Limits (MFB_ERR_UNSUPPORTED beyond): M one of 8, 16, 32, 64, 128, 256; 2 <= D <= M; 1..4096 taps; 1..M selected bins; 2^24 inputs
+ * and 2^22 outputs per call; max_selected max_out <= 2^26 samples per output set; in_base and out_base D < 2^62.  Misuse is an
+ * error code, never a fault. */
+int mfb_channelizer_create_uniform(mfb_channelizer **out, int device, int nbins, int max_selected, int max_taps, int max_in, int max_out);
+int mfb_channelizer_set_plan_uniform(mfb_channelizer *c, int decim, const float *taps, int ntaps, const int32_t *bins, int nselected,
+                                     int sample_format, float sample_scale);
 
 /* Test seams of the demodulation tail: the three kernels between the matched filters and the bit stream, launched as the product
  * launches them, on INJECTED inputs (tests/test_gpu_demod_tail.py).  Handle-less: device buffers of their own, a synchronous copy

@@ -33,6 +33,15 @@ one above, and ``Channelizer(...)`` without ``interp`` keeps running the integer
 ``[out_base, out_base + out_count)`` read inputs ``[q(out_base) - (ceil(T / U) - 1), q(out_base + out_count - 1)]``, the uniform
 bound, one sample generous for short branches.  ``factor_rate`` splits a ratio outside the limits into stages; a second stage is an
 ordinary ``Channelizer`` with ``freqs_hz=[0.0]`` fed the first stage's ``device_output`` pointer.
+
+Channels on a raster (``UniformChannelizer``; mfb_channelizer_create_uniform, csrc/channelize_uniform_kernels.hpp).  With every
+centre a multiple of ``fs / M``, M a power of two, the words ``freq_k = k 2**64 / M`` are exact and the first definition collapses:
+
+    y_k[m] = sum_{s < M} v_m[s] exp(+2 pi i k s / M)       v_m[s] = u_m[(s + m D) mod M]
+    u_m[p] = sum over j with p + jM < T of h[p + jM] x[m D - p - jM]                      p = 0 .. M - 1
+
+M branch sums with real taps, a circular shift and one M-point transform per output frame give all M bins: 2 T + 5 M log2 M flops
+instead of 8 M T.  The yardstick stays the float64 model above on those words.
 """
 import ctypes as C
 import functools
@@ -48,6 +57,7 @@ from .modulator import phase
 _U = np.uint64
 MAX_CHANNELS, MAX_DECIM, MAX_TAPS, MAX_IN, MAX_OUT = 16, 64, 1024, 1 << 24, 1 << 22
 MAX_INTERP = 32
+UNIFORM_BINS, UNIFORM_MAX_TAPS, UNIFORM_MAX_SET = (8, 16, 32, 64, 128, 256), 4096, 1 << 26
 FORMATS = {'cf32': 0, 'sc16': 1, 'sc8': 2}           # MFB_SAMPLES_* of include/mfbank.h
 _RAW = {'sc16': np.int16, 'sc8': np.int8}
 INPUT_PINNED0, INPUT_PINNED1, INPUT_DEVICE = 0, 1, 2
@@ -59,7 +69,9 @@ def design_taps(decim, taps_per_phase=16, beta=8.0, cutoff=0.4, interp=1):
     ``(T - 1) / 2`` input samples, ``taps_per_phase / 2`` output samples.  With ``interp = U > 1`` the same taps stand at the
     virtual rate ``U * fs`` of a resampling by U / decim: cutoff at ``cutoff / decim`` cycles per virtual sample, that is ``cutoff``
     cycles per output sample; they sum to U, so every branch has about unit gain and the pass-band gain is 1; the group delay is
-    ``(T - 1) / (2 U)`` input samples."""
+    ``(T - 1) / (2 U)`` input samples.  For a ``UniformChannelizer`` of M bins ``design_taps(decim)`` is the right prototype as it
+    is: every bin's pass band is ``0.4 / decim`` cycles per input sample to either side of its centre, so adjacent bins, ``1 / M``
+    apart, overlap as the taps dictate when ``decim < 0.8 M`` and are disjoint to -6 dB from there up to critical sampling."""
     decim, taps_per_phase, interp = int(decim), int(taps_per_phase), int(interp)
     if decim < 1 or taps_per_phase < 1 or interp < 1 or not 0 < cutoff <= 0.5:
         raise ValueError('decim >= 1, taps_per_phase >= 1, interp >= 1, 0 < cutoff <= 0.5')
@@ -140,6 +152,31 @@ def samples_to_c64(samples, sample_format, scale):
     raw = np.ascontiguousarray(samples, dtype=_RAW[sample_format]).reshape(-1, 2)
     f = raw.astype(np.float32) * np.float32(scale)
     return (f[:, 0] + 1j * f[:, 1]).astype(np.complex64)
+
+
+def _model_integer(taps, words, D, in_base, x, out_base, out_count):
+    """The integer-decimation definition in float64 on exact uint64 words, mix first: (y complex128 [K, out_count], S float64
+    [out_count]).  ``x`` complex128, the input from ``in_base`` on.  ``Channelizer.model`` and ``UniformChannelizer.model``."""
+    T = len(taps)
+    first = out_base * D - (T - 1)                          # may be negative: those positions read as zero
+    span = (out_count - 1) * D + T
+    lo = max(first, 0)
+    seg = np.zeros(span, dtype=np.complex128)
+    seg[lo - first:] = x[lo - in_base:first + span - in_base]
+    n = np.arange(lo, first + span, dtype=np.int64).astype(np.uint64)
+    hrev = taps.astype(np.float64)[::-1]
+    win = np.lib.stride_tricks.sliding_window_view
+    y = np.empty((len(words), out_count), dtype=np.complex128)
+    for k, f in enumerate(words):
+        z = seg
+        if f != 0:
+            with np.errstate(over='ignore'):
+                w = _U(0) - n * _U(f)                       # -phi_k(n), exact
+            z = seg.copy()
+            z[lo - first:] = np.where(w == 0, seg[lo - first:], seg[lo - first:] * phase.words_to_iq(w))
+        y[k] = win(z, T)[::D] @ hrev                       # row j: z[j D .. j D + T - 1], tap t at j D + T - 1 - t
+    S = win(np.abs(seg), T)[::D] @ np.abs(hrev)
+    return y, S
 
 
 class Channelizer:
@@ -303,26 +340,7 @@ class Channelizer:
         self._checked(in_base, len(x), out_base, out_count)
         if self.interp > 1:
             return self._model_rational(in_base, x, out_base, out_count)
-        D, T = self.decim, self.T
-        first = out_base * D - (T - 1)                      # may be negative: those positions read as zero
-        span = (out_count - 1) * D + T
-        lo = max(first, 0)
-        seg = np.zeros(span, dtype=np.complex128)
-        seg[lo - first:] = x[lo - in_base:first + span - in_base]
-        n = np.arange(lo, first + span, dtype=np.int64).astype(np.uint64)
-        hrev = self.taps.astype(np.float64)[::-1]
-        win = np.lib.stride_tricks.sliding_window_view
-        y = np.empty((self.K, out_count), dtype=np.complex128)
-        for k, f in enumerate(self.words):
-            z = seg
-            if f != 0:
-                with np.errstate(over='ignore'):
-                    w = _U(0) - n * _U(f)                   # -phi_k(n), exact
-                z = seg.copy()
-                z[lo - first:] = np.where(w == 0, seg[lo - first:], seg[lo - first:] * phase.words_to_iq(w))
-            y[k] = win(z, T)[::D] @ hrev                   # row j: z[j D .. j D + T - 1], tap t at j D + T - 1 - t
-        S = win(np.abs(seg), T)[::D] @ np.abs(hrev)
-        return y, S
+        return _model_integer(self.taps, self.words, self.decim, in_base, x, out_base, out_count)
 
     def _model_rational(self, in_base, x, out_base, out_count):
         """``model`` for U > 1: the sum of the definition, tap by tap, over the mixed stream."""
@@ -351,6 +369,81 @@ class Channelizer:
             y += h[t] * z[:, at - j]
             S += np.abs(h[t]) * mag[at - j]
         return y, S
+
+
+def check_plan_uniform(nbins, decim, taps, bins, sample_format, sample_scale):
+    """The checks of mfb_channelizer_create_uniform and mfb_channelizer_set_plan_uniform, as ValueError: (M, decim, taps float32,
+    bins int32 in [0, M), scale).  ``bins``: indices -M/2 <= b < M, taken modulo M; None: all M in index order."""
+    M, decim = int(nbins), int(decim)
+    if M not in UNIFORM_BINS:
+        raise ValueError(f'nbins is one of {UNIFORM_BINS}')
+    if not 2 <= decim <= M:
+        raise ValueError('2 <= decim <= nbins')
+    taps = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+    if not 1 <= len(taps) <= UNIFORM_MAX_TAPS or not np.all(np.isfinite(taps)):
+        raise ValueError(f'1 .. {UNIFORM_MAX_TAPS} finite taps')
+    b = np.arange(M, dtype=np.int64) if bins is None else np.atleast_1d(np.asarray(bins)).reshape(-1)
+    if b.dtype.kind not in 'iu':
+        raise ValueError('bins are integers')
+    b = b.astype(np.int64)
+    if not 1 <= len(b) <= M:
+        raise ValueError('1 .. nbins selected bins')
+    if np.any(b < -(M // 2)) or np.any(b >= M):
+        raise ValueError('-nbins / 2 <= bin < nbins')
+    b = (b % M).astype(np.int32)
+    if len(np.unique(b)) != len(b):
+        raise ValueError('a bin is selected twice')
+    if sample_format not in FORMATS:
+        raise ValueError(f'sample_format is one of {sorted(FORMATS)}')
+    scale = float(sample_scale)
+    if sample_format != 'cf32':
+        m, e = np.frexp(np.float32(scale))
+        if not (np.isfinite(scale) and scale > 0 and m == 0.5 and -100 < e < 100):
+            raise ValueError('sample_scale is a power of two')
+    return M, decim, taps, b, scale
+
+
+class UniformChannelizer(Channelizer):
+    """The channels of a raster: bin b of ``nbins = M`` (8 .. 256, a power of two) sits at ``b * fs / M``, is filtered with the real
+    ``taps`` and decimated by ``decim`` (2 <= D <= M; D need not divide M, critical sampling is D = M).  The definition is
+    ``Channelizer``'s with the exact words ``(b << 64) // M``; the device computes all M bins of an output frame with one M-point
+    transform over M branch sums (csrc/channelize_uniform_kernels.hpp, mfb_channelizer_create_uniform) and writes the selected
+    ``bins`` -- indices, signed or unsigned: -M/2 <= b < M, taken modulo M; None: all M in index order --, row i of the output
+    being ``bins[i]``.  ``design_taps(decim)`` is the prototype for it.  Everything else is ``Channelizer``'s surface: ``K`` is the
+    number of selected bins, ``interp`` is 1, ``info()`` gives (frames per workgroup, tap capacity); ``backend='host'`` and
+    ``model`` are the same float64 arithmetic on the exact words.  ``ChannelizerSource`` and ``ChannelWide`` take it as it is."""
+
+    def __init__(self, fs, nbins, decim, taps, bins=None, sample_format='cf32', sample_scale=1.0, backend='hip', device=0, max_in=1 << 20,
+                 max_out=None):
+        if backend not in ('hip', 'host'):
+            raise ValueError("backend is 'hip' or 'host'")
+        self.fs, self.backend, self.device = float(fs), backend, device
+        self.nbins, self.decim, self.taps, self.bins, self.scale = check_plan_uniform(nbins, decim, taps, bins, sample_format, sample_scale)
+        # exact: M is a power of two.  (The float route signed_quantise(2 pi f / fs) rounds some of them differently from M = 64 on.)
+        self.words = np.array([(int(b) << 64) // self.nbins for b in self.bins], dtype=np.uint64)
+        self.interp, self.rational = 1, False
+        self.sample_format, self.T, self.K = sample_format, len(self.taps), len(self.bins)
+        self.Tb = self.T
+        self.max_in = int(max_in)
+        self.max_out = int(max_out) if max_out is not None else max(1, -(-self.max_in // self.decim))
+        if not (1 <= self.max_in <= MAX_IN and 1 <= self.max_out <= MAX_OUT):
+            raise ValueError('1 <= max_in <= 2**24, 1 <= max_out <= 2**22')
+        if self.K * self.max_out > UNIFORM_MAX_SET:
+            raise ValueError('selected bins * max_out <= 2**26 samples per output set')
+        self._buffer, self._which, self._pinned = 1, 1, [None, None]
+        self.h = C.c_void_p()
+        if backend == 'hip':
+            self.lib = _lib.load()
+            _lib.check(self.lib.mfb_channelizer_create_uniform(C.byref(self.h), device, self.nbins, self.K, self.T, self.max_in, self.max_out),
+                       'mfb_channelizer_create_uniform')
+            _lib.check(self.lib.mfb_channelizer_set_plan_uniform(self.h, self.decim, self.taps.ctypes.data, self.T, self.bins.ctypes.data,
+                                                                 self.K, FORMATS[sample_format], self.scale), 'mfb_channelizer_set_plan_uniform')
+
+    @property
+    def freqs_hz(self):
+        """The selected bins' centres, the upper half of the raster as negative frequencies: ``b * fs / M`` for b < M / 2."""
+        b = self.bins.astype(np.int64)
+        return np.where(b >= self.nbins // 2, b - self.nbins, b) * (self.fs / self.nbins)
 
 
 class ChannelWide:

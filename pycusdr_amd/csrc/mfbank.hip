@@ -64,6 +64,7 @@
 #include "channel_kernels.hpp"
 #include "channelize_kernels.hpp"
 #include "channelize_rational_kernels.hpp"
+#include "channelize_uniform_kernels.hpp"
 #include "energy_kernels.hpp"
 #include "stream_kernels.hpp"
 #include "clip_kernels.hpp"
@@ -4111,6 +4112,9 @@ struct mfb_channelizer {
     bool rational = false;     // the plan in force runs k_chzr (mfb_channelizer_set_plan_rational), also at U = 1
     int U = 1, Tb = 0;         // its interpolation and ceil(T / U)
     int rtap_stride = 0;       // max_taps + CHZR_MAX_INTERP - 1 >= U Tb
+    bool uniform = false;      // made by mfb_channelizer_create_uniform: k_chu, plans of mfb_channelizer_set_plan_uniform only
+    int M = 0, F = 0;          // its bins, and the frames per workgroup of the plan in force
+    DevBuf<ChuPlan> d_uplan;   // the twiddle table and the selected bins' columns
     float scale = 1.0f;
     int cur = 0;               // the buffer of the call in flight
     int count[2] = {0, 0};     // 0: never written
@@ -4213,6 +4217,7 @@ static int chz_set_plan_body(mfb_channelizer *c, bool rational, int interp, int 
 static int chz_set_plan(mfb_channelizer *c, bool rational, int interp, int decim, const float *taps, int ntaps, const uint64_t *freq_words,
                         int nchan, int sample_format, float sample_scale) {
     if (!c || !taps || !freq_words || ntaps < 1 || nchan < 1) return MFB_ERR_ARG;
+    if (c->uniform) return MFB_ERR_STATE;
     if (sample_format != MFB_SAMPLES_CF32 && sample_format != MFB_SAMPLES_SC16 && sample_format != MFB_SAMPLES_SC8) return MFB_ERR_ARG;
     if (decim < 2 || decim > CHZ_MAX_DECIM || ntaps > CHZ_MAX_TAPS || nchan > CHZ_MAX_CHANNELS) return MFB_ERR_UNSUPPORTED;
     if (interp < 1 || interp > CHZR_MAX_INTERP) return MFB_ERR_UNSUPPORTED;
@@ -4263,12 +4268,150 @@ extern "C" int mfb_channelizer_input_buffer(mfb_channelizer *c, int which, void 
 extern "C" int mfb_channelizer_info(mfb_channelizer *c, int *outputs_per_workgroup, int *taps_capacity) {
     if (!c) return MFB_ERR_ARG;
     if (!c->have_plan) return MFB_ERR_STATE;
-    if (outputs_per_workgroup) *outputs_per_workgroup = c->rational ? c->U * c->threads : c->threads;
+    if (outputs_per_workgroup) *outputs_per_workgroup = c->uniform ? c->F : c->rational ? c->U * c->threads : c->threads;
     if (taps_capacity) *taps_capacity = c->max_taps;
     return MFB_OK;
 }
 
-// behind the launch of either kernel
+// ---- the uniform plan (channelize_uniform_kernels.hpp) on the same handle type
+static int chu_create_impl(mfb_channelizer *c) {
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamCreateWithFlags(out(c->stream), hipStreamNonBlocking));
+    HIPCHK(hipEventCreateWithFlags(out(c->done), hipEventDisableTiming));
+    HIPCHK(hipEventCreate(out(c->t0)));
+    HIPCHK(hipEventCreate(out(c->t1)));
+    HIPCHK(c->d_h.alloc((size_t)c->max_taps * sizeof(float), hip_malloc));
+    HIPCHK(c->d_uplan.alloc(sizeof(ChuPlan), hip_malloc));
+    for (int b = 0; b < 2; ++b) HIPCHK(c->d_out[b].alloc((size_t)c->max_channels * c->out_stride * sizeof(float2), hip_malloc));
+    return MFB_OK;
+}
+
+static bool chu_bins_ok(int M) { return M == 8 || M == 16 || M == 32 || M == 64 || M == 128 || M == 256; }
+
+extern "C" int mfb_channelizer_create_uniform(mfb_channelizer **out, int device, int nbins, int max_selected, int max_taps, int max_in,
+                                              int max_out) {
+    if (!out) return MFB_ERR_ARG;
+    *out = nullptr;
+    if (nbins < 1 || max_selected < 1 || max_taps < 1 || max_in < 1 || max_out < 1) return MFB_ERR_ARG;
+    if (!chu_bins_ok(nbins) || max_selected > nbins || max_taps > CHU_MAX_TAPS || max_in > CHZ_MAX_IN || max_out > CHZ_MAX_OUT)
+        return MFB_ERR_UNSUPPORTED;
+    if ((int64_t)max_selected * max_out > CHU_MAX_SET) return MFB_ERR_UNSUPPORTED;
+    int rc = device_ok(device, SYNC_MAX_DEVICES);
+    if (rc) return rc;
+    return guarded([&]() {
+        std::unique_ptr<mfb_channelizer, ChzDestroy> c(new mfb_channelizer());
+        c->device = device;
+        c->uniform = true;
+        c->M = nbins;
+        c->max_channels = max_selected;
+        c->max_taps = max_taps;
+        c->max_in = max_in;
+        c->max_out = max_out;
+        c->out_stride = (max_out + 1) & ~1;
+        const int rc2 = chu_create_impl(c.get());
+        if (rc2) return rc2;
+        *out = c.release();
+        return (int)MFB_OK;
+    });
+}
+
+static int chu_set_plan_body(mfb_channelizer *c, int decim, const float *taps, int ntaps, const int32_t *bins, int nsel, int fmt, float scale) {
+    HIPCHK(hipSetDevice(c->device));
+    ChuPlan P;
+    memset(&P, 0, sizeof(P));
+    const int M = c->M;
+    for (int q = 0; q < M; ++q) {                    // rounded once from float64; the multiples of a quarter turn are exact
+        const int e = q % (M / 4), quad = q / (M / 4);
+        double re = 1.0, im = 0.0;
+        if (e) {
+            const double a = 2.0 * M_PI * (double)e / (double)M;
+            re = cos(a);
+            im = sin(a);
+        }
+        for (int i = 0; i < quad; ++i) {             // times i
+            const double t = re;
+            re = -im;
+            im = t;
+        }
+        P.tw[q] = make_float2((float)re, (float)im);
+    }
+    for (int i = 0; i < nsel; ++i) P.col[i] = chu_column(M, bins[i]);
+    c->have_plan = false;
+    HIPCHK(hipMemcpyAsync(c->d_h, taps, (size_t)ntaps * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_uplan, &P, sizeof(P), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));       // (taps and P are the caller's and this frame's)
+    c->D = decim;
+    c->T = ntaps;
+    c->K = nsel;
+    c->fmt = fmt;
+    c->scale = scale;
+    c->U = 1;
+    c->Tb = ntaps;
+    c->F = chu_frames(M, decim, ntaps);
+    c->count[0] = c->count[1] = 0;                 // what the buffers hold belongs to the plan before
+    c->have_plan = true;
+    return MFB_OK;
+}
+
+extern "C" int mfb_channelizer_set_plan_uniform(mfb_channelizer *c, int decim, const float *taps, int ntaps, const int32_t *bins, int nselected,
+                                                int sample_format, float sample_scale) {
+    if (!c || !taps || !bins || ntaps < 1 || nselected < 1) return MFB_ERR_ARG;
+    if (!c->uniform) return MFB_ERR_STATE;
+    if (sample_format != MFB_SAMPLES_CF32 && sample_format != MFB_SAMPLES_SC16 && sample_format != MFB_SAMPLES_SC8) return MFB_ERR_ARG;
+    if (decim < 2 || decim > c->M || ntaps > CHU_MAX_TAPS || nselected > c->M) return MFB_ERR_UNSUPPORTED;
+    if (ntaps > c->max_taps || nselected > c->max_channels) return MFB_ERR_ARG;
+    bool seen[CHU_MAX_BINS] = {};
+    for (int i = 0; i < nselected; ++i) {
+        if (bins[i] < 0 || bins[i] >= c->M || seen[bins[i]]) return MFB_ERR_ARG;
+        seen[bins[i]] = true;
+    }
+    float scale = 1.0f;
+    if (sample_format != MFB_SAMPLES_CF32) {
+        scale = sample_scale == 0.0f ? (sample_format == MFB_SAMPLES_SC16 ? 0x1p-15f : 0x1p-7f) : sample_scale;
+        if (!chan_scale_ok(scale)) return MFB_ERR_ARG;
+    }
+    for (int t = 0; t < ntaps; ++t)
+        if (!std::isfinite(taps[t])) return MFB_ERR_ARG;
+    if (c->busy) return MFB_ERR_STATE;
+    return guarded([&] { return chu_set_plan_body(c, decim, taps, ntaps, bins, nselected, sample_format, scale); });
+}
+
+template <int M>
+static void chu_launch_m(mfb_channelizer *c, const ChuArgs &A, dim3 grid, size_t lds, const void *raw, float2 *outp) {
+#define CHU_LAUNCH(FMT_) \
+    hipLaunchKernelGGL((k_chu<M, FMT_>), grid, dim3(CHU_THREADS), lds, c->stream, A, (const ChuPlan *)c->d_uplan, raw, (const float *)c->d_h, outp)
+    if (c->fmt == MFB_SAMPLES_SC16) CHU_LAUNCH(CHZ_FMT_SC16);
+    else if (c->fmt == MFB_SAMPLES_SC8) CHU_LAUNCH(CHZ_FMT_SC8);
+    else CHU_LAUNCH(CHZ_FMT_CF32);
+#undef CHU_LAUNCH
+}
+
+static void chu_launch(mfb_channelizer *c, const mfb_channelizer_params *p, const void *raw) {
+    ChuArgs A;
+    A.in_base = p->in_base;
+    A.in_end = p->in_base + p->in_count;
+    A.out_base = p->out_base;
+    A.out_count = p->out_count;
+    A.D = c->D;
+    A.T = c->T;
+    A.F = c->F;
+    A.nsel = c->K;
+    A.out_stride = c->out_stride;
+    A.scale = c->scale;
+    const dim3 grid((unsigned)((p->out_count + c->F - 1) / c->F));
+    const size_t lds = chu_lds_bytes(c->M, c->D, c->T, c->F);
+    float2 *outp = c->d_out[p->buffer].get();
+    switch (c->M) {
+        case 8: chu_launch_m<8>(c, A, grid, lds, raw, outp); break;
+        case 16: chu_launch_m<16>(c, A, grid, lds, raw, outp); break;
+        case 32: chu_launch_m<32>(c, A, grid, lds, raw, outp); break;
+        case 64: chu_launch_m<64>(c, A, grid, lds, raw, outp); break;
+        case 128: chu_launch_m<128>(c, A, grid, lds, raw, outp); break;
+        default: chu_launch_m<256>(c, A, grid, lds, raw, outp); break;
+    }
+}
+
+// behind the launch of any of the kernels
 static int chz_begun(mfb_channelizer *c, const mfb_channelizer_params *p) {
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(c->t1, c->stream));
@@ -4292,6 +4435,10 @@ static int chz_begin_body(mfb_channelizer *c, const mfb_channelizer_params *p) {
     }
     c->count[p->buffer] = 0;
     HIPCHK(hipEventRecord(c->t0, c->stream));
+    if (c->uniform) {
+        chu_launch(c, p, raw);
+        return chz_begun(c, p);
+    }
     if (c->rational) {
         ChzrArgs R;
         R.in_base = p->in_base;
