@@ -907,6 +907,44 @@ int mfb_channelizer_set_plan_rational(mfb_channelizer *c, int interp, int decim,
 int mfb_channelizer_create_uniform(mfb_channelizer **out, int device, int nbins, int max_selected, int max_taps, int max_in, int max_out);
 int mfb_channelizer_set_plan_uniform(mfb_channelizer *c, int decim, const float *taps, int ntaps, const int32_t *bins, int nselected,
                                      int sample_format, float sample_scale);
+/* The survey of the raster (csrc/channelize_survey_kernels.hpp): how much power every one of the M bins of a uniform plan held in
+ * each stretch of time, what the noise floor was, and which (bin, stretch) cells stand above it -- reduced on the device from the
+ * frames a call makes anyway, with or without writing any of them.  No reference counterpart: the reference takes one narrowband
+ * stream per radio process (pyCuSDR.py:245-251).
+ * With y_k[m] the uniform plan's output for bin k = 0 .. M - 1, the very bits mfb_channelizer_begin would write:
+ *     cell      L = cell_frames = 2^l frames, 2 <= l <= 16; cell s of bin k covers the output positions [s L, (s + 1) L).
+ *     p_k[m]  = fl(fl(re re) + fl(im im)), float32, not fused.
+ *     P[s][k] = the balanced pairwise sum of the L values p_k[s L .. s L + L): at each level q[i] = fl(q[2 i] + q[2 i + 1]).
+ *     floor[s] = the rank-th smallest (0-based) of the M values P[s][.], 0 <= rank < M: an exact selection.  M / 4 stays on noise
+ *               while fewer than three quarters of the raster are occupied.
+ *     mask      bit (s, k) is set iff P[s][k] > fl(threshold floor[s]), threshold a finite float32 >= 1; packed as
+ *               uint32 mask[s][ceil(M / 32)], bit j of word w being bin 32 w + j, unused bits zero.
+ * k runs in natural bin order.  Every aligned power-of-two run of frames is a subtree of the sum, so P[s][k] is a pure function of
+ * (plan, samples read, s, k): a span of cells computed in one call equals the same cells under any cut, from any input window that
+ * covers them, in either output set, whatever bins are selected and whether or not outputs are written, bit for bit.
+ *   mfb_channelizer_set_survey    on a handle of mfb_channelizer_create_uniform with a plan: the cell length, the rank and the
+ *                                 threshold of the calls to come; allocates the partial sums, the two tables and the mask.
+ *                                 cell_frames = 0 turns the survey off and frees them.  mfb_channelizer_set_plan_uniform drops it.
+ *   mfb_channelizer_survey_info   what is set (cell_frames 0: nothing) and frames_per_workgroup, the consecutive frames a workgroup
+ *                                 of a survey call makes: the largest power of two that is at most the plan's F and fits its LDS
+ *                                 budget.  Any pointer may be NULL.
+ *   mfb_channelizer_survey_begin  mfb_channelizer_begin plus the survey of the cells out_base / L .. (out_base + out_count) / L, in
+ *                                 the same launch, and one small launch that finishes the tables, all inside the events of
+ *                                 mfb_channelizer_elapsed_ms.  write_outputs = 0: no bin is written and output set `buffer` counts as
+ *                                 never written.
+ *   mfb_channelizer_survey_end    waits; out_c64 as mfb_channelizer_end, power [ncells][M], floor [ncells] and
+ *                                 mask [ncells][ceil(M / 32)] receive the tables.  Any of the four may be NULL.
+ * mfb_channelizer_begin / _end work unchanged on a handle with a survey set.  MFB_ERR_ARG: everything mfb_channelizer_begin refuses
+ * with it; out_base or out_count not a multiple of L; a cell length that is no power of two in 4 .. 65536 or longer than max_out;
+ * a rank outside [0, M); a threshold below 1 or not finite; out_c64 where nothing was written (the call stays in flight).
+ * MFB_ERR_STATE: any of these on a handle of mfb_channelizer_create; _set_survey or _survey_info without a plan; _set_survey while a
+ * call is in flight; _survey_begin without a survey set; _survey_end behind mfb_channelizer_begin, mfb_channelizer_end behind
+ * _survey_begin.  Limits (MFB_ERR_UNSUPPORTED beyond, with those of mfb_channelizer_begin): M out_count <= 2^26 and
+ * M out_count / L <= 2^22 table entries per call.  Misuse is an error code, never a fault. */
+int mfb_channelizer_set_survey(mfb_channelizer *c, int cell_frames, int rank, float threshold);
+int mfb_channelizer_survey_info(mfb_channelizer *c, int *cell_frames, int *frames_per_workgroup, int *rank, float *threshold);
+int mfb_channelizer_survey_begin(mfb_channelizer *c, const mfb_channelizer_params *params, int write_outputs);
+int mfb_channelizer_survey_end(mfb_channelizer *c, float *out_c64, float *power, float *floor, uint32_t *mask);
 
 /* Test seams of the demodulation tail: the three kernels between the matched filters and the bit stream, launched as the product
  * launches them, on INJECTED inputs (tests/test_gpu_demod_tail.py).  Handle-less: device buffers of their own, a synchronous copy

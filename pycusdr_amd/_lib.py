@@ -227,6 +227,10 @@ PROTOTYPES = {
     'mfb_channelizer_set_plan_rational': (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _i, C.c_float]),
     'mfb_channelizer_create_uniform': (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i, _i]),
     'mfb_channelizer_set_plan_uniform': (_i, [_vp, _i, _vp, _i, _vp, _i, _i, C.c_float]),
+    'mfb_channelizer_set_survey': (_i, [_vp, _i, _i, C.c_float]),
+    'mfb_channelizer_survey_info': (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _fp]),
+    'mfb_channelizer_survey_begin': (_i, [_vp, C.POINTER(ChannelizerParams), _i]),
+    'mfb_channelizer_survey_end': (_i, [_vp, _vp, _vp, _vp, _vp]),
     'mfb_timer_start': (_i, [_vp]),
     'mfb_timer_stop': (_i, [_vp, _fp]),
     'mfb_profile_enable': (_i, [_vp, _i]),

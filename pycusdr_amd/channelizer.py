@@ -42,6 +42,19 @@ centre a multiple of ``fs / M``, M a power of two, the words ``freq_k = k 2**64 
 
 M branch sums with real taps, a circular shift and one M-point transform per output frame give all M bins: 2 T + 5 M log2 M flops
 instead of 8 M T.  The yardstick stays the float64 model above on those words.
+
+The survey of the raster (``UniformChannelizer.set_survey`` / ``survey``; mfb_channelizer_set_survey,
+csrc/channelize_survey_kernels.hpp): which bins hold a signal, and when, without writing any of them.  With ``y_k[m]`` the uniform
+plan's complex64 output of bin k = 0 .. M - 1 and a cell length ``L = 2**l`` frames, 2 <= l <= 16:
+
+    p_k[m]   = fl(fl(re * re) + fl(im * im))                     float32, not fused
+    P[s][k]  = the balanced pairwise sum of p_k[s L .. s L + L)   at each level q[i] = fl(q[2 i] + q[2 i + 1])
+    floor[s] = the rank-th smallest (0-based) of P[s][0 .. M)     default rank M / 4: on noise while < 3/4 of the raster is occupied
+    mask     bit (s, k) is set iff P[s][k] > fl(threshold * floor[s]); uint32 [s][ceil(M / 32)], bit j of word w is bin 32 w + j
+
+``pairwise_sum_f32``, ``cell_power``, ``cell_floor`` and ``cell_mask`` state these in numpy; the device gives the same bits from
+its own ``y`` whatever the cut into calls, the input window, the output set, the selected bins and whether outputs are written.
+``backend='host'`` applies them to the float64 model's outputs rounded to complex64.  ``bursts`` turns a mask into records per bin.
 """
 import ctypes as C
 import functools
@@ -444,6 +457,201 @@ class UniformChannelizer(Channelizer):
         """The selected bins' centres, the upper half of the raster as negative frequencies: ``b * fs / M`` for b < M / 2."""
         b = self.bins.astype(np.int64)
         return np.where(b >= self.nbins // 2, b - self.nbins, b) * (self.fs / self.nbins)
+
+    # ---- the survey of the raster (the section of the module docstring; mfb_channelizer_set_survey)
+    _survey = None                                           # (cell_frames, rank, threshold)
+
+    def set_survey(self, cell_frames, rank=None, threshold=4.0):
+        """The cell length L (a power of two, 4 .. 65536, at most ``max_out``), the floor's rank (default M / 4) and the mask's
+        threshold (finite, >= 1) of the ``survey`` calls to come.  ``cell_frames = 0`` turns the survey off."""
+        L = int(cell_frames)
+        if L == 0:
+            self._survey = None
+            if self.backend == 'hip':
+                _lib.check(self.lib.mfb_channelizer_set_survey(self.h, 0, 0, 1.0), 'mfb_channelizer_set_survey')
+            return
+        rank = self.nbins // 4 if rank is None else int(rank)
+        threshold = float(np.float32(threshold))
+        if L & (L - 1) or not SURVEY_MIN_CELL <= L <= SURVEY_MAX_CELL:
+            raise ValueError(f'cell_frames is a power of two, {SURVEY_MIN_CELL} .. {SURVEY_MAX_CELL}')
+        if L > self.max_out:
+            raise ValueError(f'a cell of {L} frames is longer than max_out = {self.max_out}')
+        if not 0 <= rank < self.nbins:
+            raise ValueError('0 <= rank < nbins')
+        if not (np.isfinite(threshold) and threshold >= 1.0):
+            raise ValueError('threshold is finite and >= 1')
+        if self.backend == 'hip':
+            _lib.check(self.lib.mfb_channelizer_set_survey(self.h, L, rank, threshold), 'mfb_channelizer_set_survey')
+        self._survey = (L, rank, threshold)
+
+    def survey_info(self):
+        """(frames per workgroup of a survey call, cell_frames, rank, threshold) on the device; cell_frames 0: no survey is set.
+        Cells shorter than the first are summed inside a workgroup, longer ones across workgroups."""
+        L, F, r, t = C.c_int(), C.c_int(), C.c_int(), C.c_float()
+        _lib.check(self.lib.mfb_channelizer_survey_info(self.h, C.byref(L), C.byref(F), C.byref(r), C.byref(t)), 'mfb_channelizer_survey_info')
+        return F.value, L.value, r.value, t.value
+
+    def needed_input_cells(self, first_cell, ncells):
+        """(in_base, in_count): the input positions that the cells first_cell .. first_cell + ncells read, clipped at 0."""
+        if self._survey is None:
+            raise ValueError('no survey is set: set_survey first')
+        L = self._survey[0]
+        if int(first_cell) < 0 or int(ncells) < 1:
+            raise ValueError('first_cell >= 0, ncells >= 1')
+        return self.needed_input(int(first_cell) * L, int(ncells) * L)
+
+    def survey(self, in_base, samples, first_cell, ncells, write=False, buffer=None, copy=True):
+        """The cells first_cell .. first_cell + ncells of all M bins, from input given as to ``process``: a ``SurveyResult``.
+        ``write``: the call also makes the outputs ``first_cell * L .. (first_cell + ncells) * L`` of the selected bins, exactly as
+        ``process`` does, and returns ``(result, outputs)`` with outputs complex64 [K, ncells * L]; they also stand in output set
+        ``buffer`` (hip); not ``copy`` (hip): they stay there alone, ask ``device_output`` for them, and outputs is None.  Without
+        ``write`` no bin is written and that output set counts as never written."""
+        if self._survey is None:
+            raise ValueError('no survey is set: set_survey first')
+        L, rank, threshold = self._survey
+        in_base, first_cell, ncells = int(in_base), int(first_cell), int(ncells)
+        if first_cell < 0 or ncells < 1:
+            raise ValueError('first_cell >= 0, ncells >= 1')
+        out_base, out_count = first_cell * L, ncells * L
+        if self.nbins * out_count > UNIFORM_MAX_SET or self.nbins * ncells > SURVEY_MAX_TABLE:
+            raise ValueError('nbins * frames <= 2**26 and nbins * cells <= 2**22 per survey call')
+        on_device = isinstance(samples, (int, tuple))
+        if on_device:
+            if self.backend != 'hip':
+                raise ValueError("device memory is an input of the 'hip' back end")
+            if isinstance(samples, tuple):
+                ptr, in_count = int(samples[0]), int(samples[1])
+            else:
+                first, n = self.needed_input(out_base, out_count)
+                ptr, in_count = int(samples), first + n - in_base
+        else:
+            if self.sample_format == 'cf32':
+                x = np.ascontiguousarray(samples, dtype=np.complex64).reshape(-1)
+            else:
+                x = np.ascontiguousarray(samples, dtype=_RAW[self.sample_format]).reshape(-1, 2)
+            in_count = len(x)
+        self._checked(in_base, in_count, out_base, out_count)
+        if self.backend == 'host':
+            xc = samples_to_c64(x, self.sample_format, self.scale).astype(np.complex128)
+            every = np.array([(b << 64) // self.nbins for b in range(self.nbins)], dtype=np.uint64)
+            y = _model_integer(self.taps, every, self.decim, in_base, xc, out_base, out_count)[0].astype(np.complex64)
+            power = cell_power(y, L)
+            floor = cell_floor(power, rank)
+            res = SurveyResult(power, floor, cell_mask(power, floor, threshold), first_cell, L)
+            return (res, y[self.bins]) if write else res
+        self._buffer = (self._buffer ^ 1) if buffer is None else int(buffer)
+        P = _lib.ChannelizerParams(in_base=in_base, out_base=out_base, in_count=in_count, out_count=out_count, buffer=self._buffer)
+        if on_device:
+            P.input, P.device_input = INPUT_DEVICE, ptr
+        else:
+            self._which ^= 1
+            self.input_buffer(self._which)[:in_count] = x
+            P.input = INPUT_PINNED1 if self._which else INPUT_PINNED0
+        _lib.check(self.lib.mfb_channelizer_survey_begin(self.h, C.byref(P), 1 if write else 0), 'mfb_channelizer_survey_begin')
+        self._count = out_count
+        power = np.empty((ncells, self.nbins), dtype=np.float32)
+        floor = np.empty(ncells, dtype=np.float32)
+        mask = np.empty((ncells, -(-self.nbins // 32)), dtype=np.uint32)
+        out = np.empty((self.K, out_count), dtype=np.complex64) if write and copy else None
+        _lib.check(self.lib.mfb_channelizer_survey_end(self.h, out.ctypes.data if out is not None else None, power.ctypes.data, floor.ctypes.data,
+                                                       mask.ctypes.data), 'mfb_channelizer_survey_end')
+        res = SurveyResult(power, floor, mask, first_cell, L)
+        return (res, out) if write else res
+
+
+SURVEY_MIN_CELL, SURVEY_MAX_CELL, SURVEY_MAX_TABLE = 4, 1 << 16, 1 << 22
+
+
+def pairwise_sum_f32(p):
+    """The balanced pairwise sum in float32 along the last axis, whose length is a power of two: at each level
+    ``q[i] = fl(q[2 i] + q[2 i + 1])``.  Any aligned power-of-two run of the axis is a subtree."""
+    q = np.ascontiguousarray(p, dtype=np.float32)
+    n = q.shape[-1]
+    if n < 1 or n & (n - 1):
+        raise ValueError('the length of the last axis is a power of two')
+    while q.shape[-1] > 1:
+        q = q[..., 0::2] + q[..., 1::2]
+    return q[..., 0]
+
+
+def cell_power(y, cell_frames):
+    """``P[s][k]`` float32 [ncells][M] of outputs ``y`` complex64 [M][ncells * L] whose first position is a multiple of L: the
+    pairwise sum over every cell of ``p = fl(fl(re re) + fl(im im))``, each operation rounded to float32 on its own."""
+    y = np.ascontiguousarray(y, dtype=np.complex64)
+    L = int(cell_frames)
+    if y.ndim != 2 or L < 1 or y.shape[1] % L:
+        raise ValueError('y is [M][ncells * cell_frames]')
+    re, im = y.real.astype(np.float32), y.imag.astype(np.float32)
+    p = (re * re) + (im * im)
+    return np.ascontiguousarray(pairwise_sum_f32(p.reshape(y.shape[0], -1, L)).T)
+
+
+def cell_floor(power, rank):
+    """``floor[s]``: the ``rank``-th smallest (0-based) of the M values of every cell."""
+    power = np.asarray(power, dtype=np.float32)
+    if not 0 <= int(rank) < power.shape[1]:
+        raise ValueError('0 <= rank < M')
+    return np.ascontiguousarray(np.sort(power, axis=1)[:, int(rank)])
+
+
+def cell_mask(power, floor, threshold):
+    """uint32 [ncells][ceil(M / 32)]: bit j of word w is set iff ``P[s][32 w + j] > fl(threshold * floor[s])``; unused bits zero."""
+    power = np.asarray(power, dtype=np.float32)
+    level = np.float32(threshold) * np.asarray(floor, dtype=np.float32)
+    ncells, M = power.shape
+    occ = np.zeros((ncells, -(-M // 32) * 32), dtype=bool)
+    occ[:, :M] = power > level[:, None]
+    return (occ.reshape(ncells, -1, 32).astype(np.uint32) << np.arange(32, dtype=np.uint32)).sum(axis=2, dtype=np.uint32)
+
+
+def unpack_mask(mask, nbins):
+    """bool [ncells][M] of the packed words."""
+    mask = np.asarray(mask, dtype=np.uint32)
+    bits = (mask[:, :, None] >> np.arange(32, dtype=np.uint32)) & np.uint32(1)
+    return bits.reshape(mask.shape[0], -1)[:, :nbins].astype(bool)
+
+
+BURST = np.dtype([('bin', np.int32), ('first_cell', np.int64), ('last_cell', np.int64), ('peak_power', np.float32),
+                  ('mean_power', np.float32)])
+
+
+def bursts(mask, power, hang=0, min_cells=1, first_cell=0):
+    """Runs of set cells per bin, host-only: runs separated by at most ``hang`` clear cells are merged, then runs shorter than
+    ``min_cells`` (first to last cell, bridged cells included) are dropped.  Records of dtype ``BURST`` -- (bin, first_cell,
+    last_cell, peak_power, mean_power), the cells counted from ``first_cell``, peak and mean over all cells from first to last, the
+    mean in float64 rounded to float32 -- sorted by (first_cell, bin)."""
+    power = np.asarray(power, dtype=np.float32)
+    occ = unpack_mask(mask, power.shape[1])
+    hang, min_cells = int(hang), int(min_cells)
+    if hang < 0 or min_cells < 1:
+        raise ValueError('hang >= 0, min_cells >= 1')
+    found = []
+    for k in range(occ.shape[1]):
+        on = np.flatnonzero(occ[:, k])
+        if not len(on):
+            continue
+        cut = np.flatnonzero(np.diff(on) > hang + 1)         # a gap of more than `hang` clear cells ends a run
+        for a, b in zip(np.r_[on[0], on[cut + 1]], np.r_[on[cut], on[-1]]):
+            if b - a + 1 >= min_cells:
+                seg = power[a:b + 1, k]
+                found.append((k, first_cell + a, first_cell + b, seg.max(), np.float32(seg.astype(np.float64).mean())))
+    found.sort(key=lambda r: (r[1], r[0]))
+    return np.array(found, dtype=BURST)
+
+
+class SurveyResult:
+    """``power`` float32 [ncells][M], ``floor`` float32 [ncells], ``mask`` uint32 [ncells][ceil(M / 32)] of the cells
+    ``first_cell .. first_cell + ncells`` of ``cell_frames`` frames each, bins in natural order."""
+
+    def __init__(self, power, floor, mask, first_cell, cell_frames):
+        self.power, self.floor, self.mask, self.first_cell, self.cell_frames = power, floor, mask, int(first_cell), int(cell_frames)
+
+    def occupied(self):
+        """bool [ncells][M]: the mask unpacked."""
+        return unpack_mask(self.mask, self.power.shape[1])
+
+    def bursts(self, hang=0, min_cells=1):
+        return bursts(self.mask, self.power, hang, min_cells, self.first_cell)
 
 
 class ChannelWide:

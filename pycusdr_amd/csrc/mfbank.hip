@@ -65,6 +65,7 @@
 #include "channelize_kernels.hpp"
 #include "channelize_rational_kernels.hpp"
 #include "channelize_uniform_kernels.hpp"
+#include "channelize_survey_kernels.hpp"
 #include "energy_kernels.hpp"
 #include "stream_kernels.hpp"
 #include "clip_kernels.hpp"
@@ -4119,6 +4120,18 @@ struct mfb_channelizer {
     int cur = 0;               // the buffer of the call in flight
     int count[2] = {0, 0};     // 0: never written
     int nchan[2] = {0, 0};     // the plan's channels when it was
+    // the survey of a uniform plan (channelize_survey_kernels.hpp, mfb_channelizer_set_survey)
+    int sv_L = 0;              // frames per cell; 0: no survey set
+    int sv_Fs = 0, sv_C = 0;   // the survey launch's frames per workgroup, and the frames per partial min(L, Fs)
+    int sv_rank = 0;
+    float sv_thr = 0.0f;
+    DevBuf<float> d_svpart;    // [chunks][M]
+    DevBuf<float> d_svpower;   // [cells][M]
+    DevBuf<float> d_svfloor;   // [cells]
+    DevBuf<uint32_t> d_svmask; // [cells][ceil(M / 32)]
+    bool sv_call = false;      // the call in flight, or finished last, came from mfb_channelizer_survey_begin
+    bool sv_wrote = false;     // and wrote its output set
+    int sv_cells = 0;          // its cells
 };
 
 static size_t chz_sample_bytes(int fmt) { return fmt == MFB_SAMPLES_SC16 ? 4 : fmt == MFB_SAMPLES_SC8 ? 2 : 8; }
@@ -4286,6 +4299,16 @@ static int chu_create_impl(mfb_channelizer *c) {
     return MFB_OK;
 }
 
+static hipError_t chus_drop(mfb_channelizer *c) {
+    c->sv_L = 0;
+    c->sv_call = false;
+    hipError_t e = c->d_svpart.reset(), e2;
+    if ((e2 = c->d_svpower.reset()) != hipSuccess) e = e2;
+    if ((e2 = c->d_svfloor.reset()) != hipSuccess) e = e2;
+    if ((e2 = c->d_svmask.reset()) != hipSuccess) e = e2;
+    return e;
+}
+
 static bool chu_bins_ok(int M) { return M == 8 || M == 16 || M == 32 || M == 64 || M == 128 || M == 256; }
 
 extern "C" int mfb_channelizer_create_uniform(mfb_channelizer **out, int device, int nbins, int max_selected, int max_taps, int max_in,
@@ -4337,6 +4360,7 @@ static int chu_set_plan_body(mfb_channelizer *c, int decim, const float *taps, i
     }
     for (int i = 0; i < nsel; ++i) P.col[i] = chu_column(M, bins[i]);
     c->have_plan = false;
+    HIPCHK(chus_drop(c));                          // a survey belongs to the plan it was set under
     HIPCHK(hipMemcpyAsync(c->d_h, taps, (size_t)ntaps * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->d_uplan, &P, sizeof(P), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));       // (taps and P are the caller's and this frame's)
@@ -4411,6 +4435,52 @@ static void chu_launch(mfb_channelizer *c, const mfb_channelizer_params *p, cons
     }
 }
 
+template <int M, bool WRITE>
+static void chus_launch_m(mfb_channelizer *c, const ChuArgs &A, const ChusArgs &V, dim3 grid, size_t lds, const void *raw, float2 *outp) {
+#define CHUS_LAUNCH(FMT_)                                                                                                             \
+    hipLaunchKernelGGL((k_chus<M, FMT_, WRITE>), grid, dim3(CHU_THREADS), lds, c->stream, A, V, (const ChuPlan *)c->d_uplan, raw, \
+                       (const float *)c->d_h, outp, c->d_svpart.get())
+    if (c->fmt == MFB_SAMPLES_SC16) CHUS_LAUNCH(CHZ_FMT_SC16);
+    else if (c->fmt == MFB_SAMPLES_SC8) CHUS_LAUNCH(CHZ_FMT_SC8);
+    else CHUS_LAUNCH(CHZ_FMT_CF32);
+#undef CHUS_LAUNCH
+}
+
+// the survey kernel, with or without the store, and the finishing kernel behind it
+template <bool WRITE>
+static void chus_launch(mfb_channelizer *c, const mfb_channelizer_params *p, const void *raw) {
+    ChuArgs A;
+    A.in_base = p->in_base;
+    A.in_end = p->in_base + p->in_count;
+    A.out_base = p->out_base;
+    A.out_count = p->out_count;
+    A.D = c->D;
+    A.T = c->T;
+    A.F = c->sv_Fs;
+    A.nsel = c->K;
+    A.out_stride = c->out_stride;
+    A.scale = c->scale;
+    ChusArgs V;
+    V.L = c->sv_L;
+    V.C = c->sv_C;
+    V.M = c->M;
+    V.rank = c->sv_rank;
+    V.threshold = c->sv_thr;
+    const dim3 grid((unsigned)((p->out_count + c->sv_Fs - 1) / c->sv_Fs));
+    const size_t lds = chus_lds_bytes(c->M, c->D, c->T, c->sv_Fs);
+    float2 *outp = c->d_out[p->buffer].get();
+    switch (c->M) {
+        case 8: chus_launch_m<8, WRITE>(c, A, V, grid, lds, raw, outp); break;
+        case 16: chus_launch_m<16, WRITE>(c, A, V, grid, lds, raw, outp); break;
+        case 32: chus_launch_m<32, WRITE>(c, A, V, grid, lds, raw, outp); break;
+        case 64: chus_launch_m<64, WRITE>(c, A, V, grid, lds, raw, outp); break;
+        case 128: chus_launch_m<128, WRITE>(c, A, V, grid, lds, raw, outp); break;
+        default: chus_launch_m<256, WRITE>(c, A, V, grid, lds, raw, outp); break;
+    }
+    hipLaunchKernelGGL(k_chus_finish, dim3((unsigned)(p->out_count / c->sv_L)), dim3(256), 0, c->stream, V, (const float *)c->d_svpart,
+                       c->d_svpower.get(), c->d_svfloor.get(), c->d_svmask.get());
+}
+
 // behind the launch of any of the kernels
 static int chz_begun(mfb_channelizer *c, const mfb_channelizer_params *p) {
     HIPCHK(hipGetLastError());
@@ -4419,11 +4489,13 @@ static int chz_begun(mfb_channelizer *c, const mfb_channelizer_params *p) {
     c->cur = p->buffer;
     c->count[p->buffer] = p->out_count;
     c->nchan[p->buffer] = c->K;
+    c->sv_call = false;
     c->busy = true;
     return MFB_OK;
 }
 
-static int chz_begin_body(mfb_channelizer *c, const mfb_channelizer_params *p) {
+// survey: 0 a plain call; 1 the survey alone; 2 the survey and the outputs (a uniform plan with a survey set)
+static int chz_begin_body(mfb_channelizer *c, const mfb_channelizer_params *p, int survey = 0) {
     HIPCHK(hipSetDevice(c->device));
     const size_t sb = chz_sample_bytes(c->fmt);
     const void *raw = p->device_input;
@@ -4435,6 +4507,17 @@ static int chz_begin_body(mfb_channelizer *c, const mfb_channelizer_params *p) {
     }
     c->count[p->buffer] = 0;
     HIPCHK(hipEventRecord(c->t0, c->stream));
+    if (c->uniform && survey) {
+        if (survey == 2) chus_launch<true>(c, p, raw);
+        else chus_launch<false>(c, p, raw);
+        const int rc = chz_begun(c, p);
+        if (rc) return rc;
+        if (survey != 2) c->count[p->buffer] = 0;  // the set was not written
+        c->sv_call = true;
+        c->sv_wrote = survey == 2;
+        c->sv_cells = p->out_count / c->sv_L;
+        return MFB_OK;
+    }
     if (c->uniform) {
         chu_launch(c, p, raw);
         return chz_begun(c, p);
@@ -4495,7 +4578,8 @@ static int chz_begin_body(mfb_channelizer *c, const mfb_channelizer_params *p) {
     return chz_begun(c, p);
 }
 
-extern "C" int mfb_channelizer_begin(mfb_channelizer *c, const mfb_channelizer_params *p) {
+// what mfb_channelizer_begin refuses
+static int chz_begin_check(mfb_channelizer *c, const mfb_channelizer_params *p) {
     if (!c || !p) return MFB_ERR_ARG;
     if (p->in_count < 1 || p->out_count < 1 || p->in_base < 0 || p->out_base < 0 || (p->buffer != 0 && p->buffer != 1)) return MFB_ERR_ARG;
     if (p->input != MFB_CHZ_INPUT_PINNED0 && p->input != MFB_CHZ_INPUT_PINNED1 && p->input != MFB_CHZ_INPUT_DEVICE) return MFB_ERR_ARG;
@@ -4511,12 +4595,18 @@ extern "C" int mfb_channelizer_begin(mfb_channelizer *c, const mfb_channelizer_p
     // (a rational plan: [q(out_base) - (ceil(T / U) - 1), q(out_base + out_count - 1)], q(m) = (m D) div U; U = 1 otherwise)
     const int64_t first = p->out_base * c->D / c->U - (c->Tb - 1), last = (p->out_base + p->out_count - 1) * c->D / c->U;
     if ((first > 0 ? first : 0) < p->in_base || last >= p->in_base + p->in_count) return MFB_ERR_ARG;
+    return MFB_OK;
+}
+
+extern "C" int mfb_channelizer_begin(mfb_channelizer *c, const mfb_channelizer_params *p) {
+    const int rc = chz_begin_check(c, p);
+    if (rc) return rc;
     return guarded([&] { return chz_begin_body(c, p); });
 }
 
 extern "C" int mfb_channelizer_end(mfb_channelizer *c, float *out_c64) {
     if (!c) return MFB_ERR_ARG;
-    if (!c->busy) return MFB_ERR_STATE;
+    if (!c->busy || c->sv_call) return MFB_ERR_STATE;          // (a survey call ends with mfb_channelizer_survey_end)
     HIPCHK(hipSetDevice(c->device));
     const int b = c->cur;
     if (out_c64) {
@@ -4541,9 +4631,88 @@ extern "C" int mfb_channelizer_device_output(mfb_channelizer *c, int buffer, int
 
 extern "C" int mfb_channelizer_elapsed_ms(mfb_channelizer *c, float *ms) {
     if (!c || !ms) return MFB_ERR_ARG;
-    if (c->busy || !(c->count[0] || c->count[1])) return MFB_ERR_STATE;
+    if (c->busy || !(c->count[0] || c->count[1] || c->sv_call)) return MFB_ERR_STATE;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipEventElapsedTime(ms, c->t0, c->t1));
+    return MFB_OK;
+}
+
+// ---- the survey of a uniform plan (channelize_survey_kernels.hpp)
+static int chus_set_body(mfb_channelizer *c, int cell_frames, int rank, float threshold) {
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(chus_drop(c));
+    if (!cell_frames) return MFB_OK;
+    const int Fs = chus_frames(c->M, c->D, c->T), C = cell_frames < Fs ? cell_frames : Fs;
+    // the longest call: max_out outputs, M out_count <= 2^26, M out_count / L <= 2^22
+    const int64_t most = (int64_t)c->max_out < (int64_t)CHU_MAX_SET / c->M ? (int64_t)c->max_out : (int64_t)CHU_MAX_SET / c->M;
+    int64_t cells = most / cell_frames;
+    if (cells > CHUS_MAX_TABLE / c->M) cells = CHUS_MAX_TABLE / c->M;
+    const int64_t chunks = cells * (cell_frames / C);
+    const int words = (c->M + 31) / 32;
+    HIPCHK(c->d_svpart.alloc((size_t)chunks * c->M * sizeof(float), hip_malloc));
+    HIPCHK(c->d_svpower.alloc((size_t)cells * c->M * sizeof(float), hip_malloc));
+    HIPCHK(c->d_svfloor.alloc((size_t)cells * sizeof(float), hip_malloc));
+    HIPCHK(c->d_svmask.alloc((size_t)cells * words * sizeof(uint32_t), hip_malloc));
+    c->sv_Fs = Fs;
+    c->sv_C = C;
+    c->sv_rank = rank;
+    c->sv_thr = threshold;
+    c->sv_L = cell_frames;
+    return MFB_OK;
+}
+
+extern "C" int mfb_channelizer_set_survey(mfb_channelizer *c, int cell_frames, int rank, float threshold) {
+    if (!c) return MFB_ERR_ARG;
+    if (!c->uniform || !c->have_plan || c->busy) return MFB_ERR_STATE;
+    if (cell_frames) {
+        if (cell_frames < (1 << CHUS_MIN_LOG2) || cell_frames > (1 << CHUS_MAX_LOG2) || (cell_frames & (cell_frames - 1))) return MFB_ERR_ARG;
+        if (rank < 0 || rank >= c->M || !std::isfinite(threshold) || threshold < 1.0f) return MFB_ERR_ARG;
+        if (cell_frames > c->max_out) return MFB_ERR_ARG;      // no call of this handle holds one cell
+    }
+    const int rc = guarded([&] { return chus_set_body(c, cell_frames, rank, threshold); });
+    if (rc) (void)chus_drop(c);
+    return rc;
+}
+
+extern "C" int mfb_channelizer_survey_info(mfb_channelizer *c, int *cell_frames, int *frames_per_workgroup, int *rank, float *threshold) {
+    if (!c) return MFB_ERR_ARG;
+    if (!c->uniform || !c->have_plan) return MFB_ERR_STATE;
+    if (cell_frames) *cell_frames = c->sv_L;
+    if (frames_per_workgroup) *frames_per_workgroup = c->sv_L ? c->sv_Fs : chus_frames(c->M, c->D, c->T);
+    if (rank) *rank = c->sv_rank;
+    if (threshold) *threshold = c->sv_thr;
+    return MFB_OK;
+}
+
+extern "C" int mfb_channelizer_survey_begin(mfb_channelizer *c, const mfb_channelizer_params *p, int write_outputs) {
+    if (!c || !p) return MFB_ERR_ARG;
+    if (!c->uniform) return MFB_ERR_STATE;
+    const int rc = chz_begin_check(c, p);
+    if (rc) return rc;
+    if (!c->sv_L) return MFB_ERR_STATE;
+    if (p->out_base % c->sv_L || p->out_count % c->sv_L) return MFB_ERR_ARG;
+    if ((int64_t)c->M * p->out_count > CHU_MAX_SET || (int64_t)c->M * (p->out_count / c->sv_L) > CHUS_MAX_TABLE) return MFB_ERR_UNSUPPORTED;
+    return guarded([&] { return chz_begin_body(c, p, write_outputs ? 2 : 1); });
+}
+
+extern "C" int mfb_channelizer_survey_end(mfb_channelizer *c, float *out_c64, float *power, float *floor, uint32_t *mask) {
+    if (!c) return MFB_ERR_ARG;
+    if (!c->busy || !c->sv_call) return MFB_ERR_STATE;         // (a plain call ends with mfb_channelizer_end)
+    if (out_c64 && !c->sv_wrote) return MFB_ERR_ARG;           // the call stays in flight
+    HIPCHK(hipSetDevice(c->device));
+    const int b = c->cur;
+    const size_t cells = (size_t)c->sv_cells;
+    if (out_c64) {
+        const size_t row = (size_t)c->count[b] * sizeof(float2);
+        HIPCHK(hipMemcpy2DAsync(out_c64, row, c->d_out[b].get(), (size_t)c->out_stride * sizeof(float2), row, (size_t)c->nchan[b],
+                                hipMemcpyDeviceToHost, c->stream));
+    }
+    if (power) HIPCHK(hipMemcpyAsync(power, c->d_svpower, cells * c->M * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (floor) HIPCHK(hipMemcpyAsync(floor, c->d_svfloor, cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (mask) HIPCHK(hipMemcpyAsync(mask, c->d_svmask, cells * ((c->M + 31) / 32) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (out_c64 || power || floor || mask) HIPCHK(hipStreamSynchronize(c->stream));
+    else HIPCHK(hipEventSynchronize(c->done));
+    c->busy = false;
     return MFB_OK;
 }
 
