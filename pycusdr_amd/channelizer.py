@@ -197,9 +197,7 @@ class Channelizer:
                  max_out=None, interp=1, force_rational=False):
         """``interp = U``: resample by U / decim (the module docstring); 1 takes the integer kernel, unless ``force_rational``
         (the tests' seam) sends that plan through the rational kernel too."""
-        if backend not in ('hip', 'host'):
-            raise ValueError("backend is 'hip' or 'host'")
-        self.fs, self.backend, self.device = float(fs), backend, device
+        self._check_backend(fs, backend, device)
         freqs = np.atleast_1d(np.asarray(freqs_hz, dtype=np.float64))
         if not np.all(np.abs(freqs) <= self.fs / 2):
             raise ValueError('|freq| <= fs / 2')
@@ -209,15 +207,8 @@ class Channelizer:
         self.interp = int(interp)
         self.rational = self.interp > 1 or bool(force_rational)
         self.sample_format, self.T, self.K = sample_format, len(self.taps), len(self.words)
-        self.Tb = -(-self.T // self.interp)                   # taps of the longest branch
-        self.max_in = int(max_in)
-        self.max_out = int(max_out) if max_out is not None else max(1, -(-self.max_in * self.interp // self.decim))
-        if not (1 <= self.max_in <= MAX_IN and 1 <= self.max_out <= MAX_OUT):
-            raise ValueError('1 <= max_in <= 2**24, 1 <= max_out <= 2**22')
-        self._buffer, self._which, self._pinned = 1, 1, [None, None]
-        self.h = C.c_void_p()
+        self._init_tail(max_in, max_out)
         if backend == 'hip':
-            self.lib = _lib.load()
             _lib.check(self.lib.mfb_channelizer_create(C.byref(self.h), device, self.K, self.T, self.max_in, self.max_out),
                        'mfb_channelizer_create')
             if self.rational:
@@ -227,6 +218,26 @@ class Channelizer:
             else:
                 _lib.check(self.lib.mfb_channelizer_set_plan(self.h, self.decim, self.taps.ctypes.data, self.T, self.words.ctypes.data,
                                                              self.K, FORMATS[sample_format], self.scale), 'mfb_channelizer_set_plan')
+
+    def _check_backend(self, fs, backend, device):
+        if backend not in ('hip', 'host'):
+            raise ValueError("backend is 'hip' or 'host'")
+        self.fs, self.backend, self.device = float(fs), backend, device
+
+    def _init_tail(self, max_in, max_out, max_set=None):
+        """What every constructor ends with, once ``interp``, ``decim``, ``T`` and ``K`` stand: the longest branch, the sizes of a
+        call with their limits (``max_set``: complex64 per output set), the buffers' flip state, an empty handle and the library."""
+        self.Tb = -(-self.T // self.interp)                   # taps of the longest branch
+        self.max_in = int(max_in)
+        self.max_out = int(max_out) if max_out is not None else max(1, -(-self.max_in * self.interp // self.decim))
+        if not (1 <= self.max_in <= MAX_IN and 1 <= self.max_out <= MAX_OUT):
+            raise ValueError('1 <= max_in <= 2**24, 1 <= max_out <= 2**22')
+        if max_set is not None and self.K * self.max_out > max_set:
+            raise ValueError('selected bins * max_out <= 2**26 samples per output set')
+        self._buffer, self._which, self._pinned = 1, 1, [None, None]
+        self.h = C.c_void_p()
+        if self.backend == 'hip':
+            self.lib = _lib.load()
 
     def close(self):
         if self.h:
@@ -295,17 +306,18 @@ class Channelizer:
         self.begin(in_base, samples, out_base, out_count, buffer)
         return self.end(copy)
 
-    def begin(self, in_base, samples, out_base, out_count, buffer=None):
-        in_base, out_base, out_count = int(in_base), int(out_base), int(out_count)
+    def _intake(self, in_base, samples, out_base, out_count):
+        """``samples`` as ``process`` takes them, checked against the span: (on_device, device pointer or host array of the plan's
+        format, in_count)."""
         on_device = isinstance(samples, (int, tuple))
         if on_device:
             if self.backend != 'hip':
                 raise ValueError("device memory is an input of the 'hip' back end")
             if isinstance(samples, tuple):
-                ptr, in_count = int(samples[0]), int(samples[1])
+                x, in_count = int(samples[0]), int(samples[1])
             else:
                 first, n = self.needed_input(out_base, max(out_count, 1))
-                ptr, in_count = int(samples), first + n - in_base
+                x, in_count = int(samples), first + n - in_base
         else:
             if self.sample_format == 'cf32':
                 x = np.ascontiguousarray(samples, dtype=np.complex64).reshape(-1)
@@ -313,17 +325,28 @@ class Channelizer:
                 x = np.ascontiguousarray(samples, dtype=_RAW[self.sample_format]).reshape(-1, 2)
             in_count = len(x)
         self._checked(in_base, in_count, out_base, out_count)
-        if self.backend == 'host':
-            self._host = self.model(in_base, x, out_base, out_count)[0].astype(np.complex64)
-            return
+        return on_device, x, in_count
+
+    def _params(self, on_device, x, in_base, in_count, out_base, out_count, buffer):
+        """The ``ChannelizerParams`` of a device call (``_count`` is the caller's to set once the call is begun): flips the output set unless ``buffer`` names one, and copies host samples
+        into the page-locked buffer that the call before did not use."""
         self._buffer = (self._buffer ^ 1) if buffer is None else int(buffer)
         P = _lib.ChannelizerParams(in_base=in_base, out_base=out_base, in_count=in_count, out_count=out_count, buffer=self._buffer)
         if on_device:
-            P.input, P.device_input = INPUT_DEVICE, ptr
+            P.input, P.device_input = INPUT_DEVICE, x
         else:
             self._which ^= 1
             self.input_buffer(self._which)[:in_count] = x
             P.input = INPUT_PINNED1 if self._which else INPUT_PINNED0
+        return P
+
+    def begin(self, in_base, samples, out_base, out_count, buffer=None):
+        in_base, out_base, out_count = int(in_base), int(out_base), int(out_count)
+        on_device, x, in_count = self._intake(in_base, samples, out_base, out_count)
+        if self.backend == 'host':
+            self._host = self.model(in_base, x, out_base, out_count)[0].astype(np.complex64)
+            return
+        P = self._params(on_device, x, in_base, in_count, out_base, out_count, buffer)
         _lib.check(self.lib.mfb_channelizer_begin(self.h, C.byref(P)), 'mfb_channelizer_begin')
         self._count = out_count
 
@@ -428,25 +451,14 @@ class UniformChannelizer(Channelizer):
 
     def __init__(self, fs, nbins, decim, taps, bins=None, sample_format='cf32', sample_scale=1.0, backend='hip', device=0, max_in=1 << 20,
                  max_out=None):
-        if backend not in ('hip', 'host'):
-            raise ValueError("backend is 'hip' or 'host'")
-        self.fs, self.backend, self.device = float(fs), backend, device
+        self._check_backend(fs, backend, device)
         self.nbins, self.decim, self.taps, self.bins, self.scale = check_plan_uniform(nbins, decim, taps, bins, sample_format, sample_scale)
         # exact: M is a power of two.  (The float route signed_quantise(2 pi f / fs) rounds some of them differently from M = 64 on.)
         self.words = np.array([(int(b) << 64) // self.nbins for b in self.bins], dtype=np.uint64)
         self.interp, self.rational = 1, False
         self.sample_format, self.T, self.K = sample_format, len(self.taps), len(self.bins)
-        self.Tb = self.T
-        self.max_in = int(max_in)
-        self.max_out = int(max_out) if max_out is not None else max(1, -(-self.max_in // self.decim))
-        if not (1 <= self.max_in <= MAX_IN and 1 <= self.max_out <= MAX_OUT):
-            raise ValueError('1 <= max_in <= 2**24, 1 <= max_out <= 2**22')
-        if self.K * self.max_out > UNIFORM_MAX_SET:
-            raise ValueError('selected bins * max_out <= 2**26 samples per output set')
-        self._buffer, self._which, self._pinned = 1, 1, [None, None]
-        self.h = C.c_void_p()
+        self._init_tail(max_in, max_out, UNIFORM_MAX_SET)
         if backend == 'hip':
-            self.lib = _lib.load()
             _lib.check(self.lib.mfb_channelizer_create_uniform(C.byref(self.h), device, self.nbins, self.K, self.T, self.max_in, self.max_out),
                        'mfb_channelizer_create_uniform')
             _lib.check(self.lib.mfb_channelizer_set_plan_uniform(self.h, self.decim, self.taps.ctypes.data, self.T, self.bins.ctypes.data,
@@ -515,22 +527,7 @@ class UniformChannelizer(Channelizer):
         out_base, out_count = first_cell * L, ncells * L
         if self.nbins * out_count > UNIFORM_MAX_SET or self.nbins * ncells > SURVEY_MAX_TABLE:
             raise ValueError('nbins * frames <= 2**26 and nbins * cells <= 2**22 per survey call')
-        on_device = isinstance(samples, (int, tuple))
-        if on_device:
-            if self.backend != 'hip':
-                raise ValueError("device memory is an input of the 'hip' back end")
-            if isinstance(samples, tuple):
-                ptr, in_count = int(samples[0]), int(samples[1])
-            else:
-                first, n = self.needed_input(out_base, out_count)
-                ptr, in_count = int(samples), first + n - in_base
-        else:
-            if self.sample_format == 'cf32':
-                x = np.ascontiguousarray(samples, dtype=np.complex64).reshape(-1)
-            else:
-                x = np.ascontiguousarray(samples, dtype=_RAW[self.sample_format]).reshape(-1, 2)
-            in_count = len(x)
-        self._checked(in_base, in_count, out_base, out_count)
+        on_device, x, in_count = self._intake(in_base, samples, out_base, out_count)
         if self.backend == 'host':
             xc = samples_to_c64(x, self.sample_format, self.scale).astype(np.complex128)
             every = np.array([(b << 64) // self.nbins for b in range(self.nbins)], dtype=np.uint64)
@@ -539,14 +536,7 @@ class UniformChannelizer(Channelizer):
             floor = cell_floor(power, rank)
             res = SurveyResult(power, floor, cell_mask(power, floor, threshold), first_cell, L)
             return (res, y[self.bins]) if write else res
-        self._buffer = (self._buffer ^ 1) if buffer is None else int(buffer)
-        P = _lib.ChannelizerParams(in_base=in_base, out_base=out_base, in_count=in_count, out_count=out_count, buffer=self._buffer)
-        if on_device:
-            P.input, P.device_input = INPUT_DEVICE, ptr
-        else:
-            self._which ^= 1
-            self.input_buffer(self._which)[:in_count] = x
-            P.input = INPUT_PINNED1 if self._which else INPUT_PINNED0
+        P = self._params(on_device, x, in_base, in_count, out_base, out_count, buffer)
         _lib.check(self.lib.mfb_channelizer_survey_begin(self.h, C.byref(P), 1 if write else 0), 'mfb_channelizer_survey_begin')
         self._count = out_count
         power = np.empty((ncells, self.nbins), dtype=np.float32)

@@ -32,13 +32,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "channelize_plan.hpp"        // the limits, and how wide a workgroup is (chz_threads, chz_row_len)
 #include "mod_kernels.hpp"
 
-#define CHZ_MAX_CHANNELS 16
-#define CHZ_MAX_DECIM 64
-#define CHZ_MAX_TAPS 1024
-#define CHZ_MAX_THREADS 256
-#define CHZ_LDS_BUDGET (48 * 1024)   // bytes of LDS a workgroup may take: three workgroups per CU at the least
 #define CHZ_UNROLL 8                 // taps per trip of the inner loop
 #define CHZ_FMT_CF32 0              // = MFB_SAMPLES_CF32 / _SC16 / _SC8
 #define CHZ_FMT_SC16 1
@@ -61,19 +57,6 @@ struct ChzArgs {
     int32_t ncplx, nreal;
     float scale;
 };
-
-// rows of the LDS image for a workgroup of `threads` lanes: ceil(span / D), made odd
-static inline int chz_row_len(int threads, int D, int T) {
-    const int span = (threads - 1) * D + T;
-    return ((span + D - 1) / D) | 1;
-}
-
-// the largest workgroup whose image fits the budget (64 lanes always do: 64 * 81 * 8 bytes at D = 64, T = 1024)
-static inline int chz_threads(int D, int T) {
-    for (int w = CHZ_MAX_THREADS; w > 64; w >>= 1)
-        if ((size_t)D * chz_row_len(w, D, T) * sizeof(float2) <= (size_t)CHZ_LDS_BUDGET) return w;
-    return 64;
-}
 
 // g[k][t] = h[t] e^{+2 pi i (t freq_k) / 2^64}; (h[t], 0) for a word of 0.  Grid: (ceil(T / 256), nchan).
 __global__ __launch_bounds__(256) void k_chz_taps(const float *__restrict__ h, const ChzPlan *__restrict__ P, int T, int tap_stride,

@@ -42,8 +42,7 @@
 // the same LDS budget and it adds the barriers; what the scattered stores cost beside that was not separated.
 #pragma once
 #include "channelize_kernels.hpp"
-
-#define CHZR_MAX_INTERP 32
+#include "channelize_plan.hpp"        // CHZR_MAX_INTERP, and chzr_span / chzr_row_len / chzr_threads for the S and L below
 
 struct ChzrArgs {
     int64_t in_base, in_end;         // the call's input holds the positions [in_base, in_end)
@@ -55,16 +54,6 @@ struct ChzrArgs {
     int32_t ncplx, nreal;
     float scale;
 };
-
-static inline int chzr_branch_taps(int U, int T) { return (T + U - 1) / U; }
-static inline int chzr_span(int threads, int U, int D, int T) { return chzr_branch_taps(U, T) - 1 + threads * D; }
-static inline int chzr_row_len(int threads, int U, int D, int T) { return ((chzr_span(threads, U, D, T) + D - 1) / D) | 1; }
-// the largest workgroup whose image fits the budget (64 lanes always do: 64 * 81 * 8 bytes at D = 64, Tb = 1024)
-static inline int chzr_threads(int U, int D, int T) {
-    for (int w = CHZ_MAX_THREADS; w > 64; w >>= 1)
-        if ((size_t)D * chzr_row_len(w, U, D, T) * sizeof(float2) <= (size_t)CHZ_LDS_BUDGET) return w;
-    return 64;
-}
 
 // g[k][r][j] = h[t] e^{+2 pi i ((t div U) freq_k) / 2^64} with t = r + j U; (h[t], 0) for a word of 0; (0, 0), never read, for
 // t >= T.  Grid: (ceil(U Tb / 256), nchan).

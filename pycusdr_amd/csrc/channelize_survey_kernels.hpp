@@ -33,12 +33,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "channelize_plan.hpp"        // the CHUS_ limits, chus_frames and chus_lds_bytes
 #include "channelize_uniform_kernels.hpp"
-
-#define CHUS_MIN_LOG2 2
-#define CHUS_MAX_LOG2 16
-#define CHUS_MAX_TABLE (1 << 22)     // (cell, bin) entries per call
-#define CHUS_SCRATCH 256             // floats behind the uniform kernel's LDS
 
 struct ChusArgs {
     int32_t L;                       // frames per cell
@@ -46,17 +42,6 @@ struct ChusArgs {
     int32_t M, rank;
     float threshold;
 };
-
-static inline size_t chus_lds_bytes(int M, int D, int T, int Fs) { return chu_lds_bytes(M, D, T, Fs) + CHUS_SCRATCH * sizeof(float); }
-
-// frames per workgroup of a survey launch
-static inline int chus_frames(int M, int D, int T) {
-    const int F = chu_frames(M, D, T);
-    int Fs = 1;
-    while (2 * Fs <= F) Fs <<= 1;
-    while (Fs * M > 256 && chus_lds_bytes(M, D, T, Fs) > (size_t)CHU_LDS_BUDGET) Fs >>= 1;
-    return Fs;
-}
 
 // the bin that the passes leave in image column col: the inverse of chu_column
 template <int M>

@@ -51,12 +51,7 @@
 #include <stdint.h>
 
 #include "channelize_kernels.hpp"
-
-#define CHU_THREADS 256
-#define CHU_MAX_BINS 256
-#define CHU_MAX_TAPS 4096
-#define CHU_LDS_BUDGET (64 * 1024)
-#define CHU_MAX_SET (1 << 26)        // complex64 per output set
+#include "channelize_plan.hpp"        // the CHU_ limits, chu_frames and chu_lds_bytes
 
 typedef chz_cf chu_cf;
 
@@ -87,19 +82,6 @@ static inline int chu_column(int M, int k) {
         N = L;
     }
     return col;
-}
-
-static inline size_t chu_lds_bytes(int M, int D, int T, int F) {
-    return ((size_t)(F - 1) * D + T + (size_t)F * (M + 1) + M) * sizeof(float2);
-}
-
-// frames per workgroup (the header comment has the rule)
-static inline int chu_frames(int M, int D, int T) {
-    const int step = 256 / M > 16 ? 256 / M : 16;
-    int F = 4096 / M > 128 ? 128 : 4096 / M;
-    while (F > step && chu_lds_bytes(M, D, T, F) > (size_t)CHU_LDS_BUDGET) F -= step;
-    while (F * M > 256 && chu_lds_bytes(M, D, T, F) > (size_t)CHU_LDS_BUDGET) F >>= 1;
-    return F;
 }
 
 __host__ __device__ __forceinline__ chu_cf chu_add(chu_cf a, chu_cf b) { return (chu_cf){a.x + b.x, a.y + b.y}; }

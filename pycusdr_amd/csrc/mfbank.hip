@@ -4093,12 +4093,13 @@ extern "C" int mfb_debug_channel_normals(int device, const uint32_t *words, int 
     });
 }
 
-// ---- the channeliser (channelize_kernels.hpp) -----------------------------------------------------------------------------
-#define CHZ_MAX_IN (1 << 24)
-#define CHZ_MAX_OUT (1 << 22)
+// ---- the channeliser (channelize_plan.hpp: the limits and what a plan of each kind launches; the kernels: channelize_kernels.hpp,
+// channelize_rational_kernels.hpp, channelize_uniform_kernels.hpp, channelize_survey_kernels.hpp) -------------------------------
 struct mfb_channelizer {
     Stream stream;             // (first: it goes last)
     int device = 0, max_channels = 0, max_taps = 0, max_in = 0, max_out = 0;
+    int M = 0;                 // the bins of a handle made by mfb_channelizer_create_uniform, which takes plans of
+                               // mfb_channelizer_set_plan_uniform only; 0: made by mfb_channelizer_create
     int out_stride = 0;        // float2 between two channels of an output set: max_out made even, so every channel is 16-byte aligned
     Event done, t0, t1;
     HostBuf<uint8_t> h_in[2];  // page-locked raw staging, on demand (mfb_channelizer_input_buffer)
@@ -4109,20 +4110,17 @@ struct mfb_channelizer {
     DevBuf<float2> d_rtaps;    // a rational plan's tables by branch, [max_channels][rtap_stride], on demand
     DevBuf<float2> d_out[2];   // [max_channels][out_stride]
     bool have_plan = false, busy = false;
-    int D = 0, T = 0, K = 0, fmt = 0, ncplx = 0, threads = 0, L = 0;
-    bool rational = false;     // the plan in force runs k_chzr (mfb_channelizer_set_plan_rational), also at U = 1
-    int U = 1, Tb = 0;         // its interpolation and ceil(T / U)
+    ChzGeom plan = {};         // what a call of the plan in force launches; its kind says which kernel
+    ChzGeom survey = {};       // what a survey call of a uniform plan launches (CHZ_SURVEY)
+    int K = 0, fmt = 0, ncplx = 0;
     int rtap_stride = 0;       // max_taps + CHZR_MAX_INTERP - 1 >= U Tb
-    bool uniform = false;      // made by mfb_channelizer_create_uniform: k_chu, plans of mfb_channelizer_set_plan_uniform only
-    int M = 0, F = 0;          // its bins, and the frames per workgroup of the plan in force
-    DevBuf<ChuPlan> d_uplan;   // the twiddle table and the selected bins' columns
+    DevBuf<ChuPlan> d_uplan;   // a uniform handle's twiddle table and the selected bins' columns
     float scale = 1.0f;
     int cur = 0;               // the buffer of the call in flight
     int count[2] = {0, 0};     // 0: never written
     int nchan[2] = {0, 0};     // the plan's channels when it was
-    // the survey of a uniform plan (channelize_survey_kernels.hpp, mfb_channelizer_set_survey)
+    // the survey of a uniform plan (mfb_channelizer_set_survey)
     int sv_L = 0;              // frames per cell; 0: no survey set
-    int sv_Fs = 0, sv_C = 0;   // the survey launch's frames per workgroup, and the frames per partial min(L, Fs)
     int sv_rank = 0;
     float sv_thr = 0.0f;
     DevBuf<float> d_svpart;    // [chunks][M]
@@ -4154,22 +4152,24 @@ static int chz_create_impl(mfb_channelizer *c) {
     HIPCHK(hipEventCreate(out(c->t0)));
     HIPCHK(hipEventCreate(out(c->t1)));
     HIPCHK(c->d_h.alloc((size_t)c->max_taps * sizeof(float), hip_malloc));
-    HIPCHK(c->d_plan.alloc(sizeof(ChzPlan), hip_malloc));
-    HIPCHK(c->d_taps.alloc((size_t)c->max_channels * c->max_taps * sizeof(float2), hip_malloc));
+    if (c->M) {
+        HIPCHK(c->d_uplan.alloc(sizeof(ChuPlan), hip_malloc));
+    } else {
+        HIPCHK(c->d_plan.alloc(sizeof(ChzPlan), hip_malloc));
+        HIPCHK(c->d_taps.alloc((size_t)c->max_channels * c->max_taps * sizeof(float2), hip_malloc));
+    }
     for (int b = 0; b < 2; ++b) HIPCHK(c->d_out[b].alloc((size_t)c->max_channels * c->out_stride * sizeof(float2), hip_malloc));
     return MFB_OK;
 }
 
-extern "C" int mfb_channelizer_create(mfb_channelizer **out, int device, int max_channels, int max_taps, int max_in, int max_out) {
-    if (!out) return MFB_ERR_ARG;
-    *out = nullptr;
-    if (max_channels < 1 || max_taps < 1 || max_in < 1 || max_out < 1) return MFB_ERR_ARG;
-    if (max_channels > CHZ_MAX_CHANNELS || max_taps > CHZ_MAX_TAPS || max_in > CHZ_MAX_IN || max_out > CHZ_MAX_OUT) return MFB_ERR_UNSUPPORTED;
+// behind the argument checks of either create; nbins: 0 for mfb_channelizer_create
+static int chz_create(mfb_channelizer **out, int device, int nbins, int max_channels, int max_taps, int max_in, int max_out) {
     int rc = device_ok(device, SYNC_MAX_DEVICES);
     if (rc) return rc;
     return guarded([&]() {
         std::unique_ptr<mfb_channelizer, ChzDestroy> c(new mfb_channelizer());
         c->device = device;
+        c->M = nbins;
         c->max_channels = max_channels;
         c->max_taps = max_taps;
         c->max_in = max_in;
@@ -4182,11 +4182,60 @@ extern "C" int mfb_channelizer_create(mfb_channelizer **out, int device, int max
     });
 }
 
-static int chz_set_plan_body(mfb_channelizer *c, bool rational, int interp, int decim, const float *taps, int ntaps, const uint64_t *freq_words,
-                             int nchan, int fmt, float scale) {
+extern "C" int mfb_channelizer_create(mfb_channelizer **out, int device, int max_channels, int max_taps, int max_in, int max_out) {
+    if (!out) return MFB_ERR_ARG;
+    *out = nullptr;
+    if (max_channels < 1 || max_taps < 1 || max_in < 1 || max_out < 1) return MFB_ERR_ARG;
+    if (max_channels > CHZ_MAX_CHANNELS || max_taps > CHZ_MAX_TAPS || max_in > CHZ_MAX_IN || max_out > CHZ_MAX_OUT) return MFB_ERR_UNSUPPORTED;
+    return chz_create(out, device, 0, max_channels, max_taps, max_in, max_out);
+}
+
+static bool chu_bins_ok(int M) { return M == 8 || M == 16 || M == 32 || M == 64 || M == 128 || M == 256; }
+
+extern "C" int mfb_channelizer_create_uniform(mfb_channelizer **out, int device, int nbins, int max_selected, int max_taps, int max_in,
+                                              int max_out) {
+    if (!out) return MFB_ERR_ARG;
+    *out = nullptr;
+    if (nbins < 1 || max_selected < 1 || max_taps < 1 || max_in < 1 || max_out < 1) return MFB_ERR_ARG;
+    if (!chu_bins_ok(nbins) || max_selected > nbins || max_taps > CHU_MAX_TAPS || max_in > CHZ_MAX_IN || max_out > CHZ_MAX_OUT)
+        return MFB_ERR_UNSUPPORTED;
+    if ((int64_t)max_selected * max_out > CHU_MAX_SET) return MFB_ERR_UNSUPPORTED;
+    return chz_create(out, device, nbins, max_selected, max_taps, max_in, max_out);
+}
+
+// What every set_plan refuses, in the order of the codes: `which` are the plan's n tuning words or selected bins; kind_tests() the
+// limits and the arguments of the one kind of plan, MFB_ERR_UNSUPPORTED before MFB_ERR_ARG.  *scale: the scale the plan runs with.
+template <class KindTests>
+static int chz_plan_check(mfb_channelizer *c, bool uniform, const float *taps, int ntaps, const void *which, int n, int fmt, float sample_scale,
+                          float *scale, KindTests kind_tests) {
+    if (!c || !taps || !which || ntaps < 1 || n < 1) return MFB_ERR_ARG;
+    if ((c->M != 0) != uniform) return MFB_ERR_STATE;
+    if (!chz_format_ok(fmt)) return MFB_ERR_ARG;
+    const int rc = kind_tests();
+    if (rc) return rc;
+    if (ntaps > c->max_taps || n > c->max_channels) return MFB_ERR_ARG;
+    if (!chz_plan_scale(fmt, sample_scale, chan_scale_ok, scale) || !chz_taps_finite(taps, ntaps)) return MFB_ERR_ARG;
+    return c->busy ? MFB_ERR_STATE : MFB_OK;
+}
+
+// The plan's taps and table are on their way on the stream: wait for them (both are the caller's, or the caller's frame's), then
+// the plan is in force.  Until here a set_plan that fails leaves the handle without a plan.
+static int chz_plan_commit(mfb_channelizer *c, const ChzGeom &g, int K, int ncplx, int fmt, float scale) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->plan = g;
+    c->K = K;
+    c->ncplx = ncplx;
+    c->fmt = fmt;
+    c->scale = scale;
+    c->count[0] = c->count[1] = 0;                 // what the buffers hold belongs to the plan before
+    c->have_plan = true;
+    return MFB_OK;
+}
+
+static int chz_set_plan_body(mfb_channelizer *c, const ChzGeom &g, const float *taps, const uint64_t *freq_words, int nchan, int fmt,
+                             float scale) {
     HIPCHK(hipSetDevice(c->device));
-    const int Tb = chzr_branch_taps(interp, ntaps);
-    if (rational && !c->d_rtaps) {
+    if (g.kind == CHZ_RATIONAL && !c->d_rtaps) {
         c->rtap_stride = c->max_taps + CHZR_MAX_INTERP - 1;
         HIPCHK(c->d_rtaps.alloc((size_t)c->max_channels * c->rtap_stride * sizeof(float2), hip_malloc));
     }
@@ -4201,102 +4250,40 @@ static int chz_set_plan_body(mfb_channelizer *c, bool rational, int interp, int 
     for (int k = 0; k < nchan; ++k)
         if (freq_words[k] == 0) P.order[at++] = k;
     c->have_plan = false;
-    HIPCHK(hipMemcpyAsync(c->d_h, taps, (size_t)ntaps * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_h, taps, (size_t)g.T * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->d_plan, &P, sizeof(P), hipMemcpyHostToDevice, c->stream));
-    if (rational)
-        hipLaunchKernelGGL(k_chzr_taps, dim3((interp * Tb + 255) / 256, nchan), dim3(256), 0, c->stream, (const float *)c->d_h,
-                           (const ChzPlan *)c->d_plan, interp, ntaps, Tb, c->rtap_stride, c->d_rtaps.get());
+    if (g.kind == CHZ_RATIONAL)
+        hipLaunchKernelGGL(k_chzr_taps, dim3((g.U * g.Tb + 255) / 256, nchan), dim3(256), 0, c->stream, (const float *)c->d_h,
+                           (const ChzPlan *)c->d_plan, g.U, g.T, g.Tb, c->rtap_stride, c->d_rtaps.get());
     else
-        hipLaunchKernelGGL(k_chz_taps, dim3((ntaps + 255) / 256, nchan), dim3(256), 0, c->stream, (const float *)c->d_h, (const ChzPlan *)c->d_plan,
-                           ntaps, c->max_taps, c->d_taps.get());
+        hipLaunchKernelGGL(k_chz_taps, dim3((g.T + 255) / 256, nchan), dim3(256), 0, c->stream, (const float *)c->d_h, (const ChzPlan *)c->d_plan,
+                           g.T, c->max_taps, c->d_taps.get());
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));       // (taps and P are the caller's and this frame's)
-    c->D = decim;
-    c->T = ntaps;
-    c->K = nchan;
-    c->fmt = fmt;
-    c->scale = scale;
-    c->ncplx = ncplx;
-    c->rational = rational;
-    c->U = interp;
-    c->Tb = Tb;
-    c->threads = rational ? chzr_threads(interp, decim, ntaps) : chz_threads(decim, ntaps);
-    c->L = rational ? chzr_row_len(c->threads, interp, decim, ntaps) : chz_row_len(c->threads, decim, ntaps);
-    c->count[0] = c->count[1] = 0;                 // what the buffers hold belongs to the plan before
-    c->have_plan = true;
-    return MFB_OK;
+    return chz_plan_commit(c, g, nchan, ncplx, fmt, scale);
 }
 
-static int chz_set_plan(mfb_channelizer *c, bool rational, int interp, int decim, const float *taps, int ntaps, const uint64_t *freq_words,
-                        int nchan, int sample_format, float sample_scale) {
-    if (!c || !taps || !freq_words || ntaps < 1 || nchan < 1) return MFB_ERR_ARG;
-    if (c->uniform) return MFB_ERR_STATE;
-    if (sample_format != MFB_SAMPLES_CF32 && sample_format != MFB_SAMPLES_SC16 && sample_format != MFB_SAMPLES_SC8) return MFB_ERR_ARG;
-    if (decim < 2 || decim > CHZ_MAX_DECIM || ntaps > CHZ_MAX_TAPS || nchan > CHZ_MAX_CHANNELS) return MFB_ERR_UNSUPPORTED;
-    if (interp < 1 || interp > CHZR_MAX_INTERP) return MFB_ERR_UNSUPPORTED;
-    if (interp >= decim || ntaps < interp) return MFB_ERR_ARG;
-    for (int a = decim, b = interp;;) {              // gcd(U, D) = 1
-        const int r = a % b;
-        if (!r) {
-            if (b != 1) return MFB_ERR_ARG;
-            break;
-        }
-        a = b;
-        b = r;
-    }
-    if (ntaps > c->max_taps || nchan > c->max_channels) return MFB_ERR_ARG;
+// kind: CHZ_INTEGER (interp 1) or CHZ_RATIONAL, which runs k_chzr also at U = 1
+static int chz_set_plan(mfb_channelizer *c, int kind, int interp, int decim, const float *taps, int ntaps, const uint64_t *freq_words, int nchan,
+                        int sample_format, float sample_scale) {
     float scale = 1.0f;
-    if (sample_format != MFB_SAMPLES_CF32) {
-        scale = sample_scale == 0.0f ? (sample_format == MFB_SAMPLES_SC16 ? 0x1p-15f : 0x1p-7f) : sample_scale;
-        if (!chan_scale_ok(scale)) return MFB_ERR_ARG;
-    }
-    for (int t = 0; t < ntaps; ++t)
-        if (!std::isfinite(taps[t])) return MFB_ERR_ARG;
-    if (c->busy) return MFB_ERR_STATE;
-    return guarded([&] { return chz_set_plan_body(c, rational, interp, decim, taps, ntaps, freq_words, nchan, sample_format, scale); });
+    const int rc = chz_plan_check(c, false, taps, ntaps, freq_words, nchan, sample_format, sample_scale, &scale, [&]() -> int {
+        if (decim < 2 || decim > CHZ_MAX_DECIM || ntaps > CHZ_MAX_TAPS || nchan > CHZ_MAX_CHANNELS) return MFB_ERR_UNSUPPORTED;
+        if (interp < 1 || interp > CHZR_MAX_INTERP) return MFB_ERR_UNSUPPORTED;
+        if (interp >= decim || ntaps < interp || !chzr_coprime(interp, decim)) return MFB_ERR_ARG;
+        return MFB_OK;
+    });
+    if (rc) return rc;
+    return guarded([&] { return chz_set_plan_body(c, chz_geom(kind, interp, decim, ntaps, 0), taps, freq_words, nchan, sample_format, scale); });
 }
 
 extern "C" int mfb_channelizer_set_plan(mfb_channelizer *c, int decim, const float *taps, int ntaps, const uint64_t *freq_words, int nchan,
                                         int sample_format, float sample_scale) {
-    return chz_set_plan(c, false, 1, decim, taps, ntaps, freq_words, nchan, sample_format, sample_scale);
+    return chz_set_plan(c, CHZ_INTEGER, 1, decim, taps, ntaps, freq_words, nchan, sample_format, sample_scale);
 }
 
 extern "C" int mfb_channelizer_set_plan_rational(mfb_channelizer *c, int interp, int decim, const float *taps, int ntaps,
                                                  const uint64_t *freq_words, int nchan, int sample_format, float sample_scale) {
-    return chz_set_plan(c, true, interp, decim, taps, ntaps, freq_words, nchan, sample_format, sample_scale);
-}
-
-extern "C" int mfb_channelizer_input_buffer(mfb_channelizer *c, int which, void **host, size_t *bytes) {
-    if (!c || !host || (which != 0 && which != 1)) return MFB_ERR_ARG;
-    if (!c->have_plan) return MFB_ERR_STATE;
-    return guarded([&]() {          // (also while a call is in flight: the other buffer is being filled)
-        HIPCHK(hipSetDevice(c->device));
-        if (!c->h_in[which]) HIPCHK(c->h_in[which].alloc((size_t)c->max_in * sizeof(float2), hip_host_malloc));
-        *host = c->h_in[which].get();
-        if (bytes) *bytes = (size_t)c->max_in * chz_sample_bytes(c->fmt);
-        return (int)MFB_OK;
-    });
-}
-
-extern "C" int mfb_channelizer_info(mfb_channelizer *c, int *outputs_per_workgroup, int *taps_capacity) {
-    if (!c) return MFB_ERR_ARG;
-    if (!c->have_plan) return MFB_ERR_STATE;
-    if (outputs_per_workgroup) *outputs_per_workgroup = c->uniform ? c->F : c->rational ? c->U * c->threads : c->threads;
-    if (taps_capacity) *taps_capacity = c->max_taps;
-    return MFB_OK;
-}
-
-// ---- the uniform plan (channelize_uniform_kernels.hpp) on the same handle type
-static int chu_create_impl(mfb_channelizer *c) {
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamCreateWithFlags(out(c->stream), hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(out(c->done), hipEventDisableTiming));
-    HIPCHK(hipEventCreate(out(c->t0)));
-    HIPCHK(hipEventCreate(out(c->t1)));
-    HIPCHK(c->d_h.alloc((size_t)c->max_taps * sizeof(float), hip_malloc));
-    HIPCHK(c->d_uplan.alloc(sizeof(ChuPlan), hip_malloc));
-    for (int b = 0; b < 2; ++b) HIPCHK(c->d_out[b].alloc((size_t)c->max_channels * c->out_stride * sizeof(float2), hip_malloc));
-    return MFB_OK;
+    return chz_set_plan(c, CHZ_RATIONAL, interp, decim, taps, ntaps, freq_words, nchan, sample_format, sample_scale);
 }
 
 static hipError_t chus_drop(mfb_channelizer *c) {
@@ -4307,35 +4294,6 @@ static hipError_t chus_drop(mfb_channelizer *c) {
     if ((e2 = c->d_svfloor.reset()) != hipSuccess) e = e2;
     if ((e2 = c->d_svmask.reset()) != hipSuccess) e = e2;
     return e;
-}
-
-static bool chu_bins_ok(int M) { return M == 8 || M == 16 || M == 32 || M == 64 || M == 128 || M == 256; }
-
-extern "C" int mfb_channelizer_create_uniform(mfb_channelizer **out, int device, int nbins, int max_selected, int max_taps, int max_in,
-                                              int max_out) {
-    if (!out) return MFB_ERR_ARG;
-    *out = nullptr;
-    if (nbins < 1 || max_selected < 1 || max_taps < 1 || max_in < 1 || max_out < 1) return MFB_ERR_ARG;
-    if (!chu_bins_ok(nbins) || max_selected > nbins || max_taps > CHU_MAX_TAPS || max_in > CHZ_MAX_IN || max_out > CHZ_MAX_OUT)
-        return MFB_ERR_UNSUPPORTED;
-    if ((int64_t)max_selected * max_out > CHU_MAX_SET) return MFB_ERR_UNSUPPORTED;
-    int rc = device_ok(device, SYNC_MAX_DEVICES);
-    if (rc) return rc;
-    return guarded([&]() {
-        std::unique_ptr<mfb_channelizer, ChzDestroy> c(new mfb_channelizer());
-        c->device = device;
-        c->uniform = true;
-        c->M = nbins;
-        c->max_channels = max_selected;
-        c->max_taps = max_taps;
-        c->max_in = max_in;
-        c->max_out = max_out;
-        c->out_stride = (max_out + 1) & ~1;
-        const int rc2 = chu_create_impl(c.get());
-        if (rc2) return rc2;
-        *out = c.release();
-        return (int)MFB_OK;
-    });
 }
 
 static int chu_set_plan_body(mfb_channelizer *c, int decim, const float *taps, int ntaps, const int32_t *bins, int nsel, int fmt, float scale) {
@@ -4363,139 +4321,154 @@ static int chu_set_plan_body(mfb_channelizer *c, int decim, const float *taps, i
     HIPCHK(chus_drop(c));                          // a survey belongs to the plan it was set under
     HIPCHK(hipMemcpyAsync(c->d_h, taps, (size_t)ntaps * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->d_uplan, &P, sizeof(P), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));       // (taps and P are the caller's and this frame's)
-    c->D = decim;
-    c->T = ntaps;
-    c->K = nsel;
-    c->fmt = fmt;
-    c->scale = scale;
-    c->U = 1;
-    c->Tb = ntaps;
-    c->F = chu_frames(M, decim, ntaps);
-    c->count[0] = c->count[1] = 0;                 // what the buffers hold belongs to the plan before
-    c->have_plan = true;
-    return MFB_OK;
+    c->survey = chz_geom(CHZ_SURVEY, 1, decim, ntaps, M);
+    return chz_plan_commit(c, chz_geom(CHZ_UNIFORM, 1, decim, ntaps, M), nsel, 0, fmt, scale);
 }
 
 extern "C" int mfb_channelizer_set_plan_uniform(mfb_channelizer *c, int decim, const float *taps, int ntaps, const int32_t *bins, int nselected,
                                                 int sample_format, float sample_scale) {
-    if (!c || !taps || !bins || ntaps < 1 || nselected < 1) return MFB_ERR_ARG;
-    if (!c->uniform) return MFB_ERR_STATE;
-    if (sample_format != MFB_SAMPLES_CF32 && sample_format != MFB_SAMPLES_SC16 && sample_format != MFB_SAMPLES_SC8) return MFB_ERR_ARG;
-    if (decim < 2 || decim > c->M || ntaps > CHU_MAX_TAPS || nselected > c->M) return MFB_ERR_UNSUPPORTED;
-    if (ntaps > c->max_taps || nselected > c->max_channels) return MFB_ERR_ARG;
-    bool seen[CHU_MAX_BINS] = {};
-    for (int i = 0; i < nselected; ++i) {
-        if (bins[i] < 0 || bins[i] >= c->M || seen[bins[i]]) return MFB_ERR_ARG;
-        seen[bins[i]] = true;
-    }
     float scale = 1.0f;
-    if (sample_format != MFB_SAMPLES_CF32) {
-        scale = sample_scale == 0.0f ? (sample_format == MFB_SAMPLES_SC16 ? 0x1p-15f : 0x1p-7f) : sample_scale;
-        if (!chan_scale_ok(scale)) return MFB_ERR_ARG;
-    }
-    for (int t = 0; t < ntaps; ++t)
-        if (!std::isfinite(taps[t])) return MFB_ERR_ARG;
-    if (c->busy) return MFB_ERR_STATE;
+    const int rc = chz_plan_check(c, true, taps, ntaps, bins, nselected, sample_format, sample_scale, &scale, [&]() -> int {
+        if (decim < 2 || decim > c->M || ntaps > CHU_MAX_TAPS || nselected > c->M) return MFB_ERR_UNSUPPORTED;
+        bool seen[CHU_MAX_BINS] = {};
+        for (int i = 0; i < nselected; ++i) {
+            if (bins[i] < 0 || bins[i] >= c->M || seen[bins[i]]) return MFB_ERR_ARG;
+            seen[bins[i]] = true;
+        }
+        return MFB_OK;
+    });
+    if (rc) return rc;
     return guarded([&] { return chu_set_plan_body(c, decim, taps, ntaps, bins, nselected, sample_format, scale); });
 }
 
-template <int M>
-static void chu_launch_m(mfb_channelizer *c, const ChuArgs &A, dim3 grid, size_t lds, const void *raw, float2 *outp) {
-#define CHU_LAUNCH(FMT_) \
-    hipLaunchKernelGGL((k_chu<M, FMT_>), grid, dim3(CHU_THREADS), lds, c->stream, A, (const ChuPlan *)c->d_uplan, raw, (const float *)c->d_h, outp)
-    if (c->fmt == MFB_SAMPLES_SC16) CHU_LAUNCH(CHZ_FMT_SC16);
-    else if (c->fmt == MFB_SAMPLES_SC8) CHU_LAUNCH(CHZ_FMT_SC8);
-    else CHU_LAUNCH(CHZ_FMT_CF32);
-#undef CHU_LAUNCH
+extern "C" int mfb_channelizer_input_buffer(mfb_channelizer *c, int which, void **host, size_t *bytes) {
+    if (!c || !host || (which != 0 && which != 1)) return MFB_ERR_ARG;
+    if (!c->have_plan) return MFB_ERR_STATE;
+    return guarded([&]() {          // (also while a call is in flight: the other buffer is being filled)
+        HIPCHK(hipSetDevice(c->device));
+        if (!c->h_in[which]) HIPCHK(c->h_in[which].alloc((size_t)c->max_in * sizeof(float2), hip_host_malloc));
+        *host = c->h_in[which].get();
+        if (bytes) *bytes = (size_t)c->max_in * chz_sample_bytes(c->fmt);
+        return (int)MFB_OK;
+    });
+}
+
+extern "C" int mfb_channelizer_info(mfb_channelizer *c, int *outputs_per_workgroup, int *taps_capacity) {
+    if (!c) return MFB_ERR_ARG;
+    if (!c->have_plan) return MFB_ERR_STATE;
+    if (outputs_per_workgroup) *outputs_per_workgroup = c->plan.tile;
+    if (taps_capacity) *taps_capacity = c->max_taps;
+    return MFB_OK;
+}
+
+// ---- the launches: one function per kind of plan
+// f(tag) with tag::value the CHZ_FMT_* of the plan's sample format / the bins of a uniform handle: the kernels' template arguments
+template <class F>
+static void visit_chz_fmt(int fmt, F f) {
+    if (fmt == MFB_SAMPLES_SC16) f(std::integral_constant<int, CHZ_FMT_SC16>{});
+    else if (fmt == MFB_SAMPLES_SC8) f(std::integral_constant<int, CHZ_FMT_SC8>{});
+    else f(std::integral_constant<int, CHZ_FMT_CF32>{});
+}
+template <class F>
+static void visit_chu_bins(int M, F f) {
+    switch (M) {
+        case 8: f(std::integral_constant<int, 8>{}); break;
+        case 16: f(std::integral_constant<int, 16>{}); break;
+        case 32: f(std::integral_constant<int, 32>{}); break;
+        case 64: f(std::integral_constant<int, 64>{}); break;
+        case 128: f(std::integral_constant<int, 128>{}); break;
+        default: f(std::integral_constant<int, 256>{}); break;
+    }
+}
+
+// the call's window and the plan's D, T, scale: the fields that ChzArgs, ChzrArgs and ChuArgs share
+template <class Args>
+static Args chz_window(const mfb_channelizer *c, const ChzGeom &g, const mfb_channelizer_params *p) {
+    Args A;
+    A.in_base = p->in_base;
+    A.in_end = p->in_base + p->in_count;
+    A.out_base = p->out_base;
+    A.out_count = p->out_count;
+    A.D = g.D;
+    A.T = g.T;
+    A.out_stride = c->out_stride;
+    A.scale = c->scale;
+    return A;
 }
 
 static void chu_launch(mfb_channelizer *c, const mfb_channelizer_params *p, const void *raw) {
-    ChuArgs A;
-    A.in_base = p->in_base;
-    A.in_end = p->in_base + p->in_count;
-    A.out_base = p->out_base;
-    A.out_count = p->out_count;
-    A.D = c->D;
-    A.T = c->T;
-    A.F = c->F;
+    const ChzGeom &g = c->plan;
+    ChuArgs A = chz_window<ChuArgs>(c, g, p);
+    A.F = g.tile;
     A.nsel = c->K;
-    A.out_stride = c->out_stride;
-    A.scale = c->scale;
-    const dim3 grid((unsigned)((p->out_count + c->F - 1) / c->F));
-    const size_t lds = chu_lds_bytes(c->M, c->D, c->T, c->F);
-    float2 *outp = c->d_out[p->buffer].get();
-    switch (c->M) {
-        case 8: chu_launch_m<8>(c, A, grid, lds, raw, outp); break;
-        case 16: chu_launch_m<16>(c, A, grid, lds, raw, outp); break;
-        case 32: chu_launch_m<32>(c, A, grid, lds, raw, outp); break;
-        case 64: chu_launch_m<64>(c, A, grid, lds, raw, outp); break;
-        case 128: chu_launch_m<128>(c, A, grid, lds, raw, outp); break;
-        default: chu_launch_m<256>(c, A, grid, lds, raw, outp); break;
-    }
-}
-
-template <int M, bool WRITE>
-static void chus_launch_m(mfb_channelizer *c, const ChuArgs &A, const ChusArgs &V, dim3 grid, size_t lds, const void *raw, float2 *outp) {
-#define CHUS_LAUNCH(FMT_)                                                                                                             \
-    hipLaunchKernelGGL((k_chus<M, FMT_, WRITE>), grid, dim3(CHU_THREADS), lds, c->stream, A, V, (const ChuPlan *)c->d_uplan, raw, \
-                       (const float *)c->d_h, outp, c->d_svpart.get())
-    if (c->fmt == MFB_SAMPLES_SC16) CHUS_LAUNCH(CHZ_FMT_SC16);
-    else if (c->fmt == MFB_SAMPLES_SC8) CHUS_LAUNCH(CHZ_FMT_SC8);
-    else CHUS_LAUNCH(CHZ_FMT_CF32);
-#undef CHUS_LAUNCH
+    visit_chu_bins(g.M, [&](auto m) {
+        visit_chz_fmt(c->fmt, [&](auto fmt) {
+            hipLaunchKernelGGL((k_chu<decltype(m)::value, decltype(fmt)::value>), dim3(chz_grid(g, p->out_count)), dim3(g.threads), g.lds_bytes,
+                               c->stream, A, (const ChuPlan *)c->d_uplan, raw, (const float *)c->d_h, c->d_out[p->buffer].get());
+        });
+    });
 }
 
 // the survey kernel, with or without the store, and the finishing kernel behind it
-template <bool WRITE>
-static void chus_launch(mfb_channelizer *c, const mfb_channelizer_params *p, const void *raw) {
-    ChuArgs A;
-    A.in_base = p->in_base;
-    A.in_end = p->in_base + p->in_count;
-    A.out_base = p->out_base;
-    A.out_count = p->out_count;
-    A.D = c->D;
-    A.T = c->T;
-    A.F = c->sv_Fs;
+static void chus_launch(mfb_channelizer *c, const mfb_channelizer_params *p, const void *raw, bool write) {
+    const ChzGeom &g = c->survey;
+    ChuArgs A = chz_window<ChuArgs>(c, g, p);
+    A.F = g.tile;
     A.nsel = c->K;
-    A.out_stride = c->out_stride;
-    A.scale = c->scale;
     ChusArgs V;
     V.L = c->sv_L;
-    V.C = c->sv_C;
-    V.M = c->M;
+    V.C = chus_chunk(g, c->sv_L);
+    V.M = g.M;
     V.rank = c->sv_rank;
     V.threshold = c->sv_thr;
-    const dim3 grid((unsigned)((p->out_count + c->sv_Fs - 1) / c->sv_Fs));
-    const size_t lds = chus_lds_bytes(c->M, c->D, c->T, c->sv_Fs);
-    float2 *outp = c->d_out[p->buffer].get();
-    switch (c->M) {
-        case 8: chus_launch_m<8, WRITE>(c, A, V, grid, lds, raw, outp); break;
-        case 16: chus_launch_m<16, WRITE>(c, A, V, grid, lds, raw, outp); break;
-        case 32: chus_launch_m<32, WRITE>(c, A, V, grid, lds, raw, outp); break;
-        case 64: chus_launch_m<64, WRITE>(c, A, V, grid, lds, raw, outp); break;
-        case 128: chus_launch_m<128, WRITE>(c, A, V, grid, lds, raw, outp); break;
-        default: chus_launch_m<256, WRITE>(c, A, V, grid, lds, raw, outp); break;
-    }
+    auto launch = [&](auto wr) {
+        visit_chu_bins(g.M, [&](auto m) {
+            visit_chz_fmt(c->fmt, [&](auto fmt) {
+                hipLaunchKernelGGL((k_chus<decltype(m)::value, decltype(fmt)::value, decltype(wr)::value>), dim3(chz_grid(g, p->out_count)),
+                                   dim3(g.threads), g.lds_bytes, c->stream, A, V, (const ChuPlan *)c->d_uplan, raw, (const float *)c->d_h,
+                                   c->d_out[p->buffer].get(), c->d_svpart.get());
+            });
+        });
+    };
+    if (write) launch(std::true_type{});
+    else launch(std::false_type{});
     hipLaunchKernelGGL(k_chus_finish, dim3((unsigned)(p->out_count / c->sv_L)), dim3(256), 0, c->stream, V, (const float *)c->d_svpart,
                        c->d_svpower.get(), c->d_svfloor.get(), c->d_svmask.get());
 }
 
-// behind the launch of any of the kernels
-static int chz_begun(mfb_channelizer *c, const mfb_channelizer_params *p) {
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->t1, c->stream));
-    HIPCHK(hipEventRecord(c->done, c->stream));
-    c->cur = p->buffer;
-    c->count[p->buffer] = p->out_count;
-    c->nchan[p->buffer] = c->K;
-    c->sv_call = false;
-    c->busy = true;
-    return MFB_OK;
+static void chzr_launch(mfb_channelizer *c, const mfb_channelizer_params *p, const void *raw) {
+    const ChzGeom &g = c->plan;
+    ChzrArgs R = chz_window<ChzrArgs>(c, g, p);
+    R.U = g.U;
+    R.Tb = g.Tb;
+    R.L = g.L;
+    R.S = g.S;
+    R.rD = 1.0f / (float)g.D;
+    R.tap_stride = c->rtap_stride;
+    R.ncplx = c->ncplx;
+    R.nreal = c->K - c->ncplx;
+    visit_chz_fmt(c->fmt, [&](auto fmt) {
+        hipLaunchKernelGGL(k_chzr<decltype(fmt)::value>, dim3(chz_grid(g, p->out_count)), dim3(g.threads), g.lds_bytes, c->stream, R,
+                           (const ChzPlan *)c->d_plan, raw, (const float2 *)c->d_rtaps, c->d_out[p->buffer].get());
+    });
 }
 
-// survey: 0 a plain call; 1 the survey alone; 2 the survey and the outputs (a uniform plan with a survey set)
-static int chz_begin_body(mfb_channelizer *c, const mfb_channelizer_params *p, int survey = 0) {
+static void chz_launch(mfb_channelizer *c, const mfb_channelizer_params *p, const void *raw) {
+    const ChzGeom &g = c->plan;
+    ChzArgs A = chz_window<ChzArgs>(c, g, p);
+    A.L = g.L;
+    A.rD = 1.0f / (float)g.D;
+    A.tap_stride = c->max_taps;
+    A.ncplx = c->ncplx;
+    A.nreal = c->K - c->ncplx;
+    visit_chz_fmt(c->fmt, [&](auto fmt) {
+        hipLaunchKernelGGL(k_chz<decltype(fmt)::value>, dim3(chz_grid(g, p->out_count)), dim3(g.threads), g.lds_bytes, c->stream, A,
+                           (const ChzPlan *)c->d_plan, raw, (const float2 *)c->d_taps, c->d_out[p->buffer].get());
+    });
+}
+
+// kind: the plan's for a plain call, CHZ_SURVEY for a survey call, which writes the output set only if `write`
+static int chz_begin_body(mfb_channelizer *c, const mfb_channelizer_params *p, int kind, bool write = true) {
     HIPCHK(hipSetDevice(c->device));
     const size_t sb = chz_sample_bytes(c->fmt);
     const void *raw = p->device_input;
@@ -4507,75 +4480,25 @@ static int chz_begin_body(mfb_channelizer *c, const mfb_channelizer_params *p, i
     }
     c->count[p->buffer] = 0;
     HIPCHK(hipEventRecord(c->t0, c->stream));
-    if (c->uniform && survey) {
-        if (survey == 2) chus_launch<true>(c, p, raw);
-        else chus_launch<false>(c, p, raw);
-        const int rc = chz_begun(c, p);
-        if (rc) return rc;
-        if (survey != 2) c->count[p->buffer] = 0;  // the set was not written
-        c->sv_call = true;
-        c->sv_wrote = survey == 2;
+    switch (kind) {
+        case CHZ_INTEGER: chz_launch(c, p, raw); break;
+        case CHZ_RATIONAL: chzr_launch(c, p, raw); break;
+        case CHZ_UNIFORM: chu_launch(c, p, raw); break;
+        default: chus_launch(c, p, raw, write); break;
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->t1, c->stream));
+    HIPCHK(hipEventRecord(c->done, c->stream));
+    c->cur = p->buffer;
+    c->count[p->buffer] = write ? p->out_count : 0;    // (0: the set was not written)
+    c->nchan[p->buffer] = c->K;
+    c->sv_call = kind == CHZ_SURVEY;
+    if (c->sv_call) {
+        c->sv_wrote = write;
         c->sv_cells = p->out_count / c->sv_L;
-        return MFB_OK;
     }
-    if (c->uniform) {
-        chu_launch(c, p, raw);
-        return chz_begun(c, p);
-    }
-    if (c->rational) {
-        ChzrArgs R;
-        R.in_base = p->in_base;
-        R.in_end = p->in_base + p->in_count;
-        R.out_base = p->out_base;
-        R.out_count = p->out_count;
-        R.U = c->U;
-        R.D = c->D;
-        R.T = c->T;
-        R.Tb = c->Tb;
-        R.L = c->L;
-        R.S = chzr_span(c->threads, c->U, c->D, c->T);
-        R.rD = 1.0f / (float)c->D;
-        R.tap_stride = c->rtap_stride;
-        R.out_stride = c->out_stride;
-        R.ncplx = c->ncplx;
-        R.nreal = c->K - c->ncplx;
-        R.scale = c->scale;
-        const int tile = c->U * c->threads;
-        const dim3 rgrid((unsigned)((p->out_count + tile - 1) / tile)), rblock(c->threads);
-        const size_t rlds = (size_t)c->D * c->L * sizeof(float2);
-#define CHZR_LAUNCH(FMT_)                                                                                                                \
-    hipLaunchKernelGGL(k_chzr<FMT_>, rgrid, rblock, rlds, c->stream, R, (const ChzPlan *)c->d_plan, raw, (const float2 *)c->d_rtaps, \
-                       c->d_out[p->buffer].get())
-        if (c->fmt == MFB_SAMPLES_SC16) CHZR_LAUNCH(CHZ_FMT_SC16);
-        else if (c->fmt == MFB_SAMPLES_SC8) CHZR_LAUNCH(CHZ_FMT_SC8);
-        else CHZR_LAUNCH(CHZ_FMT_CF32);
-#undef CHZR_LAUNCH
-        return chz_begun(c, p);
-    }
-    ChzArgs A;
-    A.in_base = p->in_base;
-    A.in_end = p->in_base + p->in_count;
-    A.out_base = p->out_base;
-    A.out_count = p->out_count;
-    A.D = c->D;
-    A.T = c->T;
-    A.L = c->L;
-    A.rD = 1.0f / (float)c->D;
-    A.tap_stride = c->max_taps;
-    A.out_stride = c->out_stride;
-    A.ncplx = c->ncplx;
-    A.nreal = c->K - c->ncplx;
-    A.scale = c->scale;
-    const dim3 grid((unsigned)((p->out_count + c->threads - 1) / c->threads)), block(c->threads);
-    const size_t lds = (size_t)c->D * c->L * sizeof(float2);
-#define CHZ_LAUNCH(FMT_)                                                                                                              \
-    hipLaunchKernelGGL(k_chz<FMT_>, grid, block, lds, c->stream, A, (const ChzPlan *)c->d_plan, raw, (const float2 *)c->d_taps, \
-                       c->d_out[p->buffer].get())
-    if (c->fmt == MFB_SAMPLES_SC16) CHZ_LAUNCH(CHZ_FMT_SC16);
-    else if (c->fmt == MFB_SAMPLES_SC8) CHZ_LAUNCH(CHZ_FMT_SC8);
-    else CHZ_LAUNCH(CHZ_FMT_CF32);
-#undef CHZ_LAUNCH
-    return chz_begun(c, p);
+    c->busy = true;
+    return MFB_OK;
 }
 
 // what mfb_channelizer_begin refuses
@@ -4588,12 +4511,13 @@ static int chz_begin_check(mfb_channelizer *c, const mfb_channelizer_params *p) 
     if (p->in_count > c->max_in || p->out_count > c->max_out) return MFB_ERR_ARG;
     if (c->busy) return MFB_ERR_STATE;
     if (!c->have_plan) return MFB_ERR_STATE;
-    if (p->out_base >= (((int64_t)1 << 62) + c->D - 1) / c->D) return MFB_ERR_UNSUPPORTED;       // out_base * D < 2^62
+    const int D = c->plan.D;
+    if (p->out_base >= (((int64_t)1 << 62) + D - 1) / D) return MFB_ERR_UNSUPPORTED;             // out_base * D < 2^62
     if (p->input == MFB_CHZ_INPUT_DEVICE && ((uintptr_t)p->device_input & (chz_sample_bytes(c->fmt) - 1))) return MFB_ERR_ARG;
     if (p->input != MFB_CHZ_INPUT_DEVICE && !c->h_in[p->input == MFB_CHZ_INPUT_PINNED1]) return MFB_ERR_STATE;
     // every input an output reads, apart from the positions below 0, lies inside the call's input
-    // (a rational plan: [q(out_base) - (ceil(T / U) - 1), q(out_base + out_count - 1)], q(m) = (m D) div U; U = 1 otherwise)
-    const int64_t first = p->out_base * c->D / c->U - (c->Tb - 1), last = (p->out_base + p->out_count - 1) * c->D / c->U;
+    int64_t first = 0, last = 0;
+    chz_input_span(c->plan, p->out_base, p->out_count, &first, &last);
     if ((first > 0 ? first : 0) < p->in_base || last >= p->in_base + p->in_count) return MFB_ERR_ARG;
     return MFB_OK;
 }
@@ -4601,18 +4525,23 @@ static int chz_begin_check(mfb_channelizer *c, const mfb_channelizer_params *p) 
 extern "C" int mfb_channelizer_begin(mfb_channelizer *c, const mfb_channelizer_params *p) {
     const int rc = chz_begin_check(c, p);
     if (rc) return rc;
-    return guarded([&] { return chz_begin_body(c, p); });
+    return guarded([&] { return chz_begin_body(c, p, c->plan.kind); });
+}
+
+// the output set of the call in flight to the host, on the stream
+static hipError_t chz_copy_out(mfb_channelizer *c, float *out_c64) {
+    const int b = c->cur;
+    const size_t row = (size_t)c->count[b] * sizeof(float2);
+    return hipMemcpy2DAsync(out_c64, row, c->d_out[b].get(), (size_t)c->out_stride * sizeof(float2), row, (size_t)c->nchan[b], hipMemcpyDeviceToHost,
+                            c->stream);
 }
 
 extern "C" int mfb_channelizer_end(mfb_channelizer *c, float *out_c64) {
     if (!c) return MFB_ERR_ARG;
     if (!c->busy || c->sv_call) return MFB_ERR_STATE;          // (a survey call ends with mfb_channelizer_survey_end)
     HIPCHK(hipSetDevice(c->device));
-    const int b = c->cur;
     if (out_c64) {
-        const size_t row = (size_t)c->count[b] * sizeof(float2);
-        HIPCHK(hipMemcpy2DAsync(out_c64, row, c->d_out[b].get(), (size_t)c->out_stride * sizeof(float2), row, (size_t)c->nchan[b],
-                                hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(chz_copy_out(c, out_c64));
         HIPCHK(hipStreamSynchronize(c->stream));
     } else {
         HIPCHK(hipEventSynchronize(c->done));
@@ -4642,19 +4571,11 @@ static int chus_set_body(mfb_channelizer *c, int cell_frames, int rank, float th
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(chus_drop(c));
     if (!cell_frames) return MFB_OK;
-    const int Fs = chus_frames(c->M, c->D, c->T), C = cell_frames < Fs ? cell_frames : Fs;
-    // the longest call: max_out outputs, M out_count <= 2^26, M out_count / L <= 2^22
-    const int64_t most = (int64_t)c->max_out < (int64_t)CHU_MAX_SET / c->M ? (int64_t)c->max_out : (int64_t)CHU_MAX_SET / c->M;
-    int64_t cells = most / cell_frames;
-    if (cells > CHUS_MAX_TABLE / c->M) cells = CHUS_MAX_TABLE / c->M;
-    const int64_t chunks = cells * (cell_frames / C);
-    const int words = (c->M + 31) / 32;
-    HIPCHK(c->d_svpart.alloc((size_t)chunks * c->M * sizeof(float), hip_malloc));
-    HIPCHK(c->d_svpower.alloc((size_t)cells * c->M * sizeof(float), hip_malloc));
-    HIPCHK(c->d_svfloor.alloc((size_t)cells * sizeof(float), hip_malloc));
-    HIPCHK(c->d_svmask.alloc((size_t)cells * words * sizeof(uint32_t), hip_malloc));
-    c->sv_Fs = Fs;
-    c->sv_C = C;
+    const ChusTables t = chus_tables(c->survey, cell_frames, c->max_out);
+    HIPCHK(c->d_svpart.alloc((size_t)t.chunks * c->M * sizeof(float), hip_malloc));
+    HIPCHK(c->d_svpower.alloc((size_t)t.cells * c->M * sizeof(float), hip_malloc));
+    HIPCHK(c->d_svfloor.alloc((size_t)t.cells * sizeof(float), hip_malloc));
+    HIPCHK(c->d_svmask.alloc((size_t)t.cells * t.words * sizeof(uint32_t), hip_malloc));
     c->sv_rank = rank;
     c->sv_thr = threshold;
     c->sv_L = cell_frames;
@@ -4663,7 +4584,7 @@ static int chus_set_body(mfb_channelizer *c, int cell_frames, int rank, float th
 
 extern "C" int mfb_channelizer_set_survey(mfb_channelizer *c, int cell_frames, int rank, float threshold) {
     if (!c) return MFB_ERR_ARG;
-    if (!c->uniform || !c->have_plan || c->busy) return MFB_ERR_STATE;
+    if (!c->M || !c->have_plan || c->busy) return MFB_ERR_STATE;
     if (cell_frames) {
         if (cell_frames < (1 << CHUS_MIN_LOG2) || cell_frames > (1 << CHUS_MAX_LOG2) || (cell_frames & (cell_frames - 1))) return MFB_ERR_ARG;
         if (rank < 0 || rank >= c->M || !std::isfinite(threshold) || threshold < 1.0f) return MFB_ERR_ARG;
@@ -4676,9 +4597,9 @@ extern "C" int mfb_channelizer_set_survey(mfb_channelizer *c, int cell_frames, i
 
 extern "C" int mfb_channelizer_survey_info(mfb_channelizer *c, int *cell_frames, int *frames_per_workgroup, int *rank, float *threshold) {
     if (!c) return MFB_ERR_ARG;
-    if (!c->uniform || !c->have_plan) return MFB_ERR_STATE;
+    if (!c->M || !c->have_plan) return MFB_ERR_STATE;
     if (cell_frames) *cell_frames = c->sv_L;
-    if (frames_per_workgroup) *frames_per_workgroup = c->sv_L ? c->sv_Fs : chus_frames(c->M, c->D, c->T);
+    if (frames_per_workgroup) *frames_per_workgroup = c->survey.tile;
     if (rank) *rank = c->sv_rank;
     if (threshold) *threshold = c->sv_thr;
     return MFB_OK;
@@ -4686,13 +4607,13 @@ extern "C" int mfb_channelizer_survey_info(mfb_channelizer *c, int *cell_frames,
 
 extern "C" int mfb_channelizer_survey_begin(mfb_channelizer *c, const mfb_channelizer_params *p, int write_outputs) {
     if (!c || !p) return MFB_ERR_ARG;
-    if (!c->uniform) return MFB_ERR_STATE;
+    if (!c->M) return MFB_ERR_STATE;
     const int rc = chz_begin_check(c, p);
     if (rc) return rc;
     if (!c->sv_L) return MFB_ERR_STATE;
     if (p->out_base % c->sv_L || p->out_count % c->sv_L) return MFB_ERR_ARG;
     if ((int64_t)c->M * p->out_count > CHU_MAX_SET || (int64_t)c->M * (p->out_count / c->sv_L) > CHUS_MAX_TABLE) return MFB_ERR_UNSUPPORTED;
-    return guarded([&] { return chz_begin_body(c, p, write_outputs ? 2 : 1); });
+    return guarded([&] { return chz_begin_body(c, p, CHZ_SURVEY, write_outputs != 0); });
 }
 
 extern "C" int mfb_channelizer_survey_end(mfb_channelizer *c, float *out_c64, float *power, float *floor, uint32_t *mask) {
@@ -4700,13 +4621,8 @@ extern "C" int mfb_channelizer_survey_end(mfb_channelizer *c, float *out_c64, fl
     if (!c->busy || !c->sv_call) return MFB_ERR_STATE;         // (a plain call ends with mfb_channelizer_end)
     if (out_c64 && !c->sv_wrote) return MFB_ERR_ARG;           // the call stays in flight
     HIPCHK(hipSetDevice(c->device));
-    const int b = c->cur;
     const size_t cells = (size_t)c->sv_cells;
-    if (out_c64) {
-        const size_t row = (size_t)c->count[b] * sizeof(float2);
-        HIPCHK(hipMemcpy2DAsync(out_c64, row, c->d_out[b].get(), (size_t)c->out_stride * sizeof(float2), row, (size_t)c->nchan[b],
-                                hipMemcpyDeviceToHost, c->stream));
-    }
+    if (out_c64) HIPCHK(chz_copy_out(c, out_c64));
     if (power) HIPCHK(hipMemcpyAsync(power, c->d_svpower, cells * c->M * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (floor) HIPCHK(hipMemcpyAsync(floor, c->d_svfloor, cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (mask) HIPCHK(hipMemcpyAsync(mask, c->d_svmask, cells * ((c->M + 31) / 32) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
