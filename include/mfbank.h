@@ -946,6 +946,64 @@ int mfb_channelizer_survey_info(mfb_channelizer *c, int *cell_frames, int *frame
 int mfb_channelizer_survey_begin(mfb_channelizer *c, const mfb_channelizer_params *params, int write_outputs);
 int mfb_channelizer_survey_end(mfb_channelizer *c, float *out_c64, float *power, float *floor, uint32_t *mask);
 
+typedef struct mfb_synthesizer mfb_synthesizer;
+typedef struct mfb_synthesizer_params {
+    int64_t out_base;         /* absolute wide position of the call's first output */
+    int32_t out_count;
+    int32_t buffer;           /* 0 or 1: the output set the call writes */
+} mfb_synthesizer_params;
+typedef struct mfb_synthesizer_placement {
+    int64_t start;            /* absolute position of the first sample in the bin's narrow stream */
+    int64_t src;              /* its first sample in the source */
+    int32_t length;
+    int32_t bin;              /* 0 .. M - 1 */
+    float gain;
+    int32_t reserved;
+} mfb_synthesizer_placement;
+/* The uniform polyphase synthesiser (csrc/synthesize_uniform_kernels.hpp), the dual of mfb_channelizer_create_uniform: narrowband
+ * streams are put onto the M bins of a raster of one wideband stream, each interpolated by I, filtered with the plan's real taps and
+ * mixed to b fs / M, all with one M-point transform per input frame.  No reference counterpart: the reference makes one narrowband
+ * stream per radio process (pyCuSDR.py:245-251).
+ * x_b[m] = fl(gain source[src + m - start]) (float32, one rounding per component; a gain of 1 multiplies nothing) where a placement
+ * of bin b covers m, 0 elsewhere.  With n the absolute wide position and (q, r) = divmod(n, I):
+ *     w[n] = sum_b e^{+2 pi i b n / M} sum_{j >= 0, r + j I < T} h[r + j I] x_b[q - j]
+ *          = sum_{j >= 0, r + j I < T} h[r + j I] X_{q - j}[n mod M]          X_m[s] = sum_b x_b[m] e^{+2 pi i b s / M}
+ * zero-stuff by I, filter, mix to the exact word b 2^64 / M, without the zero products.  Each output starts from (-0, -0) and adds
+ * j = 0, 1, ... in order, one fused multiply-add per component and tap; w[n] is a pure function of (h, I, M, the placements, n): a
+ * span equals itself under any cut into calls, in either output set, bit for bit.
+ *   mfb_synthesizer_create         a stream, two output sets of max_out complex64, a tap table of max_taps, device room for
+ *                                  max_source source samples and max_frames placements, page-locked staging for the placements.
+ *   mfb_synthesizer_set_plan       I and the taps (wide rate); waits.  2 <= I <= M, I need not divide M.
+ *   mfb_synthesizer_set_source     what the placements read, as mfb_channel_set_source: host samples are copied in (at most
+ *                                  max_source), device memory is used in place and stays the caller's.
+ *   mfb_synthesizer_begin          enqueues the outputs [out_base, out_base + out_count) into output set params->buffer and returns.
+ *                                  placements[n] in any order; those of one bin must not overlap (abutting is allowed); each reads
+ *                                  source[src .. src + length); n = 0: zeros, placements may be NULL.
+ *   mfb_synthesizer_end            waits; out_c64 (may be NULL: the outputs stay on the device) receives out_count complex64.
+ *   mfb_synthesizer_device_output  the call that wrote output set `buffer` last: 16-byte aligned complex64, what
+ *                                  mfb_channelizer_begin takes with MFB_CHZ_INPUT_DEVICE and mfb_channel_set_source with on_device.
+ *                                  Valid until the next _begin on that set.
+ *   mfb_synthesizer_info           frames_per_workgroup: the F input frames whose F I outputs a workgroup makes; rows: the
+ *                                  F + ceil(T / I) - 1 frames it transforms for them.  Either pointer may be NULL.
+ *   mfb_synthesizer_elapsed_ms     device time of the call finished last (events around its kernel).
+ * Misuse is an error code, never a fault, and launches nothing.  MFB_ERR_ARG: NULL where not allowed, counts < 1, a negative
+ * out_base, start or src, a length < 1, a bin outside [0, M), a gain or tap that is not finite, a placement reading outside the
+ * source, overlapping placements on one bin, a buffer outside 0 / 1, more taps, outputs, source samples or placements than the
+ * handle was created for.  MFB_ERR_STATE: _begin, _set_plan or _set_source while a call is in flight, _begin before a plan or a
+ * source, _info without a plan, _end without _begin, _device_output of a set never written or in flight, _elapsed_ms before a call
+ * has finished.  Limits (MFB_ERR_UNSUPPORTED beyond): M one of 8, 16, 32, 64, 128, 256; 2 <= I <= M; 1..4096 taps; 2^24 outputs per
+ * call, 2^26 source samples, 4096 placements; out_base and start < 2^62; a plan whose smallest tile, ceil(T / I) frames of M + 1
+ * complex64 beside the table and the taps, does not fit 64 KiB of LDS -- every plan with ceil(T / I) <= 17 fits. */
+int mfb_synthesizer_create(mfb_synthesizer **out, int device, int nbins, int max_taps, int max_out, int max_source, int max_frames);
+int mfb_synthesizer_destroy(mfb_synthesizer *s);
+int mfb_synthesizer_set_plan(mfb_synthesizer *s, int interp, const float *taps, int ntaps);
+int mfb_synthesizer_set_source(mfb_synthesizer *s, const void *samples_c64, int64_t nsamples, int on_device);
+int mfb_synthesizer_begin(mfb_synthesizer *s, const mfb_synthesizer_params *params, const mfb_synthesizer_placement *placements, int n);
+int mfb_synthesizer_end(mfb_synthesizer *s, float *out_c64);
+int mfb_synthesizer_device_output(mfb_synthesizer *s, int buffer, const void **dev_c64, int64_t *nsamples);
+int mfb_synthesizer_info(mfb_synthesizer *s, int *frames_per_workgroup, int *rows);
+int mfb_synthesizer_elapsed_ms(mfb_synthesizer *s, float *ms);
+
 /* Test seams of the demodulation tail: the three kernels between the matched filters and the bit stream, launched as the product
  * launches them, on INJECTED inputs (tests/test_gpu_demod_tail.py).  Handle-less: device buffers of their own, a synchronous copy
  * back; the product paths do not use them.  MFB_ERR_UNSUPPORTED: more than 2^26 complex64 input elements.

@@ -121,6 +121,17 @@ class ChannelizerParams(C.Structure):
                 ('out_count', C.c_int32), ('input', C.c_int32), ('buffer', C.c_int32)]
 
 
+class SynthesizerParams(C.Structure):
+    """mfb_synthesizer_params of include/mfbank.h."""
+    _fields_ = [('out_base', C.c_int64), ('out_count', C.c_int32), ('buffer', C.c_int32)]
+
+
+class SynthesizerPlacement(C.Structure):
+    """mfb_synthesizer_placement of include/mfbank.h."""
+    _fields_ = [('start', C.c_int64), ('src', C.c_int64), ('length', C.c_int32), ('bin', C.c_int32), ('gain', C.c_float),
+                ('reserved', C.c_int32)]
+
+
 # name -> (restype, argtypes); exactly the prototypes of include/mfbank.h
 PROTOTYPES = {
     'mfb_strerror': (C.c_char_p, [_i]),
@@ -231,6 +242,15 @@ PROTOTYPES = {
     'mfb_channelizer_survey_info': (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _fp]),
     'mfb_channelizer_survey_begin': (_i, [_vp, C.POINTER(ChannelizerParams), _i]),
     'mfb_channelizer_survey_end': (_i, [_vp, _vp, _vp, _vp, _vp]),
+    'mfb_synthesizer_create': (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i, _i]),
+    'mfb_synthesizer_destroy': (_i, [_vp]),
+    'mfb_synthesizer_set_plan': (_i, [_vp, _i, _vp, _i]),
+    'mfb_synthesizer_set_source': (_i, [_vp, _vp, C.c_int64, _i]),
+    'mfb_synthesizer_begin': (_i, [_vp, C.POINTER(SynthesizerParams), _vp, _i]),
+    'mfb_synthesizer_end': (_i, [_vp, _vp]),
+    'mfb_synthesizer_device_output': (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(C.c_int64)]),
+    'mfb_synthesizer_info': (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
+    'mfb_synthesizer_elapsed_ms': (_i, [_vp, _fp]),
     'mfb_timer_start': (_i, [_vp]),
     'mfb_timer_stop': (_i, [_vp, _fp]),
     'mfb_profile_enable': (_i, [_vp, _i]),

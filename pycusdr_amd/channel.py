@@ -180,12 +180,14 @@ class Channel:
 
     def set_source(self, samples):
         """What the frames read: complex samples (copied in), or a ``DeviceBatch`` of the device modulator, used in place
-        (hip back end only; it stays valid until that modulator's next call)."""
-        if isinstance(samples, DeviceBatch):
+        (hip back end only; it stays valid until that modulator's next call), or ``(device_ptr, count)`` of complex64, used in
+        place likewise (a synthesiser's ``device_output``)."""
+        if isinstance(samples, (DeviceBatch, tuple)):
             if self.backend != 'hip':
-                raise ValueError("a DeviceBatch is a source of the 'hip' back end")
-            _lib.check(self.lib.mfb_channel_set_source(self.h, C.c_void_p(samples.ptr), samples.total, 1), 'mfb_channel_set_source')
-            self._keep, self.source_len = samples, samples.total
+                raise ValueError("device memory is a source of the 'hip' back end")
+            ptr, n = (samples.ptr, samples.total) if isinstance(samples, DeviceBatch) else (int(samples[0]), int(samples[1]))
+            _lib.check(self.lib.mfb_channel_set_source(self.h, C.c_void_p(ptr), n, 1), 'mfb_channel_set_source')
+            self._keep, self.source_len = samples, n
             return
         src = np.ascontiguousarray(samples, dtype=np.complex64).reshape(-1)
         if not 1 <= len(src) <= self.max_source:

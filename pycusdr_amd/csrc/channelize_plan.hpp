@@ -1,9 +1,9 @@
 // channelize_plan.hpp -- the channeliser's launch plan: the ONE statement of its limits, of the arithmetic that sizes a workgroup's
-// LDS image, and of what a plan of each kind launches (mfb_channelizer_* in mfbank.hip; the kernels are channelize_kernels.hpp,
-// channelize_rational_kernels.hpp, channelize_uniform_kernels.hpp and channelize_survey_kernels.hpp, which include this for the
-// limits their argument structs and launch bounds use).  Host only and free of HIP, so a plain C++ compiler builds it
-// (tests/csrc/channelize_plan_print.cpp; tests/golden/channelize_plans.json was recorded from the helpers below before ChzGeom
-// was built on them).
+// LDS image, and of what a plan of each kind launches (mfb_channelizer_* and mfb_synthesizer_* in mfbank.hip; the kernels are
+// channelize_kernels.hpp, channelize_rational_kernels.hpp, channelize_uniform_kernels.hpp, channelize_survey_kernels.hpp and
+// synthesize_uniform_kernels.hpp, which include this for the limits their argument structs and launch bounds use).  Host only and
+// free of HIP, so a plain C++ compiler builds it (tests/csrc/channelize_plan_print.cpp and synthesize_plan_print.cpp;
+// tests/golden/channelize_plans.json was recorded from the helpers below before ChzGeom was built on them).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -28,6 +28,10 @@
 #define CHUS_MAX_TABLE (1 << 22)     // (cell, bin) entries per call
 #define CHUS_SCRATCH 256             // floats behind the uniform kernel's LDS
 #define CHZ_CF_BYTES 8               // sizeof(float2): one staged sample, one image word
+#define CHSY_MAX_FRAMES 4096         // placements per call of the synthesiser
+#define CHSY_MAX_OUT (1 << 24)       // wide outputs per call
+#define CHSY_MAX_SOURCE (1 << 26)    // complex64 of a source copied in
+#define CHSY_MAX_TILE 128            // input frames a workgroup makes outputs for, at the most
 
 // ---- the geometry of each kernel (the rules are in the kernel headers' comments)
 // rows of the LDS image for a workgroup of `threads` lanes: ceil(span / D), made odd
@@ -66,6 +70,22 @@ static inline int chu_frames(int M, int D, int T) {
     return F;
 }
 
+// the synthesiser (synthesize_uniform_kernels.hpp): the image of the F + J - 1 input frames that the outputs of F frames read,
+// J = ceil(T / I), rows of M + 1 words; the twiddle table; the taps
+static inline int chsy_rows(int I, int T, int F) { return F + chzr_branch_taps(I, T) - 1; }
+static inline size_t chsy_lds_bytes(int M, int I, int T, int F) {
+    return ((size_t)chsy_rows(I, T, F) * (M + 1) + M) * CHZ_CF_BYTES + (size_t)T * sizeof(float);
+}
+
+// Frames per workgroup of the synthesiser: the largest F <= CHSY_MAX_TILE whose image fits CHU_LDS_BUDGET (a larger tile repeats
+// fewer transforms, (J - 1) / F of them; beyond 128 frames that share is small and the grid of a short call would thin out).
+// 0: not even F = 1 fits, the plan is refused.  J <= 17 always fits: (17 * 257 + 256) * 8 + 4096 * 4 = 53384 bytes at M = 256.
+static inline int chsy_frames(int M, int I, int T) {
+    int F = CHSY_MAX_TILE;
+    while (F > 0 && chsy_lds_bytes(M, I, T, F) > (size_t)CHU_LDS_BUDGET) --F;
+    return F;
+}
+
 static inline size_t chus_lds_bytes(int M, int D, int T, int Fs) { return chu_lds_bytes(M, D, T, Fs) + CHUS_SCRATCH * sizeof(float); }
 
 // frames per workgroup of a survey launch
@@ -78,25 +98,27 @@ static inline int chus_frames(int M, int D, int T) {
 }
 
 // ---- what a plan launches
-enum ChzKind { CHZ_INTEGER = 0, CHZ_RATIONAL = 1, CHZ_UNIFORM = 2, CHZ_SURVEY = 3 };       // k_chz, k_chzr, k_chu, k_chus
+enum ChzKind { CHZ_INTEGER = 0, CHZ_RATIONAL = 1, CHZ_UNIFORM = 2, CHZ_SURVEY = 3, CHZ_SYNTHESIS = 4 };   // k_chz, k_chzr, k_chu, k_chus, k_chsy
 
 struct ChzGeom {
     int kind;
-    int U, D, T;           // interpolation (1 unless rational), decimation, taps
+    int U, D, T;           // interpolation (1 unless rational; the synthesiser's I), decimation (the synthesiser's is 1), taps
     int Tb;                // ceil(T / U): the taps of the longest branch
-    int M;                 // the raster's bins (uniform, survey); 0 otherwise
+    int M;                 // the raster's bins (uniform, survey, synthesis); 0 otherwise
     int threads;           // lanes of a workgroup
-    int tile;              // outputs per workgroup: threads, U threads, F or Fs by kind
+    int tile;              // outputs per workgroup: threads, U threads, F or Fs by kind; synthesis: the F input frames whose F I
+                           // outputs a workgroup makes, 0 where the plan does not fit
     int L;                 // float2 per LDS row (integer, rational); 0 otherwise
     int S;                 // staged positions of a rational plan; 0 otherwise
     size_t lds_bytes;      // dynamic LDS of the launch
 };
 
-// U is read for a rational plan and M for a uniform one or its survey; the limits are the caller's to check
+// U is read for a rational plan and for a synthesis (its I, with D = 1), M for a uniform plan, its survey or a synthesis; the
+// limits are the caller's to check
 static inline ChzGeom chz_geom(int kind, int U, int D, int T, int M) {
     ChzGeom g = {};
     g.kind = kind;
-    g.U = kind == CHZ_RATIONAL ? U : 1;
+    g.U = (kind == CHZ_RATIONAL || kind == CHZ_SYNTHESIS) ? U : 1;
     g.D = D;
     g.T = T;
     g.Tb = chzr_branch_taps(g.U, T);
@@ -119,6 +141,12 @@ static inline ChzGeom chz_geom(int kind, int U, int D, int T, int M) {
             g.tile = chu_frames(M, D, T);
             g.lds_bytes = chu_lds_bytes(M, D, T, g.tile);
             break;
+        case CHZ_SYNTHESIS:
+            g.M = M;
+            g.threads = CHU_THREADS;
+            g.tile = chsy_frames(M, g.U, T);
+            g.lds_bytes = g.tile ? chsy_lds_bytes(M, g.U, T, g.tile) : 0;
+            break;
         default:
             g.M = M;
             g.threads = CHU_THREADS;
@@ -131,6 +159,18 @@ static inline ChzGeom chz_geom(int kind, int U, int D, int T, int M) {
 
 // workgroups of a call of out_count outputs
 static inline unsigned chz_grid(const ChzGeom &g, int out_count) { return (unsigned)((out_count + g.tile - 1) / g.tile); }
+
+// A synthesis tiles the input frames, not the outputs: the wide outputs [out_base, out_base + out_count) belong to the frames
+// out_base div I .. (out_base + out_count - 1) div I, workgroup g taking F of them from (out_base div I) + g F on.
+static inline void chsy_frame_span(const ChzGeom &g, int64_t out_base, int out_count, int64_t *first, int64_t *last) {
+    *first = out_base / g.U;
+    *last = (out_base + out_count - 1) / g.U;
+}
+static inline unsigned chsy_grid(const ChzGeom &g, int64_t out_base, int out_count) {
+    int64_t first = 0, last = 0;
+    chsy_frame_span(g, out_base, out_count, &first, &last);
+    return (unsigned)((last - first + g.tile) / g.tile);
+}
 
 // Every input that the outputs [out_base, out_base + out_count) read lies in [*first, *last]; *first may be negative, positions
 // below 0 read as zero.  A rational plan: [q(out_base) - (Tb - 1), q(out_base + out_count - 1)] with q(m) = (m D) div U, one
