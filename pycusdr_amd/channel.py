@@ -20,8 +20,9 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._handle import OutputStage
 from .modulator import phase
-from .modulator.device import DeviceBatch
+from .modulator.device import DeviceBatch         # noqa: F401  (a source ``set_source`` takes: callers name it from here)
 
 _U = np.uint64
 _M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
@@ -150,7 +151,9 @@ def check_frames(frames, source_len):
         free_from = f.start + f.length
 
 
-class Channel:
+class Channel(OutputStage):
+    PREFIX = 'mfb_channel'
+
     def __init__(self, fs, seed=0, backend='hip', device=0, max_samples=1 << 20, max_source=1 << 20, max_frames=4096):
         if backend not in ('hip', 'host'):
             raise ValueError("backend is 'hip' or 'host'")
@@ -167,36 +170,13 @@ class Channel:
             _lib.check(self.lib.mfb_channel_create(C.byref(self.h), device, self.max_samples, self.max_source, self.max_frames),
                        'mfb_channel_create')
 
-    def close(self):
-        if self.h:
-            self.lib.mfb_channel_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def set_source(self, samples):
         """What the frames read: complex samples (copied in), or a ``DeviceBatch`` of the device modulator, used in place
         (hip back end only; it stays valid until that modulator's next call), or ``(device_ptr, count)`` of complex64, used in
         place likewise (a synthesiser's ``device_output``)."""
-        if isinstance(samples, (DeviceBatch, tuple)):
-            if self.backend != 'hip':
-                raise ValueError("device memory is a source of the 'hip' back end")
-            ptr, n = (samples.ptr, samples.total) if isinstance(samples, DeviceBatch) else (int(samples[0]), int(samples[1]))
-            _lib.check(self.lib.mfb_channel_set_source(self.h, C.c_void_p(ptr), n, 1), 'mfb_channel_set_source')
-            self._keep, self.source_len = samples, n
-            return
-        src = np.ascontiguousarray(samples, dtype=np.complex64).reshape(-1)
-        if not 1 <= len(src) <= self.max_source:
-            raise ValueError(f'1 <= source samples <= max_source = {self.max_source}')
-        if self.backend == 'hip':
-            _lib.check(self.lib.mfb_channel_set_source(self.h, src.ctypes.data, len(src), 0), 'mfb_channel_set_source')
-        else:
+        src = self._set_source(samples)
+        if src is not None and self.backend == 'host':        # (only the model reads the host's samples again)
             self._src = src.copy()
-        self.source_len = len(src)
 
     def frame(self, start, src, length, gain=1.0, doppler_hz=0.0, rate_hz_per_s=0.0, phase_rad=0.0):
         """A descriptor: the carrier is at ``doppler_hz`` at the frame's first sample and moves by ``rate_hz_per_s``."""
@@ -250,24 +230,15 @@ class Channel:
         P = _lib.ChannelParams(base=base, mute_before=mute_before, seed=self.seed, count=count, buffer=self._buffer, sigma=sigma,
                                adc_scale=scale, adc_bits=bits)
         F = frames if isinstance(frames, np.ndarray) else pack_frames(frames)
-        _lib.check(self.lib.mfb_channel_begin(self.h, C.byref(P), F.ctypes.data if len(F) else None, len(F)), 'mfb_channel_begin')
+        self._call('mfb_channel_begin', C.byref(P), F.ctypes.data if len(F) else None, len(F))
         self._count = count
 
     def end(self, copy=True):
-        if self.backend == 'host':
-            out, self._host = self._host, None
-            return out
-        if copy:
-            out = np.empty(self._count, dtype=np.complex64)
-            _lib.check(self.lib.mfb_channel_end(self.h, out.ctypes.data), 'mfb_channel_end')
-            return out
-        _lib.check(self.lib.mfb_channel_end(self.h, None), 'mfb_channel_end')
-        return self.device_output(self._buffer)
+        out = self._end(copy)
+        return out if copy or self.backend == 'host' else self.device_output(self._buffer)     # (not ``copy``: where the window is)
 
     def device_output(self, buffer):
-        ptr, n = C.c_void_p(), C.c_int64()
-        _lib.check(self.lib.mfb_channel_device_output(self.h, buffer, C.byref(ptr), C.byref(n)), 'mfb_channel_device_output')
-        return ptr.value, n.value
+        return self._device_output(buffer)
 
     def model_parts(self, base, count, frames, sigma):
         """The float64 model before rounding, for error bounds: (signal complex128 [count], noise complex128 [count] =

@@ -64,6 +64,7 @@ from fractions import Fraction
 import numpy as np
 
 from . import _lib
+from ._handle import OutputStage
 from .channel import signed_quantise
 from .modulator import phase
 
@@ -192,7 +193,9 @@ def _model_integer(taps, words, D, in_base, x, out_base, out_count):
     return y, S
 
 
-class Channelizer:
+class Channelizer(OutputStage):
+    PREFIX = 'mfb_channelizer'
+
     def __init__(self, fs, decim, taps, freqs_hz, sample_format='cf32', sample_scale=1.0, backend='hip', device=0, max_in=1 << 20,
                  max_out=None, interp=1, force_rational=False):
         """``interp = U``: resample by U / decim (the module docstring); 1 takes the integer kernel, unless ``force_rational``
@@ -211,13 +214,11 @@ class Channelizer:
         if backend == 'hip':
             _lib.check(self.lib.mfb_channelizer_create(C.byref(self.h), device, self.K, self.T, self.max_in, self.max_out),
                        'mfb_channelizer_create')
+            plan = (self.decim, self.taps.ctypes.data, self.T, self.words.ctypes.data, self.K, FORMATS[sample_format], self.scale)
             if self.rational:
-                _lib.check(self.lib.mfb_channelizer_set_plan_rational(self.h, self.interp, self.decim, self.taps.ctypes.data, self.T,
-                                                                      self.words.ctypes.data, self.K, FORMATS[sample_format], self.scale),
-                           'mfb_channelizer_set_plan_rational')
+                self._call('mfb_channelizer_set_plan_rational', self.interp, *plan)
             else:
-                _lib.check(self.lib.mfb_channelizer_set_plan(self.h, self.decim, self.taps.ctypes.data, self.T, self.words.ctypes.data,
-                                                             self.K, FORMATS[sample_format], self.scale), 'mfb_channelizer_set_plan')
+                self._call('mfb_channelizer_set_plan', *plan)
 
     def _check_backend(self, fs, backend, device):
         if backend not in ('hip', 'host'):
@@ -241,25 +242,18 @@ class Channelizer:
 
     def close(self):
         if self.h:
-            self._pinned = [None, None]
-            self.lib.mfb_channelizer_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+            self._pinned = [None, None]                       # (views of page-locked memory that goes with the handle)
+        super().close()
 
     def info(self):
         """(outputs per workgroup, tap capacity) of the plan in force (hip)."""
         a, b = C.c_int(), C.c_int()
-        _lib.check(self.lib.mfb_channelizer_info(self.h, C.byref(a), C.byref(b)), 'mfb_channelizer_info')
+        self._call('mfb_channelizer_info', C.byref(a), C.byref(b))
         return a.value, b.value
 
     def elapsed_ms(self):
         ms = C.c_float()
-        _lib.check(self.lib.mfb_channelizer_elapsed_ms(self.h, C.byref(ms)), 'mfb_channelizer_elapsed_ms')
+        self._call('mfb_channelizer_elapsed_ms', C.byref(ms))
         return ms.value
 
     def needed_input(self, out_base, out_count):
@@ -289,7 +283,7 @@ class Channelizer:
         int16 / int8 [max_in, 2]."""
         if self._pinned[which] is None:
             ptr, nbytes = C.c_void_p(), C.c_size_t()
-            _lib.check(self.lib.mfb_channelizer_input_buffer(self.h, which, C.byref(ptr), C.byref(nbytes)), 'mfb_channelizer_input_buffer')
+            self._call('mfb_channelizer_input_buffer', which, C.byref(ptr), C.byref(nbytes))
             raw = (C.c_uint8 * nbytes.value).from_address(ptr.value)
             if self.sample_format == 'cf32':
                 self._pinned[which] = np.frombuffer(raw, dtype=np.complex64)
@@ -347,25 +341,15 @@ class Channelizer:
             self._host = self.model(in_base, x, out_base, out_count)[0].astype(np.complex64)
             return
         P = self._params(on_device, x, in_base, in_count, out_base, out_count, buffer)
-        _lib.check(self.lib.mfb_channelizer_begin(self.h, C.byref(P)), 'mfb_channelizer_begin')
+        self._call('mfb_channelizer_begin', C.byref(P))
         self._count = out_count
 
     def end(self, copy=True):
-        if self.backend == 'host':
-            out, self._host = self._host, None
-            return out
-        if copy:
-            out = np.empty((self.K, self._count), dtype=np.complex64)
-            _lib.check(self.lib.mfb_channelizer_end(self.h, out.ctypes.data), 'mfb_channelizer_end')
-            return out
-        _lib.check(self.lib.mfb_channelizer_end(self.h, None), 'mfb_channelizer_end')
-        return None
+        return self._end(copy, self.K)                        # complex64 [K, out_count]; not ``copy``: None
 
     def device_output(self, buffer, k):
         """(device_ptr, count) of channel ``k`` in output set ``buffer``."""
-        ptr, n = C.c_void_p(), C.c_int64()
-        _lib.check(self.lib.mfb_channelizer_device_output(self.h, buffer, k, C.byref(ptr), C.byref(n)), 'mfb_channelizer_device_output')
-        return ptr.value, n.value
+        return self._device_output(buffer, k)
 
     def model(self, in_base, samples, out_base, out_count):
         """The definition in float64, mix first, before rounding: (y complex128 [K, out_count], S float64 [out_count]) with
@@ -461,8 +445,8 @@ class UniformChannelizer(Channelizer):
         if backend == 'hip':
             _lib.check(self.lib.mfb_channelizer_create_uniform(C.byref(self.h), device, self.nbins, self.K, self.T, self.max_in, self.max_out),
                        'mfb_channelizer_create_uniform')
-            _lib.check(self.lib.mfb_channelizer_set_plan_uniform(self.h, self.decim, self.taps.ctypes.data, self.T, self.bins.ctypes.data,
-                                                                 self.K, FORMATS[sample_format], self.scale), 'mfb_channelizer_set_plan_uniform')
+            self._call('mfb_channelizer_set_plan_uniform', self.decim, self.taps.ctypes.data, self.T, self.bins.ctypes.data, self.K,
+                       FORMATS[sample_format], self.scale)
 
     @property
     def freqs_hz(self):
@@ -480,7 +464,7 @@ class UniformChannelizer(Channelizer):
         if L == 0:
             self._survey = None
             if self.backend == 'hip':
-                _lib.check(self.lib.mfb_channelizer_set_survey(self.h, 0, 0, 1.0), 'mfb_channelizer_set_survey')
+                self._call('mfb_channelizer_set_survey', 0, 0, 1.0)
             return
         rank = self.nbins // 4 if rank is None else int(rank)
         threshold = float(np.float32(threshold))
@@ -493,14 +477,14 @@ class UniformChannelizer(Channelizer):
         if not (np.isfinite(threshold) and threshold >= 1.0):
             raise ValueError('threshold is finite and >= 1')
         if self.backend == 'hip':
-            _lib.check(self.lib.mfb_channelizer_set_survey(self.h, L, rank, threshold), 'mfb_channelizer_set_survey')
+            self._call('mfb_channelizer_set_survey', L, rank, threshold)
         self._survey = (L, rank, threshold)
 
     def survey_info(self):
         """(frames per workgroup of a survey call, cell_frames, rank, threshold) on the device; cell_frames 0: no survey is set.
         Cells shorter than the first are summed inside a workgroup, longer ones across workgroups."""
         L, F, r, t = C.c_int(), C.c_int(), C.c_int(), C.c_float()
-        _lib.check(self.lib.mfb_channelizer_survey_info(self.h, C.byref(L), C.byref(F), C.byref(r), C.byref(t)), 'mfb_channelizer_survey_info')
+        self._call('mfb_channelizer_survey_info', C.byref(L), C.byref(F), C.byref(r), C.byref(t))
         return F.value, L.value, r.value, t.value
 
     def needed_input_cells(self, first_cell, ncells):
@@ -537,14 +521,13 @@ class UniformChannelizer(Channelizer):
             res = SurveyResult(power, floor, cell_mask(power, floor, threshold), first_cell, L)
             return (res, y[self.bins]) if write else res
         P = self._params(on_device, x, in_base, in_count, out_base, out_count, buffer)
-        _lib.check(self.lib.mfb_channelizer_survey_begin(self.h, C.byref(P), 1 if write else 0), 'mfb_channelizer_survey_begin')
+        self._call('mfb_channelizer_survey_begin', C.byref(P), 1 if write else 0)
         self._count = out_count
         power = np.empty((ncells, self.nbins), dtype=np.float32)
         floor = np.empty(ncells, dtype=np.float32)
         mask = np.empty((ncells, -(-self.nbins // 32)), dtype=np.uint32)
         out = np.empty((self.K, out_count), dtype=np.complex64) if write and copy else None
-        _lib.check(self.lib.mfb_channelizer_survey_end(self.h, out.ctypes.data if out is not None else None, power.ctypes.data, floor.ctypes.data,
-                                                       mask.ctypes.data), 'mfb_channelizer_survey_end')
+        self._call('mfb_channelizer_survey_end', out.ctypes.data if out is not None else None, power.ctypes.data, floor.ctypes.data, mask.ctypes.data)
         res = SurveyResult(power, floor, mask, first_cell, L)
         return (res, out) if write else res
 

@@ -29,6 +29,11 @@
 // no intermediate at all; the two-pass path below stays as the fallback for filters without a short
 // impulse response and for blocks too small to segment, and serves the plain forward transforms.
 //
+// This file keeps the bank (mfb_ctx and everything that serves it).  The six side handles -- sync finder, combiner, modulator,
+// channel, channeliser, synthesiser -- have their host side in sync_api.hpp, combine_api.hpp, mod_api.hpp, channel_api.hpp,
+// channelize_api.hpp and synthesize_uniform_api.hpp, included below where that code stood (one translation unit, as before);
+// what they share is stage_handle.hpp, what they share with the bank mfb_common.hpp.
+//
 // Reference semantics reproduced (file:line in the reference tree, pyCuSDR/):
 //   shift-multiply  demodulator/cuda_kernels.cu:339-373, 174-185
 //   |.|^2 / 2^18 row sums  cuda_kernels.cu:421-480      pick  cuda_kernels.cu:502-597
@@ -75,6 +80,8 @@
 #include "unpack_kernels.hpp"
 #include "hostcopy.hpp"
 #include "hip_owned.hpp"
+#include "mfb_common.hpp"
+#include "stage_handle.hpp"
 #include "record_layout.hpp"
 
 // ------------------------------------------------------------------------------------------------
@@ -250,24 +257,6 @@ struct mfb_ctx {
     size_t raw_cap[4] = {};
 };
 
-#define HIPCHK(x)                                                                            \
-    do {                                                                                     \
-        hipError_t e_ = (x);                                                                 \
-        if (e_ != hipSuccess) {                                                              \
-            fprintf(stderr, "mfbank: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return (e_ == hipErrorOutOfMemory) ? MFB_ERR_ALLOC : MFB_ERR_HIP;               \
-        }                                                                                    \
-    } while (0)
-
-// The one device check: `device` exists (and is below `limit`, where per-device tables are indexed by it) and is now the current one.
-static int device_ok(int device, int limit = INT_MAX) {
-    int ndev = 0;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev || device >= limit) return MFB_ERR_ARG;
-    HIPCHK(hipSetDevice(device));
-    return MFB_OK;
-}
-
 // the handle's stream and -- when a batch has put work there since the last wait -- the second stream of the batch path
 static hipError_t sync_streams(mfb_ctx *c) {
     hipError_t e = hipStreamSynchronize(c->stream);
@@ -276,40 +265,6 @@ static hipError_t sync_streams(mfb_ctx *c) {
         if (e == hipSuccess) c->s2_busy = false;
     }
     return e;
-}
-
-// Device allocations of a handle go through dev_alloc so that a test can make the n-th one fail
-// (mfb_debug_fail_alloc): the only way to exercise the free-on-error path of mfb_create without driving
-// a 288 GB device out of memory.
-static thread_local int g_fail_alloc_countdown = 0;
-static thread_local int g_throw_alloc_countdown = 0;      // nth < 0: the |nth|-th allocation throws std::bad_alloc instead (see guarded)
-static hipError_t dev_alloc(void **p, size_t bytes) {
-    if (g_fail_alloc_countdown > 0 && --g_fail_alloc_countdown == 0) {
-        *p = nullptr;
-        return hipErrorOutOfMemory;
-    }
-    if (g_throw_alloc_countdown > 0 && --g_throw_alloc_countdown == 0) {
-        *p = nullptr;
-        throw std::bad_alloc();
-    }
-    return hipMalloc(p, bytes);
-}
-// No C++ exception leaves the library: the entry points that do host-side preparation (filter analysis, segment spectra, tables:
-// std::vector, std::thread) run inside this; a failed host allocation is MFB_ERR_ALLOC like a failed device allocation.
-template <class F>
-static int guarded(F &&f) noexcept {
-    try {
-        return f();
-    } catch (const std::bad_alloc &) {
-        return MFB_ERR_ALLOC;
-    } catch (...) {
-        return MFB_ERR_STATE;
-    }
-}
-extern "C" int mfb_debug_fail_alloc(int nth) {
-    g_fail_alloc_countdown = nth > 0 ? nth : 0;
-    g_throw_alloc_countdown = nth < 0 ? -nth : 0;
-    return MFB_OK;
 }
 
 extern "C" const char *mfb_strerror(int s) {
@@ -3109,1851 +3064,13 @@ extern "C" int mfb_get_envelope(mfb_ctx *c, float *host) {
     return MFB_OK;
 }
 
-// Workspaces of the (handle-less) sync correlator.  Every call borrows a workspace -- device buffers
-// that only grow, plus a stream of its own -- from a per-device pool and returns it afterwards, so
-// concurrent callers (two decoder threads, two demodulator instances on one device) never share
-// buffers or serialise on the null stream.  The pool itself is guarded by a mutex.
-struct SyncWs {
-    Stream stream;            // (first: it goes last)
-    DevBuf<uint8_t> bits;
-    DevBuf<int8_t> tmpl;
-    DevBuf<int32_t> out;
-    DevBuf<int> seg;        // segcnt | segoff | counts
-    DevBuf<int32_t> hits;   // hit_idx | hit_score
-    size_t cap_bits = 0, cap_tmpl = 0, cap_out = 0, cap_seg = 0, cap_hits = 0;
-    // small calls (one block's bit stream, a few templates): inputs and results each travel as ONE packed copy
-    // through page-locked staging -- every separate copy of pageable memory costs a round trip of its own
-    HostBuf<uint8_t> h_stage;
-    DevBuf<uint8_t> d_stage;
-    size_t cap_hstage = 0, cap_dstage = 0;
-};
-#define SYNC_STAGE_MAX ((size_t)1 << 20)
-#define SYNC_MAX_DEVICES 64
-static std::mutex g_sync_mu;
-static std::vector<SyncWs *> g_sync_pool[SYNC_MAX_DEVICES];
-
-static SyncWs *ws_acquire(int device) {
-    {
-        std::lock_guard<std::mutex> lk(g_sync_mu);
-        auto &pool = g_sync_pool[device];
-        if (!pool.empty()) {
-            SyncWs *w = pool.back();
-            pool.pop_back();
-            return w;
-        }
-    }
-    std::unique_ptr<SyncWs> w(new SyncWs());
-    // highest priority: the decoder's small searches run while the demodulator's stream has the next block's kernels queued
-    int lo = 0, hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    if (hipStreamCreateWithPriority(out(w->stream), hipStreamNonBlocking, hi) != hipSuccess) return nullptr;
-    return w.release();      // (the pool keeps its workspaces until the process exits)
-}
-static void ws_release(int device, SyncWs *w) {
-    std::lock_guard<std::mutex> lk(g_sync_mu);
-    g_sync_pool[device].push_back(w);
-}
-struct WsLease {   // returns the workspace on every exit path
-    int device;
-    SyncWs *w;
-    ~WsLease() {
-        if (w) ws_release(device, w);
-    }
-};
-
-static int ws_reserve(Mem<DevFree> *p, size_t *cap, size_t need) {
-    HIPCHK(reserve(*p, *cap, need, need, hip_malloc));
-    return MFB_OK;
-}
-
-extern "C" int mfb_sync_correlate(int device, const uint8_t *bits, int B, int L, const int8_t *tmpl, int T, int32_t *scores) {
-    if (!bits || !tmpl || !scores || B < 1 || L < 1 || T < 1 || T > 4096) return MFB_ERR_ARG;
-    int rc = device_ok(device, SYNC_MAX_DEVICES);
-    if (rc) return rc;
-    const int outLen = L + T - 1;
-    WsLease lease{device, ws_acquire(device)};
-    if (!lease.w) return MFB_ERR_HIP;
-    SyncWs &w = *lease.w;
-    if ((rc = ws_reserve(&w.bits, &w.cap_bits, (size_t)B * L))) return rc;
-    if ((rc = ws_reserve(&w.tmpl, &w.cap_tmpl, (size_t)T))) return rc;
-    if ((rc = ws_reserve(&w.out, &w.cap_out, (size_t)B * outLen * sizeof(int32_t)))) return rc;
-    HIPCHK(hipMemcpyAsync(w.bits, bits, (size_t)B * L, hipMemcpyHostToDevice, w.stream));
-    HIPCHK(hipMemcpyAsync(w.tmpl, tmpl, (size_t)T, hipMemcpyHostToDevice, w.stream));
-    const int bs = 256;
-    const size_t lds = (size_t)T + bs + T - 1;
-    hipLaunchKernelGGL(k_sync_corr, dim3((outLen + bs - 1) / bs, B), dim3(bs), lds, w.stream, w.bits, w.tmpl, w.out, L, T);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(scores, w.out, (size_t)B * outLen * sizeof(int32_t), hipMemcpyDeviceToHost, w.stream));
-    HIPCHK(hipStreamSynchronize(w.stream));
-    return MFB_OK;
-}
-
-
-// K templates against the same B bit streams; template t: T[t] taps at tmpls + sum(T[0..t)), threshold thr[t];
-// its results sit at counts + t*B, hit_idx / hit_score + t*B*max_hits.
-static int sync_find_impl(int device, const uint8_t *bits, int B, int L, const int8_t *tmpls, const int *T, const int *thr, int K,
-                          int max_hits, int32_t *hit_idx, int32_t *hit_score, int32_t *counts) {
-    if (!bits || !tmpls || !T || !thr || !hit_idx || !hit_score || !counts || B < 1 || L < 1 || K < 1 || K > 16 || max_hits < 1)
-        return MFB_ERR_ARG;
-    size_t taps = 0;
-    int Tmax = 0;
-    for (int t = 0; t < K; ++t) {
-        if (T[t] < 1 || T[t] > 4096) return MFB_ERR_ARG;
-        taps += (size_t)T[t];
-        if (T[t] > Tmax) Tmax = T[t];
-    }
-    int rc = device_ok(device, SYNC_MAX_DEVICES);
-    if (rc) return rc;
-    const int nseg = (L + Tmax - 1 + SYNC_SEG - 1) / SYNC_SEG;      // segments of the longest output
-    WsLease lease{device, ws_acquire(device)};
-    if (!lease.w) return MFB_ERR_HIP;
-    SyncWs &w = *lease.w;
-    const size_t nbits = (size_t)B * L;
-    const size_t res_ints = (size_t)K * B * (1 + 2 * (size_t)max_hits);       // counts | idx | score, template-major
-    const bool packed = align16(taps) + nbits <= SYNC_STAGE_MAX && res_ints * sizeof(int32_t) <= SYNC_STAGE_MAX;
-    if ((rc = ws_reserve(&w.seg, &w.cap_seg, ((size_t)2 * B * nseg) * sizeof(int)))) return rc;
-    if ((rc = ws_reserve(&w.hits, &w.cap_hits, res_ints * sizeof(int32_t)))) return rc;
-    int32_t *d_counts = w.hits, *d_idx = w.hits + (size_t)K * B, *d_sc = d_idx + (size_t)K * B * max_hits;
-    const uint8_t *d_bits;
-    const int8_t *d_tmpl;
-    if (packed) {
-        const size_t in_bytes = align16(taps) + nbits;
-        const size_t hneed = in_bytes > res_ints * sizeof(int32_t) ? in_bytes : res_ints * sizeof(int32_t);
-        HIPCHK(reserve(w.h_stage, w.cap_hstage, hneed, hneed, hip_host_malloc));
-        if ((rc = ws_reserve(&w.d_stage, &w.cap_dstage, in_bytes))) return rc;
-        memcpy(w.h_stage, tmpls, taps);
-        memcpy(w.h_stage + align16(taps), bits, nbits);
-        HIPCHK(hipMemcpyAsync(w.d_stage, w.h_stage, in_bytes, hipMemcpyHostToDevice, w.stream));
-        d_tmpl = (const int8_t *)w.d_stage.get();
-        d_bits = w.d_stage + align16(taps);
-    } else {
-        if ((rc = ws_reserve(&w.bits, &w.cap_bits, nbits))) return rc;
-        if ((rc = ws_reserve(&w.tmpl, &w.cap_tmpl, taps))) return rc;
-        HIPCHK(hipMemcpyAsync(w.bits, bits, nbits, hipMemcpyHostToDevice, w.stream));
-        HIPCHK(hipMemcpyAsync(w.tmpl, tmpls, taps, hipMemcpyHostToDevice, w.stream));
-        d_bits = w.bits;
-        d_tmpl = w.tmpl;
-    }
-    int *segcnt = w.seg, *segoff = w.seg + (size_t)B * nseg;
-    size_t toff = 0;
-    if ((long long)B * nseg * K <= 64) {
-        // the decoder's case: everything in one launch (k_sync_small)
-        SyncSmallArgs sa;
-        size_t o = 0;
-        for (int t = 0; t < K; ++t) {
-            sa.T[t] = T[t];
-            sa.thr[t] = thr[t];
-            sa.toff[t] = (int)o;
-            o += (size_t)T[t];
-        }
-        const size_t lds = (size_t)Tmax + SYNC_SEG + Tmax - 1;
-        hipLaunchKernelGGL(k_sync_small, dim3(K, B), dim3(256), lds, w.stream, d_bits, d_tmpl, sa, B, L, max_hits, d_counts, d_idx, d_sc);
-        HIPCHK(hipGetLastError());
-    } else
-    for (int t = 0; t < K; ++t) {
-        const int Tt = T[t];
-        const int ns = (L + Tt - 1 + SYNC_SEG - 1) / SYNC_SEG;
-        const size_t lds = (size_t)Tt + SYNC_SEG + Tt - 1;
-        int32_t *ci = d_counts + (size_t)t * B, *ii = d_idx + (size_t)t * B * max_hits, *si = d_sc + (size_t)t * B * max_hits;
-        hipLaunchKernelGGL((k_sync_find<false>), dim3(ns, B), dim3(256), lds, w.stream, d_bits, d_tmpl + toff, L, Tt, thr[t], ns, segcnt,
-                           (const int *)nullptr, max_hits, (int32_t *)nullptr, (int32_t *)nullptr);
-        hipLaunchKernelGGL(k_sync_scan, dim3((B + 63) / 64), dim3(64), 0, w.stream, (const int *)segcnt, segoff, ci, B, ns);
-        hipLaunchKernelGGL((k_sync_find<true>), dim3(ns, B), dim3(256), lds, w.stream, d_bits, d_tmpl + toff, L, Tt, thr[t], ns, segcnt,
-                           (const int *)segoff, max_hits, ii, si);
-        HIPCHK(hipGetLastError());
-        toff += (size_t)Tt;
-    }
-    const size_t nc = (size_t)K * B, nh = (size_t)K * B * max_hits;
-    if (packed) {
-        HIPCHK(hipMemcpyAsync(w.h_stage, w.hits, res_ints * sizeof(int32_t), hipMemcpyDeviceToHost, w.stream));
-        HIPCHK(hipStreamSynchronize(w.stream));
-        const int32_t *r = (const int32_t *)w.h_stage.get();
-        memcpy(counts, r, nc * sizeof(int32_t));
-        memcpy(hit_idx, r + nc, nh * sizeof(int32_t));
-        memcpy(hit_score, r + nc + nh, nh * sizeof(int32_t));
-    } else {
-        HIPCHK(hipMemcpyAsync(counts, d_counts, nc * sizeof(int32_t), hipMemcpyDeviceToHost, w.stream));
-        HIPCHK(hipMemcpyAsync(hit_idx, d_idx, nh * sizeof(int32_t), hipMemcpyDeviceToHost, w.stream));
-        HIPCHK(hipMemcpyAsync(hit_score, d_sc, nh * sizeof(int32_t), hipMemcpyDeviceToHost, w.stream));
-        HIPCHK(hipStreamSynchronize(w.stream));
-    }
-    return MFB_OK;
-}
-
-extern "C" int mfb_sync_find(int device, const uint8_t *bits, int B, int L, const int8_t *tmpl, int T, int threshold,
-                             int max_hits, int32_t *hit_idx, int32_t *hit_score, int32_t *counts) {
-    return sync_find_impl(device, bits, B, L, tmpl, &T, &threshold, 1, max_hits, hit_idx, hit_score, counts);
-}
-
-extern "C" int mfb_sync_find_multi(int device, const uint8_t *bits, int B, int L, const int8_t *tmpls, const int *T,
-                                   const int *thresholds, int ntmpl, int max_hits, int32_t *hit_idx, int32_t *hit_score,
-                                   int32_t *counts) {
-    return sync_find_impl(device, bits, B, L, tmpls, T, thresholds, ntmpl, max_hits, hit_idx, hit_score, counts);
-}
-
-// ---- a decoder's own sync finder -------------------------------------------------------------------------------------------
-// The decoder searches the SAME templates in every block's bit stream (DEC:96-113).  A finder object keeps them on the
-// device together with a stream, page-locked staging and result buffers of its own, and splits the search into begin
-// (copy in, enqueue, return) and end (wait, copy out): the caller overlaps the round trip with its other work.
-struct mfb_syncfinder {
-    Stream stream;                 // (first: it goes last)
-    int device = 0, K = 0, max_hits = 0, Tmax = 0;
-    std::vector<int> T, thr;
-    Event done;
-    DevBuf<int8_t> d_tmpl;
-    DevBuf<uint8_t> d_bits;
-    HostBuf<uint8_t> h_bits;
-    int cap_bits = 0;
-    DevBuf<int32_t> d_res;         // counts[K] | idx[K][max_hits] | score[K][max_hits]
-    HostBuf<int32_t> h_res;
-    DevBuf<int> d_seg;             // segcnt | segoff of the multi-pass form (long streams)
-    size_t cap_seg = 0;
-    SyncSmallArgs sa = {};
-    bool busy = false;
-};
-
-static int sf_reserve_bits(mfb_syncfinder *f, int L) {
-    if (L <= f->cap_bits) return MFB_OK;
-    HIPCHK(hipStreamSynchronize(f->stream));
-    f->cap_bits = 0;
-    const int cap = L + L / 2 + 1024;
-    HIPCHK(f->d_bits.alloc((size_t)cap, hip_malloc));
-    HIPCHK(f->h_bits.alloc((size_t)cap, hip_host_malloc));
-    f->cap_bits = cap;
-    return MFB_OK;
-}
-
-extern "C" int mfb_syncfinder_destroy(mfb_syncfinder *f) {
-    if (!f) return MFB_ERR_ARG;
-    (void)hipSetDevice(f->device);
-    if (f->stream) (void)hipStreamSynchronize(f->stream);
-    delete f;
-    return MFB_OK;
-}
-
-struct SfDestroy {
-    void operator()(mfb_syncfinder *f) const { (void)mfb_syncfinder_destroy(f); }
-};
-static int sf_create_impl(mfb_syncfinder *f, const int8_t *tmpls, int max_bits) {
-    int lo = 0, hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    HIPCHK(hipStreamCreateWithPriority(out(f->stream), hipStreamNonBlocking, hi));
-    HIPCHK(hipEventCreateWithFlags(out(f->done), hipEventDisableTiming));
-    size_t taps = 0;
-    for (int t = 0; t < f->K; ++t) {
-        f->sa.T[t] = f->T[t];
-        f->sa.thr[t] = f->thr[t];
-        f->sa.toff[t] = (int)taps;
-        taps += (size_t)f->T[t];
-    }
-    HIPCHK(f->d_tmpl.alloc(taps, hip_malloc));
-    HIPCHK(hipMemcpy(f->d_tmpl, tmpls, taps, hipMemcpyHostToDevice));
-    const size_t res_bytes = (size_t)f->K * (1 + 2 * (size_t)f->max_hits) * sizeof(int32_t);
-    HIPCHK(f->d_res.alloc(res_bytes, hip_malloc));
-    HIPCHK(f->h_res.alloc(res_bytes, hip_host_malloc));
-    return sf_reserve_bits(f, max_bits);
-}
-
-extern "C" int mfb_syncfinder_create(mfb_syncfinder **out, int device, const int8_t *tmpls, const int *T, const int *thresholds, int ntmpl,
-                                     int max_bits, int max_hits) {
-    if (!out) return MFB_ERR_ARG;
-    *out = nullptr;
-    if (!tmpls || !T || !thresholds || ntmpl < 1 || ntmpl > 16 || max_bits < 1 || max_hits < 1) return MFB_ERR_ARG;
-    for (int t = 0; t < ntmpl; ++t)
-        if (T[t] < 1 || T[t] > 4096) return MFB_ERR_ARG;
-    int rc = device_ok(device, SYNC_MAX_DEVICES);
-    if (rc) return rc;
-    std::unique_ptr<mfb_syncfinder, SfDestroy> f(new mfb_syncfinder());
-    f->device = device;
-    f->K = ntmpl;
-    f->max_hits = max_hits;
-    f->T.assign(T, T + ntmpl);
-    f->thr.assign(thresholds, thresholds + ntmpl);
-    f->Tmax = 0;
-    for (int t = 0; t < ntmpl; ++t) f->Tmax = T[t] > f->Tmax ? T[t] : f->Tmax;
-    if ((rc = sf_create_impl(f.get(), tmpls, max_bits))) return rc;
-    *out = f.release();
-    return MFB_OK;
-}
-
-extern "C" int mfb_syncfinder_begin(mfb_syncfinder *f, const uint8_t *bits, int L) {
-    if (!f || !bits || L < 1) return MFB_ERR_ARG;
-    if (f->busy) return MFB_ERR_STATE;
-    HIPCHK(hipSetDevice(f->device));
-    int rc = sf_reserve_bits(f, L);
-    if (rc) return rc;
-    memcpy(f->h_bits, bits, (size_t)L);
-    HIPCHK(hipMemcpyAsync(f->d_bits, f->h_bits, (size_t)L, hipMemcpyHostToDevice, f->stream));
-    const int K = f->K, mh = f->max_hits;
-    int32_t *d_counts = f->d_res, *d_idx = f->d_res + K, *d_sc = d_idx + (size_t)K * mh;
-    const int nseg = (L + f->Tmax - 1 + SYNC_SEG - 1) / SYNC_SEG;
-    if (nseg <= 16) {
-        const size_t lds = (size_t)f->Tmax + SYNC_SEG + f->Tmax - 1;
-        hipLaunchKernelGGL(k_sync_small, dim3(K, 1), dim3(256), lds, f->stream, (const uint8_t *)f->d_bits, (const int8_t *)f->d_tmpl, f->sa, 1,
-                           L, mh, d_counts, d_idx, d_sc);
-    } else {
-        const size_t need = (size_t)2 * nseg * sizeof(int);
-        if (f->cap_seg < need) {
-            HIPCHK(hipStreamSynchronize(f->stream));
-            HIPCHK(reserve(f->d_seg, f->cap_seg, need, need, hip_malloc));
-        }
-        int *segcnt = f->d_seg, *segoff = f->d_seg + nseg;
-        for (int t = 0; t < K; ++t) {
-            const int Tt = f->T[t];
-            const int ns = (L + Tt - 1 + SYNC_SEG - 1) / SYNC_SEG;
-            const size_t lds = (size_t)Tt + SYNC_SEG + Tt - 1;
-            const int8_t *tp = f->d_tmpl + f->sa.toff[t];
-            hipLaunchKernelGGL((k_sync_find<false>), dim3(ns, 1), dim3(256), lds, f->stream, (const uint8_t *)f->d_bits, tp, L, Tt, f->thr[t], ns,
-                               segcnt, (const int *)nullptr, mh, (int32_t *)nullptr, (int32_t *)nullptr);
-            hipLaunchKernelGGL(k_sync_scan, dim3(1), dim3(64), 0, f->stream, (const int *)segcnt, segoff, d_counts + t, 1, ns);
-            hipLaunchKernelGGL((k_sync_find<true>), dim3(ns, 1), dim3(256), lds, f->stream, (const uint8_t *)f->d_bits, tp, L, Tt, f->thr[t], ns,
-                               segcnt, (const int *)segoff, mh, d_idx + (size_t)t * mh, d_sc + (size_t)t * mh);
-        }
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(f->h_res, f->d_res, (size_t)K * (1 + 2 * (size_t)mh) * sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
-    HIPCHK(hipEventRecord(f->done, f->stream));
-    f->busy = true;
-    return MFB_OK;
-}
-
-extern "C" int mfb_syncfinder_end(mfb_syncfinder *f, int32_t *counts, int32_t *hit_idx, int32_t *hit_score) {
-    if (!f || !counts || !hit_idx || !hit_score) return MFB_ERR_ARG;
-    if (!f->busy) return MFB_ERR_STATE;
-    HIPCHK(hipSetDevice(f->device));
-    HIPCHK(hipEventSynchronize(f->done));
-    f->busy = false;
-    const int K = f->K, mh = f->max_hits;
-    const int32_t *r = f->h_res;
-    memcpy(counts, r, (size_t)K * sizeof(int32_t));
-    for (int t = 0; t < K; ++t) {
-        const int n = r[t] < mh ? r[t] : mh;
-        memcpy(hit_idx + (size_t)t * mh, r + K + (size_t)t * mh, (size_t)n * sizeof(int32_t));
-        memcpy(hit_score + (size_t)t * mh, r + K + (size_t)K * mh + (size_t)t * mh, (size_t)n * sizeof(int32_t));
-    }
-    return MFB_OK;
-}
-
-// ---- the soft combiner (combine_kernels.hpp) --------------------------------------------------------------------------------
-// A combiner keeps a stream, page-locked staging and device buffers of its own, like the sync finder above.  Staging layout, host
-// and device alike: master bits | master trust | slave 0 bits | slave 0 trust | ...; results: mfb_combine_result | bits | trust.
-#define CMB_MAX_BITS (1 << 20)
-struct mfb_combiner {
-    Stream stream;             // (first: it goes last)
-    int device = 0, max_bits = 0, max_slaves = 0;
-    Event done;
-    HostBuf<uint8_t> h_in, h_out;
-    DevBuf<uint8_t> d_in, d_out;
-    DevBuf<uint32_t> d_mw, d_sw;
-    DevBuf<int32_t> d_x;
-    DevBuf<cmb_key> d_cand;
-    DevBuf<uint8_t> d_lut;
-    int lut_set = 0;           // bit v: the table for v voters is set
-    bool busy = false;
-    int Lm = 0;
-};
-
-static int cmb_pow2ceil(int n) {
-    int N = 1;
-    while (N < n) N <<= 1;
-    return N;
-}
-
-// pack -> zero x -> correlate -> per-workgroup candidates, all on `s`; returns the number of candidates through *ncand
-static int cmb_enqueue_xcorr(hipStream_t s, const uint8_t *d_slave, int n, int Lmax, const uint32_t *d_mw, uint32_t *d_sw, int32_t *d_x,
-                             cmb_key *d_cand, const mfb_combine_result *d_res, int Lfix, int *ncand) {
-    const int N = cmb_pow2ceil(n);
-    const int NW = N >= 32 ? N / 32 : 1;
-    hipLaunchKernelGGL(k_cmb_pack, dim3((NW * 32 + 255) / 256), dim3(256), 0, s, d_slave, n, (uint32_t)(N - 1), d_sw, NW);
-    HIPCHK(hipMemsetAsync(d_x, 0, (size_t)N * sizeof(int32_t), s));
-    const int L = Lmax < n ? Lmax : n;
-    const int tiles = ((L + 31) / 32 + CMB_TILE - 1) / CMB_TILE;
-    const int gx = (NW + CMB_QB - 1) / CMB_QB;
-    int gy = 1024 / gx;
-    gy = gy < 1 ? 1 : gy > tiles ? tiles : gy;
-    hipLaunchKernelGGL(k_cmb_xcorr, dim3(gx, gy), dim3(256), 0, s, d_mw, (const uint32_t *)d_sw, (uint32_t)(NW - 1), n, N, d_res, Lfix, d_x);
-    if (d_cand) {
-        const int g = (N + CMB_SEG - 1) / CMB_SEG;
-        hipLaunchKernelGGL(k_cmb_top_seg, dim3(g), dim3(256), 0, s, (const int32_t *)d_x, N, d_res, d_cand);
-        *ncand = g * CMB_TOPK;
-    }
-    HIPCHK(hipGetLastError());
-    return MFB_OK;
-}
-
-extern "C" int mfb_combiner_destroy(mfb_combiner *c) {
-    if (!c) return MFB_ERR_ARG;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    delete c;
-    return MFB_OK;
-}
-
-struct CmbDestroy {
-    void operator()(mfb_combiner *c) const { (void)mfb_combiner_destroy(c); }
-};
-static int cmb_create_impl(mfb_combiner *c) {
-    HIPCHK(hipStreamCreateWithFlags(out(c->stream), hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(out(c->done), hipEventDisableTiming));
-    const size_t in_bytes = (size_t)2 * c->max_bits * (1 + c->max_slaves);
-    const size_t out_bytes = sizeof(mfb_combine_result) + (size_t)2 * c->max_bits;
-    const int N = cmb_pow2ceil(c->max_bits);
-    HIPCHK(c->d_in.alloc(in_bytes, hip_malloc));
-    HIPCHK(c->h_in.alloc(in_bytes, hip_host_malloc));
-    HIPCHK(c->d_out.alloc(out_bytes, hip_malloc));
-    HIPCHK(c->h_out.alloc(out_bytes, hip_host_malloc));
-    HIPCHK(c->d_mw.alloc(((size_t)c->max_bits / 32 + 2) * sizeof(uint32_t), hip_malloc));
-    HIPCHK(c->d_sw.alloc(((size_t)N / 32 + 2) * sizeof(uint32_t), hip_malloc));
-    HIPCHK(c->d_x.alloc((size_t)N * sizeof(int32_t), hip_malloc));
-    HIPCHK(c->d_cand.alloc((size_t)(CMB_MAX_BITS / CMB_SEG) * CMB_TOPK * sizeof(cmb_key), hip_malloc));
-    HIPCHK(c->d_lut.alloc((size_t)3 * CMB_LUT_STRIDE, hip_malloc));
-    HIPCHK(hipMemset(c->d_lut, 0, (size_t)3 * CMB_LUT_STRIDE));
-    return MFB_OK;
-}
-
-extern "C" int mfb_combiner_create(mfb_combiner **out, int device, int max_bits, int max_slaves) {
-    if (!out) return MFB_ERR_ARG;
-    *out = nullptr;
-    if (max_bits < 1 || max_slaves < 0) return MFB_ERR_ARG;
-    if (max_bits > CMB_MAX_BITS || max_slaves > MFB_COMBINE_MAX_SLAVES) return MFB_ERR_UNSUPPORTED;
-    int rc = device_ok(device, SYNC_MAX_DEVICES);
-    if (rc) return rc;
-    return guarded([&]() {
-        std::unique_ptr<mfb_combiner, CmbDestroy> c(new mfb_combiner());
-        c->device = device;
-        c->max_bits = max_bits;
-        c->max_slaves = max_slaves;
-        const int rc2 = cmb_create_impl(c.get());
-        if (rc2) return rc2;
-        *out = c.release();
-        return (int)MFB_OK;
-    });
-}
-
-extern "C" int mfb_combiner_set_vote(mfb_combiner *c, int voters, const uint8_t *lut_bits, const int8_t *lut_trust, int entries) {
-    if (!c || !lut_bits || !lut_trust || voters < 2 || voters > MFB_COMBINE_MAX_SLAVES + 1 || entries != 1 << (3 * voters)) return MFB_ERR_ARG;
-    if (c->busy) return MFB_ERR_STATE;
-    HIPCHK(hipSetDevice(c->device));
-    uint8_t *t = c->d_lut + (size_t)(voters - 2) * CMB_LUT_STRIDE;
-    HIPCHK(hipMemcpy(t, lut_bits, (size_t)entries, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(t + 4096, lut_trust, (size_t)entries, hipMemcpyHostToDevice));
-    c->lut_set |= 1 << voters;
-    return MFB_OK;
-}
-
-extern "C" int mfb_combiner_begin(mfb_combiner *c, const mfb_combine_params *p, const uint8_t *master_bits, const int8_t *master_trust,
-                                  const uint8_t *const *slave_bits, const int8_t *const *slave_trust) {
-    if (!c || !p || !master_bits || !master_trust) return MFB_ERR_ARG;
-    const int ns = p->num_slaves, Lm = p->master_len;
-    if (ns < 0 || Lm < 1 || Lm > c->max_bits) return MFB_ERR_ARG;
-    if (ns > MFB_COMBINE_MAX_SLAVES) return MFB_ERR_UNSUPPORTED;
-    if (ns > c->max_slaves || (ns > 0 && (!slave_bits || !slave_trust))) return MFB_ERR_ARG;
-    for (int i = 0; i < ns; ++i)
-        if (p->slave_len[i] < 1 || p->slave_len[i] > c->max_bits || !slave_bits[i] || !slave_trust[i]) return MFB_ERR_ARG;
-    if (c->busy) return MFB_ERR_STATE;
-    for (int v = 2; v <= ns + 1; ++v)
-        if (!(c->lut_set & (1 << v))) return MFB_ERR_STATE;
-    HIPCHK(hipSetDevice(c->device));
-    // one packed copy in
-    size_t off = 0, soff[MFB_COMBINE_MAX_SLAVES] = {};
-    memcpy(c->h_in, master_bits, (size_t)Lm);
-    memcpy(c->h_in + Lm, master_trust, (size_t)Lm);
-    off = (size_t)2 * Lm;
-    for (int i = 0; i < ns; ++i) {
-        const size_t n = (size_t)p->slave_len[i];
-        soff[i] = off;
-        memcpy(c->h_in + off, slave_bits[i], n);
-        memcpy(c->h_in + off + n, slave_trust[i], n);
-        off += 2 * n;
-    }
-    HIPCHK(hipMemcpyAsync(c->d_in, c->h_in, off, hipMemcpyHostToDevice, c->stream));
-    mfb_combine_result *d_res = (mfb_combine_result *)c->d_out.get();
-    hipLaunchKernelGGL(k_cmb_init, dim3(1), dim3(64), 0, c->stream, d_res, Lm, ns);
-    const int MW = (Lm + 31) / 32;
-    hipLaunchKernelGGL(k_cmb_pack, dim3((MW * 32 + 255) / 256), dim3(256), 0, c->stream, (const uint8_t *)c->d_in, Lm, 0xFFFFFFFFu, c->d_mw, MW);
-    CmbVoteArgs va = {};
-    for (int i = 0; i < ns; ++i) {
-        const int n = p->slave_len[i];
-        va.bits[i] = c->d_in + soff[i];
-        va.trust[i] = (const int8_t *)(c->d_in + soff[i] + n);
-        va.n[i] = n;
-        if (n < 16) continue;          // not evaluated, not matched (mfbank.h)
-        int ncand = 0;
-        const int rc = cmb_enqueue_xcorr(c->stream, va.bits[i], n, Lm, c->d_mw, c->d_sw, c->d_x, c->d_cand, d_res, 0, &ncand);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_cmb_decide, dim3(1), dim3(256), 0, c->stream, (const cmb_key *)c->d_cand, ncand, d_res, i, n, p->variance_multiplier,
-                           p->min_length);
-    }
-    uint8_t *d_ob = c->d_out + sizeof(mfb_combine_result);
-    hipLaunchKernelGGL(k_cmb_vote, dim3((Lm + 255) / 256), dim3(256), 0, c->stream, (const mfb_combine_result *)d_res, (const uint8_t *)c->d_in,
-                       (const int8_t *)(c->d_in + Lm), va, (const uint8_t *)c->d_lut, d_ob, (int8_t *)(d_ob + Lm));
-    hipLaunchKernelGGL(k_cmb_finish, dim3(1), dim3(1), 0, c->stream, d_res);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(c->h_out, c->d_out, sizeof(mfb_combine_result) + (size_t)2 * Lm, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipEventRecord(c->done, c->stream));
-    c->Lm = Lm;
-    c->busy = true;
-    return MFB_OK;
-}
-
-extern "C" int mfb_combiner_end(mfb_combiner *c, mfb_combine_result *result, uint8_t *bits, int8_t *trust) {
-    if (!c || !result || !bits || !trust) return MFB_ERR_ARG;
-    if (!c->busy) return MFB_ERR_STATE;
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipEventSynchronize(c->done));
-    c->busy = false;
-    memcpy(result, c->h_out, sizeof(mfb_combine_result));
-    const int L = result->out_len;
-    if (L < 0 || L > c->Lm) return MFB_ERR_HIP;
-    memcpy(bits, c->h_out + sizeof(mfb_combine_result), (size_t)L);
-    memcpy(trust, c->h_out + sizeof(mfb_combine_result) + c->Lm, (size_t)L);
-    return MFB_OK;
-}
-
-extern "C" int mfb_debug_bit_xcorr(int device, const uint8_t *a_bits, int n, const uint8_t *b_bits, int m, int32_t *out) {
-    if (!a_bits || !b_bits || !out || n < 1 || m < 1) return MFB_ERR_ARG;
-    if (n > CMB_MAX_BITS || m > CMB_MAX_BITS) return MFB_ERR_UNSUPPORTED;
-    int rc = device_ok(device, SYNC_MAX_DEVICES);
-    if (rc) return rc;
-    const int N = cmb_pow2ceil(n), MW = (m + 31) / 32;
-    DevBuf<uint8_t> d_a, d_b;
-    DevBuf<uint32_t> d_mw, d_sw;
-    DevBuf<int32_t> d_x;
-    HIPCHK(d_a.alloc((size_t)n, hip_malloc));
-    HIPCHK(d_b.alloc((size_t)m, hip_malloc));
-    HIPCHK(d_mw.alloc(((size_t)MW + 2) * sizeof(uint32_t), hip_malloc));
-    HIPCHK(d_sw.alloc(((size_t)N / 32 + 2) * sizeof(uint32_t), hip_malloc));
-    HIPCHK(d_x.alloc((size_t)N * sizeof(int32_t), hip_malloc));
-    HIPCHK(hipMemcpy(d_a, a_bits, (size_t)n, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_b, b_bits, (size_t)m, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_cmb_pack, dim3((MW * 32 + 255) / 256), dim3(256), 0, nullptr, (const uint8_t *)d_b, m, 0xFFFFFFFFu, d_mw, MW);
-    int ncand = 0;
-    const int rc2 = cmb_enqueue_xcorr(nullptr, d_a, n, m, d_mw, d_sw, d_x, nullptr, nullptr, m, &ncand);
-    if (rc2) return rc2;
-    HIPCHK(hipMemcpy(out, d_x, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return MFB_OK;
-}
-
-// Test seam of the peak stages: what a call runs for slave 0 after its correlation -- init, top-15 per segment, merge and decision,
-// finish: the same kernels, the same grids -- on a correlation x[nlags] of the caller's choice.  No streams, so no vote.
-extern "C" int mfb_debug_combine_peaks(int device, const int32_t *x, int nlags, int n, int master_len, double variance_multiplier,
-                                       int min_length, mfb_combine_result *out) {
-    if (!x || !out || nlags < 1 || n < 1 || master_len < 1) return MFB_ERR_ARG;
-    if (nlags > CMB_MAX_BITS || n > CMB_MAX_BITS || master_len > CMB_MAX_BITS) return MFB_ERR_UNSUPPORTED;
-    for (int i = 0; i < nlags; ++i)
-        if (x[i] < 0) return MFB_ERR_ARG;
-    int rc = device_ok(device, SYNC_MAX_DEVICES);
-    if (rc) return rc;
-    const int g = (nlags + CMB_SEG - 1) / CMB_SEG;
-    DevBuf<int32_t> d_x;
-    DevBuf<cmb_key> d_cand;
-    DevBuf<mfb_combine_result> d_res;
-    HIPCHK(d_x.alloc((size_t)nlags * sizeof(int32_t), hip_malloc));
-    HIPCHK(d_cand.alloc((size_t)g * CMB_TOPK * sizeof(cmb_key), hip_malloc));
-    HIPCHK(d_res.alloc(sizeof(mfb_combine_result), hip_malloc));
-    HIPCHK(hipMemcpy(d_x, x, (size_t)nlags * sizeof(int32_t), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_cmb_init, dim3(1), dim3(64), 0, nullptr, d_res, master_len, 1);
-    hipLaunchKernelGGL(k_cmb_top_seg, dim3(g), dim3(256), 0, nullptr, (const int32_t *)d_x, nlags, (const mfb_combine_result *)d_res, d_cand);
-    hipLaunchKernelGGL(k_cmb_decide, dim3(1), dim3(256), 0, nullptr, (const cmb_key *)d_cand, g * CMB_TOPK, d_res, 0, n, variance_multiplier,
-                       min_length);
-    hipLaunchKernelGGL(k_cmb_finish, dim3(1), dim3(1), 0, nullptr, d_res);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(out, d_res, sizeof(mfb_combine_result), hipMemcpyDeviceToHost));
-    return MFB_OK;
-}
-
-// ---- the modulator (mod_kernels.hpp) -----------------------------------------------------------------------------------------
-// A modulator keeps a stream, page-locked staging and device buffers of its own, like the combiner above.  Staging layout, host
-// and device alike: sample_off int64 [B+1] | d uint64 [B] | init uint64 [B] | bit_off int32 [B+1] | bits uint8 -- 8-byte fields first.
-#define MOD_MAX_FRAME_BITS (1 << 17)
-#define MOD_MAX_FRAMES 4096
-#define MOD_MAX_BITS (1 << 22)
-#define MOD_MAX_SAMPLES (1 << 24)
-struct mfb_modulator {
-    Stream stream;             // (first: it goes last)
-    int device = 0, max_bits = 0, max_samples = 0;
-    Event done;
-    HostBuf<uint8_t> h_in;
-    HostBuf<float> h_out;      // on demand (mfb_modulator_host_buffer)
-    DevBuf<uint8_t> d_in, d_rows;
-    DevBuf<mod_u64> d_symbase, d_P, d_T;
-    DevBuf<float2> d_noise, d_out;
-    int kind = -1, sps = 0;    // kind < 0: no LUT yet
-    int noise_len = 0, pad = 0, min_len = 0;
-    bool busy = false, have = false;
-    int B = 0;
-    int64_t total = 0;         // samples of the batch in flight / finished last
-    std::vector<int64_t> sample_off;
-};
-
-// the quantisation rule of mfbank.h, in IEEE double
-static mod_u64 mod_quantise(double v_rad) {
-    double t = v_rad / 6.283185307179586;
-    t -= floor(t);
-    return t >= 1.0 ? 0 : (mod_u64)(t * 18446744073709551616.0);
-}
-
-static size_t mod_staging_bytes(int B, int nbits) {
-    return (size_t)(B + 1) * 8 + (size_t)B * 16 + (size_t)(B + 1) * 4 + (size_t)nbits;
-}
-
-extern "C" int mfb_modulator_destroy(mfb_modulator *m) {
-    if (!m) return MFB_ERR_ARG;
-    (void)hipSetDevice(m->device);
-    if (m->stream) (void)hipStreamSynchronize(m->stream);
-    delete m;
-    return MFB_OK;
-}
-
-struct ModDestroy {
-    void operator()(mfb_modulator *m) const { (void)mfb_modulator_destroy(m); }
-};
-static int mod_create_impl(mfb_modulator *m) {
-    HIPCHK(hipStreamCreateWithFlags(out(m->stream), hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(out(m->done), hipEventDisableTiming));
-    const int maxB = m->max_bits < MOD_MAX_FRAMES ? m->max_bits : MOD_MAX_FRAMES;
-    const size_t in_bytes = mod_staging_bytes(maxB, m->max_bits);
-    HIPCHK(m->d_in.alloc(in_bytes, hip_malloc));
-    HIPCHK(m->h_in.alloc(in_bytes, hip_host_malloc));
-    HIPCHK(m->d_rows.alloc((size_t)m->max_bits, hip_malloc));
-    HIPCHK(m->d_symbase.alloc((size_t)m->max_bits * sizeof(mod_u64), hip_malloc));
-    HIPCHK(m->d_P.alloc((size_t)MOD_MAX_ROWS * MOD_MAX_SPS * sizeof(mod_u64), hip_malloc));
-    HIPCHK(m->d_T.alloc((size_t)MOD_MAX_ROWS * sizeof(mod_u64), hip_malloc));
-    HIPCHK(m->d_out.alloc((size_t)m->max_samples * sizeof(float2), hip_malloc));
-    HIPCHK(hipMemset(m->d_T, 0, (size_t)MOD_MAX_ROWS * sizeof(mod_u64)));
-    return MFB_OK;
-}
-
-extern "C" int mfb_modulator_create(mfb_modulator **out, int device, int max_bits, int max_samples) {
-    if (!out) return MFB_ERR_ARG;
-    *out = nullptr;
-    if (max_bits < 1 || max_samples < 1) return MFB_ERR_ARG;
-    if (max_bits > MOD_MAX_BITS || max_samples > MOD_MAX_SAMPLES) return MFB_ERR_UNSUPPORTED;
-    int rc = device_ok(device, SYNC_MAX_DEVICES);
-    if (rc) return rc;
-    return guarded([&]() {
-        std::unique_ptr<mfb_modulator, ModDestroy> m(new mfb_modulator());
-        m->device = device;
-        m->max_bits = max_bits;
-        m->max_samples = max_samples;
-        const int rc2 = mod_create_impl(m.get());
-        if (rc2) return rc2;
-        *out = m.release();
-        return (int)MFB_OK;
-    });
-}
-
-static int mod_set_lut_body(mfb_modulator *m, int kind, const double *lut_rad, int rows, int sps) {
-    std::vector<mod_u64> P((size_t)rows * sps), T(MOD_MAX_ROWS, 0);
-    for (int r = 0; r < rows; ++r) {
-        mod_u64 acc = 0;
-        for (int j = 0; j < sps; ++j) {
-            const double v = lut_rad[(size_t)r * sps + j];
-            if (!std::isfinite(v)) return MFB_ERR_ARG;
-            acc += mod_quantise(v);
-            P[(size_t)r * sps + j] = acc;
-        }
-        T[r] = acc;
-    }
-    HIPCHK(hipSetDevice(m->device));
-    HIPCHK(hipStreamSynchronize(m->stream));      // nothing in flight, but mfb_debug_mod_phase may have read the old table last
-    m->kind = -1;
-    m->have = false;                              // the finished batch's rows and scan belong to the old table
-    HIPCHK(hipMemcpy(m->d_P, P.data(), P.size() * sizeof(mod_u64), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(m->d_T, T.data(), T.size() * sizeof(mod_u64), hipMemcpyHostToDevice));
-    m->kind = kind;
-    m->sps = sps;
-    return MFB_OK;
-}
-
-extern "C" int mfb_modulator_set_lut(mfb_modulator *m, int kind, const double *lut_rad, int rows, int sps) {
-    if (!m || !lut_rad || (kind != MFB_MOD_FSK && kind != MFB_MOD_GMSK3) || rows != (kind == MFB_MOD_FSK ? 2 : 8) || sps < 1) return MFB_ERR_ARG;
-    if (sps < 2 || sps > MOD_MAX_SPS) return MFB_ERR_UNSUPPORTED;
-    if (m->busy) return MFB_ERR_STATE;
-    return guarded([&] { return mod_set_lut_body(m, kind, lut_rad, rows, sps); });
-}
-
-extern "C" int mfb_modulator_set_pad(mfb_modulator *m, const float *noise_iq, int noise_len, int pad_len, int min_len) {
-    if (!m || pad_len < 0 || min_len < 0 || noise_len < 0) return MFB_ERR_ARG;
-    const int need = pad_len > min_len ? pad_len : min_len;
-    if (need > 0 && (!noise_iq || noise_len < need)) return MFB_ERR_ARG;
-    if (noise_len > MOD_MAX_SAMPLES) return MFB_ERR_UNSUPPORTED;
-    if (m->busy) return MFB_ERR_STATE;
-    HIPCHK(hipSetDevice(m->device));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    m->have = false;
-    m->pad = m->min_len = m->noise_len = 0;
-    if (need > 0) {
-        HIPCHK(m->d_noise.alloc((size_t)need * sizeof(float2), hip_malloc));
-        HIPCHK(hipMemcpy(m->d_noise, noise_iq, (size_t)need * sizeof(float2), hipMemcpyHostToDevice));
-    }
-    m->noise_len = need;
-    m->pad = pad_len;
-    m->min_len = min_len;
-    return MFB_OK;
-}
-
-static void mod_launch_samples(mfb_modulator *m, const uint8_t *d_stage, mod_u64 *d_words) {
-    const int B = m->B;
-    const int64_t *d_soff = (const int64_t *)d_stage;
-    const mod_u64 *d_d = (const mod_u64 *)(d_stage + (size_t)(B + 1) * 8);
-    const int32_t *d_boff = (const int32_t *)(d_stage + (size_t)(B + 1) * 8 + (size_t)B * 16);
-    hipLaunchKernelGGL(k_mod_samples, dim3((unsigned)((m->total + 255) / 256)), dim3(256), 0, m->stream, (const uint8_t *)m->d_rows,
-                       (const mod_u64 *)m->d_symbase, d_boff, d_soff, B, (const mod_u64 *)m->d_P, d_d, m->sps, 1.0f / (float)m->sps, m->pad,
-                       (const float2 *)m->d_noise, m->d_out.get(), d_words);
-}
-
-static int mod_begin_body(mfb_modulator *m, const uint8_t *bits, const int32_t *bit_off, const double *dphi_rad, int B) {
-    const int nbits = bit_off[B], sps = m->sps, pad = m->pad;
-    // the frames' places in the output
-    m->sample_off.assign((size_t)B + 1, 0);
-    int64_t total = 0;
-    for (int f = 0; f < B; ++f) {
-        int64_t len = (int64_t)(bit_off[f + 1] - bit_off[f]) * sps + 2 * (int64_t)pad;
-        if (len < m->min_len) len = m->min_len;
-        m->sample_off[f] = total;
-        total += len;
-    }
-    m->sample_off[B] = total;
-    if (total > MOD_MAX_SAMPLES) return MFB_ERR_UNSUPPORTED;
-    if (total > m->max_samples) return MFB_ERR_ARG;
-    HIPCHK(hipSetDevice(m->device));
-    uint8_t *h = m->h_in;
-    int64_t *h_soff = (int64_t *)h;
-    mod_u64 *h_d = (mod_u64 *)(h + (size_t)(B + 1) * 8);
-    mod_u64 *h_init = h_d + B;
-    int32_t *h_boff = (int32_t *)(h_init + B);
-    uint8_t *h_bits = (uint8_t *)(h_boff + B + 1);
-    memcpy(h_soff, m->sample_off.data(), (size_t)(B + 1) * 8);
-    for (int f = 0; f < B; ++f) {
-        h_d[f] = dphi_rad ? mod_quantise(dphi_rad[f]) : 0;
-        // FSK_LUT.py:31: - (2 b0 - 1) pi / 2, a quarter turn back for a leading 1 and forward for a leading 0
-        h_init[f] = m->kind == MFB_MOD_FSK ? mod_quantise(bits[bit_off[f]] ? -1.5707963267948966 : 1.5707963267948966) : 0;
-    }
-    memcpy(h_boff, bit_off, (size_t)(B + 1) * 4);
-    memcpy(h_bits, bits, (size_t)nbits);
-    const size_t bytes = mod_staging_bytes(B, nbits);
-    HIPCHK(hipMemcpyAsync(m->d_in, m->h_in, bytes, hipMemcpyHostToDevice, m->stream));
-    const uint8_t *d = m->d_in;
-    const mod_u64 *d_d = (const mod_u64 *)(d + (size_t)(B + 1) * 8);
-    const mod_u64 *d_init = d_d + B;
-    const int32_t *d_boff = (const int32_t *)(d_init + B);
-    const uint8_t *d_bits = (const uint8_t *)(d_boff + B + 1);
-    m->B = B;
-    m->total = total;
-    m->have = false;
-    hipLaunchKernelGGL(k_mod_rows, dim3((nbits + 255) / 256), dim3(256), 0, m->stream, d_bits, d_boff, B, m->kind == MFB_MOD_GMSK3 ? 1 : 0,
-                       m->d_rows.get());
-    hipLaunchKernelGGL(k_mod_scan, dim3(B), dim3(MOD_THREADS), 0, m->stream, (const uint8_t *)m->d_rows, d_boff, (const mod_u64 *)m->d_T, d_d, d_init,
-                       sps, m->d_symbase.get());
-    mod_launch_samples(m, d, nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(m->done, m->stream));
-    m->busy = true;
-    return MFB_OK;
-}
-
-extern "C" int mfb_modulator_begin(mfb_modulator *m, const uint8_t *bits, const int32_t *bit_off, const double *dphi_rad, int B) {
-    if (!m || !bits || !bit_off || B < 1) return MFB_ERR_ARG;
-    if (B > MOD_MAX_FRAMES) return MFB_ERR_UNSUPPORTED;
-    if (bit_off[0] != 0) return MFB_ERR_ARG;
-    if (m->busy || m->kind < 0) return MFB_ERR_STATE;
-    const int min_bits = m->kind == MFB_MOD_GMSK3 ? 2 : 1;
-    for (int f = 0; f < B; ++f) {
-        const int64_t n = (int64_t)bit_off[f + 1] - bit_off[f];
-        if (n < min_bits) return MFB_ERR_ARG;
-        if (n > MOD_MAX_FRAME_BITS) return MFB_ERR_UNSUPPORTED;
-        if (bit_off[f + 1] > m->max_bits) return MFB_ERR_ARG;
-        if (dphi_rad && !std::isfinite(dphi_rad[f])) return MFB_ERR_ARG;
-    }
-    if (B > m->max_bits) return MFB_ERR_ARG;
-    return guarded([&] { return mod_begin_body(m, bits, bit_off, dphi_rad, B); });
-}
-
-extern "C" int mfb_modulator_end(mfb_modulator *m, float *out_iq, int64_t *sample_off) {
-    if (!m) return MFB_ERR_ARG;
-    if (!m->busy) return MFB_ERR_STATE;
-    HIPCHK(hipSetDevice(m->device));
-    if (out_iq) {
-        HIPCHK(hipMemcpyAsync(out_iq, m->d_out, (size_t)m->total * sizeof(float2), hipMemcpyDeviceToHost, m->stream));
-        HIPCHK(hipStreamSynchronize(m->stream));
-    } else {
-        HIPCHK(hipEventSynchronize(m->done));
-    }
-    m->busy = false;
-    m->have = true;
-    if (sample_off) memcpy(sample_off, m->sample_off.data(), (size_t)(m->B + 1) * sizeof(int64_t));
-    return MFB_OK;
-}
-
-extern "C" int mfb_modulator_device_output(mfb_modulator *m, const void **dev_c64, int64_t *nsamples) {
-    if (!m || !dev_c64) return MFB_ERR_ARG;
-    if (m->busy || !m->have) return MFB_ERR_STATE;
-    *dev_c64 = m->d_out.get();
-    if (nsamples) *nsamples = m->total;
-    return MFB_OK;
-}
-
-extern "C" int mfb_modulator_host_buffer(mfb_modulator *m, float **host_iq) {
-    if (!m || !host_iq) return MFB_ERR_ARG;
-    if (!m->h_out) {
-        HIPCHK(hipSetDevice(m->device));
-        HIPCHK(m->h_out.alloc((size_t)m->max_samples * sizeof(float2), hip_host_malloc));
-    }
-    *host_iq = m->h_out;
-    return MFB_OK;
-}
-
-extern "C" int mfb_debug_mod_phase(mfb_modulator *m, uint64_t *words, int64_t capacity) {
-    if (!m || !words) return MFB_ERR_ARG;
-    if (m->busy || !m->have) return MFB_ERR_STATE;
-    if (capacity < m->total) return MFB_ERR_ARG;
-    HIPCHK(hipSetDevice(m->device));
-    DevBuf<mod_u64> d_words;
-    HIPCHK(d_words.alloc((size_t)m->total * sizeof(mod_u64), hip_malloc));
-    mod_launch_samples(m, m->d_in, d_words);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(m->stream));
-    HIPCHK(hipMemcpy(words, d_words, (size_t)m->total * sizeof(mod_u64), hipMemcpyDeviceToHost));
-    return MFB_OK;
-}
-
-// ---- the channel (channel_kernels.hpp) ----------------------------------------------------------------------------------------
-#define CHAN_MAX_SAMPLES (1 << 24)
-#define CHAN_MAX_SOURCE (1 << 26)
-#define CHAN_MAX_FRAMES (1 << 20)
-static_assert(sizeof(ChanFrame) == sizeof(mfb_channel_frame) && sizeof(ChanFrame) == 48, "the descriptors are copied as they come");
-struct mfb_channel {
-    Stream stream;             // (first: it goes last)
-    int device = 0, max_samples = 0, max_source = 0, max_frames = 0;
-    Event done;
-    HostBuf<ChanFrame> h_frames;
-    DevBuf<ChanFrame> d_frames;
-    DevBuf<float2> d_out[2];   // max_samples + 2 each: the aligned pair in front of an odd base, and behind an odd end
-    DevBuf<float2> d_src;
-    const float2 *src = nullptr;        // d_src, or the caller's device pointer
-    int64_t src_count = 0;
-    bool busy = false;
-    int cur = 0;               // the buffer of the call in flight
-    int64_t base[2] = {0, 0};
-    int count[2] = {0, 0};     // 0: never rendered
-};
-
-extern "C" int mfb_channel_destroy(mfb_channel *c) {
-    if (!c) return MFB_ERR_ARG;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    delete c;
-    return MFB_OK;
-}
-
-struct ChanDestroy {
-    void operator()(mfb_channel *c) const { (void)mfb_channel_destroy(c); }
-};
-static int chan_create_impl(mfb_channel *c) {
-    HIPCHK(hipStreamCreateWithFlags(out(c->stream), hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(out(c->done), hipEventDisableTiming));
-    HIPCHK(c->h_frames.alloc((size_t)c->max_frames * sizeof(ChanFrame), hip_host_malloc));
-    HIPCHK(c->d_frames.alloc((size_t)c->max_frames * sizeof(ChanFrame), hip_malloc));
-    for (int b = 0; b < 2; ++b) HIPCHK(c->d_out[b].alloc(((size_t)c->max_samples + 2) * sizeof(float2), hip_malloc));
-    HIPCHK(c->d_src.alloc((size_t)c->max_source * sizeof(float2), hip_malloc));
-    return MFB_OK;
-}
-
-extern "C" int mfb_channel_create(mfb_channel **out, int device, int max_samples, int max_source, int max_frames) {
-    if (!out) return MFB_ERR_ARG;
-    *out = nullptr;
-    if (max_samples < 1 || max_source < 1 || max_frames < 1) return MFB_ERR_ARG;
-    if (max_samples > CHAN_MAX_SAMPLES || max_source > CHAN_MAX_SOURCE || max_frames > CHAN_MAX_FRAMES) return MFB_ERR_UNSUPPORTED;
-    int rc = device_ok(device, SYNC_MAX_DEVICES);
-    if (rc) return rc;
-    return guarded([&]() {
-        std::unique_ptr<mfb_channel, ChanDestroy> c(new mfb_channel());
-        c->device = device;
-        c->max_samples = max_samples;
-        c->max_source = max_source;
-        c->max_frames = max_frames;
-        const int rc2 = chan_create_impl(c.get());
-        if (rc2) return rc2;
-        *out = c.release();
-        return (int)MFB_OK;
-    });
-}
-
-extern "C" int mfb_channel_set_source(mfb_channel *c, const void *samples_c64, int64_t nsamples, int on_device) {
-    if (!c || !samples_c64 || nsamples < 1) return MFB_ERR_ARG;
-    if (!on_device && nsamples > c->max_source) return MFB_ERR_ARG;
-    if (c->busy) return MFB_ERR_STATE;
-    HIPCHK(hipSetDevice(c->device));
-    c->src = nullptr;
-    c->src_count = 0;
-    if (on_device) {
-        c->src = (const float2 *)samples_c64;
-    } else {
-        HIPCHK(hipMemcpy(c->d_src, samples_c64, (size_t)nsamples * sizeof(float2), hipMemcpyHostToDevice));
-        c->src = c->d_src;
-    }
-    c->src_count = nsamples;
-    return MFB_OK;
-}
-
-// a positive, finite power of two whose reciprocal is one too
-static bool chan_scale_ok(float s) {
-    int e = 0;
-    return std::isfinite(s) && s > 0.0f && frexpf(s, &e) == 0.5f && e > -100 && e < 100;
-}
-
-static int chan_begin_body(mfb_channel *c, const mfb_channel_params *P, const mfb_channel_frame *frames, int nframes) {
-    HIPCHK(hipSetDevice(c->device));
-    if (nframes) {
-        memcpy(c->h_frames.get(), frames, (size_t)nframes * sizeof(ChanFrame));
-        HIPCHK(hipMemcpyAsync(c->d_frames, c->h_frames, (size_t)nframes * sizeof(ChanFrame), hipMemcpyHostToDevice, c->stream));
-    }
-    ChanArgs A;
-    A.base = P->base;
-    A.mute_before = P->mute_before;
-    A.count = P->count;
-    A.nframes = nframes;
-    A.key0 = (uint32_t)P->seed;
-    A.key1 = (uint32_t)(P->seed >> 32);
-    A.sigma = P->sigma;
-    A.adc_bits = P->adc_bits;
-    A.adc_scale = P->adc_bits ? P->adc_scale : 1.0f;
-    A.adc_inv = 1.0f / A.adc_scale;
-    const int64_t pairs = ((P->base + P->count + 1) >> 1) - (P->base >> 1);      // <= max_samples / 2 + 1: inside max_samples + 2
-    c->count[P->buffer] = 0;
-    hipLaunchKernelGGL(k_chan_render, dim3((unsigned)((pairs + CHAN_THREADS - 1) / CHAN_THREADS)), dim3(CHAN_THREADS), 0, c->stream, A,
-                       (const ChanFrame *)c->d_frames, c->src, c->d_out[P->buffer].get());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->done, c->stream));
-    c->cur = P->buffer;
-    c->base[P->buffer] = P->base;
-    c->count[P->buffer] = P->count;
-    c->busy = true;
-    return MFB_OK;
-}
-
-extern "C" int mfb_channel_begin(mfb_channel *c, const mfb_channel_params *P, const mfb_channel_frame *frames, int nframes) {
-    if (!c || !P || nframes < 0 || (nframes > 0 && !frames)) return MFB_ERR_ARG;
-    if (P->count < 1 || P->base < 0 || P->mute_before < 0 || (P->buffer != 0 && P->buffer != 1)) return MFB_ERR_ARG;
-    if (P->count > CHAN_MAX_SAMPLES || P->base >= ((int64_t)1 << 62) || nframes > CHAN_MAX_FRAMES) return MFB_ERR_UNSUPPORTED;
-    if (P->count > c->max_samples || nframes > c->max_frames) return MFB_ERR_ARG;
-    if (!std::isfinite(P->sigma) || P->sigma < 0.0f) return MFB_ERR_ARG;
-    if (P->adc_bits != 0 && P->adc_bits != 8 && P->adc_bits != 16) return MFB_ERR_ARG;
-    if (P->adc_bits && !chan_scale_ok(P->adc_scale)) return MFB_ERR_ARG;
-    if (c->busy) return MFB_ERR_STATE;
-    if (nframes > 0 && !c->src) return MFB_ERR_STATE;
-    int64_t free_from = 0;          // the first position the next frame may take
-    for (int f = 0; f < nframes; ++f) {
-        const mfb_channel_frame &F = frames[f];
-        if (F.length < 1 || F.start < free_from || F.start >= ((int64_t)1 << 62) || !std::isfinite(F.gain)) return MFB_ERR_ARG;
-        if (F.src < 0 || F.src > c->src_count - F.length) return MFB_ERR_ARG;
-        free_from = F.start + F.length;
-    }
-    return guarded([&] { return chan_begin_body(c, P, frames, nframes); });
-}
-
-extern "C" int mfb_channel_end(mfb_channel *c, float *out_iq) {
-    if (!c) return MFB_ERR_ARG;
-    if (!c->busy) return MFB_ERR_STATE;
-    HIPCHK(hipSetDevice(c->device));
-    const int b = c->cur;
-    if (out_iq) {
-        HIPCHK(hipMemcpyAsync(out_iq, c->d_out[b].get() + (c->base[b] & 1), (size_t)c->count[b] * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    } else {
-        HIPCHK(hipEventSynchronize(c->done));
-    }
-    c->busy = false;
-    return MFB_OK;
-}
-
-extern "C" int mfb_channel_device_output(mfb_channel *c, int buffer, const void **dev_c64, int64_t *nsamples) {
-    if (!c || !dev_c64 || (buffer != 0 && buffer != 1)) return MFB_ERR_ARG;
-    if ((c->busy && c->cur == buffer) || !c->count[buffer]) return MFB_ERR_STATE;
-    *dev_c64 = c->d_out[buffer].get() + (c->base[buffer] & 1);
-    if (nsamples) *nsamples = c->count[buffer];
-    return MFB_OK;
-}
-
-extern "C" int mfb_debug_channel_normals(int device, const uint32_t *words, int npairs, float *out) {
-    if (!words || !out || npairs < 1) return MFB_ERR_ARG;
-    if (npairs > CHAN_MAX_SAMPLES) return MFB_ERR_UNSUPPORTED;
-    int rc = device_ok(device, SYNC_MAX_DEVICES);
-    if (rc) return rc;
-    return guarded([&]() {
-        DevBuf<uint32_t> d_w;
-        DevBuf<float2> d_o;
-        HIPCHK(d_w.alloc((size_t)npairs * 8, hip_malloc));
-        HIPCHK(d_o.alloc((size_t)npairs * 8, hip_malloc));
-        HIPCHK(hipMemcpy(d_w, words, (size_t)npairs * 8, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_chan_normals, dim3((npairs + 255) / 256), dim3(256), 0, 0, (const uint32_t *)d_w, npairs, d_o.get());
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipMemcpy(out, d_o, (size_t)npairs * 8, hipMemcpyDeviceToHost));
-        return (int)MFB_OK;
-    });
-}
-
-// ---- the channeliser (channelize_plan.hpp: the limits and what a plan of each kind launches; the kernels: channelize_kernels.hpp,
-// channelize_rational_kernels.hpp, channelize_uniform_kernels.hpp, channelize_survey_kernels.hpp) -------------------------------
-struct mfb_channelizer {
-    Stream stream;             // (first: it goes last)
-    int device = 0, max_channels = 0, max_taps = 0, max_in = 0, max_out = 0;
-    int M = 0;                 // the bins of a handle made by mfb_channelizer_create_uniform, which takes plans of
-                               // mfb_channelizer_set_plan_uniform only; 0: made by mfb_channelizer_create
-    int out_stride = 0;        // float2 between two channels of an output set: max_out made even, so every channel is 16-byte aligned
-    Event done, t0, t1;
-    HostBuf<uint8_t> h_in[2];  // page-locked raw staging, on demand (mfb_channelizer_input_buffer)
-    DevBuf<uint8_t> d_in[2];   // their device copies, on demand
-    DevBuf<float> d_h;
-    DevBuf<ChzPlan> d_plan;
-    DevBuf<float2> d_taps;     // [max_channels][max_taps]
-    DevBuf<float2> d_rtaps;    // a rational plan's tables by branch, [max_channels][rtap_stride], on demand
-    DevBuf<float2> d_out[2];   // [max_channels][out_stride]
-    bool have_plan = false, busy = false;
-    ChzGeom plan = {};         // what a call of the plan in force launches; its kind says which kernel
-    ChzGeom survey = {};       // what a survey call of a uniform plan launches (CHZ_SURVEY)
-    int K = 0, fmt = 0, ncplx = 0;
-    int rtap_stride = 0;       // max_taps + CHZR_MAX_INTERP - 1 >= U Tb
-    DevBuf<ChuPlan> d_uplan;   // a uniform handle's twiddle table and the selected bins' columns
-    float scale = 1.0f;
-    int cur = 0;               // the buffer of the call in flight
-    int count[2] = {0, 0};     // 0: never written
-    int nchan[2] = {0, 0};     // the plan's channels when it was
-    // the survey of a uniform plan (mfb_channelizer_set_survey)
-    int sv_L = 0;              // frames per cell; 0: no survey set
-    int sv_rank = 0;
-    float sv_thr = 0.0f;
-    DevBuf<float> d_svpart;    // [chunks][M]
-    DevBuf<float> d_svpower;   // [cells][M]
-    DevBuf<float> d_svfloor;   // [cells]
-    DevBuf<uint32_t> d_svmask; // [cells][ceil(M / 32)]
-    bool sv_call = false;      // the call in flight, or finished last, came from mfb_channelizer_survey_begin
-    bool sv_wrote = false;     // and wrote its output set
-    int sv_cells = 0;          // its cells
-};
-
-static size_t chz_sample_bytes(int fmt) { return fmt == MFB_SAMPLES_SC16 ? 4 : fmt == MFB_SAMPLES_SC8 ? 2 : 8; }
-
-extern "C" int mfb_channelizer_destroy(mfb_channelizer *c) {
-    if (!c) return MFB_ERR_ARG;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    delete c;
-    return MFB_OK;
-}
-
-struct ChzDestroy {
-    void operator()(mfb_channelizer *c) const { (void)mfb_channelizer_destroy(c); }
-};
-static int chz_create_impl(mfb_channelizer *c) {
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamCreateWithFlags(out(c->stream), hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(out(c->done), hipEventDisableTiming));
-    HIPCHK(hipEventCreate(out(c->t0)));
-    HIPCHK(hipEventCreate(out(c->t1)));
-    HIPCHK(c->d_h.alloc((size_t)c->max_taps * sizeof(float), hip_malloc));
-    if (c->M) {
-        HIPCHK(c->d_uplan.alloc(sizeof(ChuPlan), hip_malloc));
-    } else {
-        HIPCHK(c->d_plan.alloc(sizeof(ChzPlan), hip_malloc));
-        HIPCHK(c->d_taps.alloc((size_t)c->max_channels * c->max_taps * sizeof(float2), hip_malloc));
-    }
-    for (int b = 0; b < 2; ++b) HIPCHK(c->d_out[b].alloc((size_t)c->max_channels * c->out_stride * sizeof(float2), hip_malloc));
-    return MFB_OK;
-}
-
-// behind the argument checks of either create; nbins: 0 for mfb_channelizer_create
-static int chz_create(mfb_channelizer **out, int device, int nbins, int max_channels, int max_taps, int max_in, int max_out) {
-    int rc = device_ok(device, SYNC_MAX_DEVICES);
-    if (rc) return rc;
-    return guarded([&]() {
-        std::unique_ptr<mfb_channelizer, ChzDestroy> c(new mfb_channelizer());
-        c->device = device;
-        c->M = nbins;
-        c->max_channels = max_channels;
-        c->max_taps = max_taps;
-        c->max_in = max_in;
-        c->max_out = max_out;
-        c->out_stride = (max_out + 1) & ~1;
-        const int rc2 = chz_create_impl(c.get());
-        if (rc2) return rc2;
-        *out = c.release();
-        return (int)MFB_OK;
-    });
-}
-
-extern "C" int mfb_channelizer_create(mfb_channelizer **out, int device, int max_channels, int max_taps, int max_in, int max_out) {
-    if (!out) return MFB_ERR_ARG;
-    *out = nullptr;
-    if (max_channels < 1 || max_taps < 1 || max_in < 1 || max_out < 1) return MFB_ERR_ARG;
-    if (max_channels > CHZ_MAX_CHANNELS || max_taps > CHZ_MAX_TAPS || max_in > CHZ_MAX_IN || max_out > CHZ_MAX_OUT) return MFB_ERR_UNSUPPORTED;
-    return chz_create(out, device, 0, max_channels, max_taps, max_in, max_out);
-}
-
-static bool chu_bins_ok(int M) { return M == 8 || M == 16 || M == 32 || M == 64 || M == 128 || M == 256; }
-
-extern "C" int mfb_channelizer_create_uniform(mfb_channelizer **out, int device, int nbins, int max_selected, int max_taps, int max_in,
-                                              int max_out) {
-    if (!out) return MFB_ERR_ARG;
-    *out = nullptr;
-    if (nbins < 1 || max_selected < 1 || max_taps < 1 || max_in < 1 || max_out < 1) return MFB_ERR_ARG;
-    if (!chu_bins_ok(nbins) || max_selected > nbins || max_taps > CHU_MAX_TAPS || max_in > CHZ_MAX_IN || max_out > CHZ_MAX_OUT)
-        return MFB_ERR_UNSUPPORTED;
-    if ((int64_t)max_selected * max_out > CHU_MAX_SET) return MFB_ERR_UNSUPPORTED;
-    return chz_create(out, device, nbins, max_selected, max_taps, max_in, max_out);
-}
-
-// What every set_plan refuses, in the order of the codes: `which` are the plan's n tuning words or selected bins; kind_tests() the
-// limits and the arguments of the one kind of plan, MFB_ERR_UNSUPPORTED before MFB_ERR_ARG.  *scale: the scale the plan runs with.
-template <class KindTests>
-static int chz_plan_check(mfb_channelizer *c, bool uniform, const float *taps, int ntaps, const void *which, int n, int fmt, float sample_scale,
-                          float *scale, KindTests kind_tests) {
-    if (!c || !taps || !which || ntaps < 1 || n < 1) return MFB_ERR_ARG;
-    if ((c->M != 0) != uniform) return MFB_ERR_STATE;
-    if (!chz_format_ok(fmt)) return MFB_ERR_ARG;
-    const int rc = kind_tests();
-    if (rc) return rc;
-    if (ntaps > c->max_taps || n > c->max_channels) return MFB_ERR_ARG;
-    if (!chz_plan_scale(fmt, sample_scale, chan_scale_ok, scale) || !chz_taps_finite(taps, ntaps)) return MFB_ERR_ARG;
-    return c->busy ? MFB_ERR_STATE : MFB_OK;
-}
-
-// The plan's taps and table are on their way on the stream: wait for them (both are the caller's, or the caller's frame's), then
-// the plan is in force.  Until here a set_plan that fails leaves the handle without a plan.
-static int chz_plan_commit(mfb_channelizer *c, const ChzGeom &g, int K, int ncplx, int fmt, float scale) {
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->plan = g;
-    c->K = K;
-    c->ncplx = ncplx;
-    c->fmt = fmt;
-    c->scale = scale;
-    c->count[0] = c->count[1] = 0;                 // what the buffers hold belongs to the plan before
-    c->have_plan = true;
-    return MFB_OK;
-}
-
-static int chz_set_plan_body(mfb_channelizer *c, const ChzGeom &g, const float *taps, const uint64_t *freq_words, int nchan, int fmt,
-                             float scale) {
-    HIPCHK(hipSetDevice(c->device));
-    if (g.kind == CHZ_RATIONAL && !c->d_rtaps) {
-        c->rtap_stride = c->max_taps + CHZR_MAX_INTERP - 1;
-        HIPCHK(c->d_rtaps.alloc((size_t)c->max_channels * c->rtap_stride * sizeof(float2), hip_malloc));
-    }
-    ChzPlan P;
-    memset(&P, 0, sizeof(P));
-    int ncplx = 0, at = 0;
-    for (int k = 0; k < nchan; ++k) {
-        P.freq[k] = freq_words[k];
-        if (freq_words[k] != 0) P.order[ncplx++] = k;
-    }
-    at = ncplx;
-    for (int k = 0; k < nchan; ++k)
-        if (freq_words[k] == 0) P.order[at++] = k;
-    c->have_plan = false;
-    HIPCHK(hipMemcpyAsync(c->d_h, taps, (size_t)g.T * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_plan, &P, sizeof(P), hipMemcpyHostToDevice, c->stream));
-    if (g.kind == CHZ_RATIONAL)
-        hipLaunchKernelGGL(k_chzr_taps, dim3((g.U * g.Tb + 255) / 256, nchan), dim3(256), 0, c->stream, (const float *)c->d_h,
-                           (const ChzPlan *)c->d_plan, g.U, g.T, g.Tb, c->rtap_stride, c->d_rtaps.get());
-    else
-        hipLaunchKernelGGL(k_chz_taps, dim3((g.T + 255) / 256, nchan), dim3(256), 0, c->stream, (const float *)c->d_h, (const ChzPlan *)c->d_plan,
-                           g.T, c->max_taps, c->d_taps.get());
-    HIPCHK(hipGetLastError());
-    return chz_plan_commit(c, g, nchan, ncplx, fmt, scale);
-}
-
-// kind: CHZ_INTEGER (interp 1) or CHZ_RATIONAL, which runs k_chzr also at U = 1
-static int chz_set_plan(mfb_channelizer *c, int kind, int interp, int decim, const float *taps, int ntaps, const uint64_t *freq_words, int nchan,
-                        int sample_format, float sample_scale) {
-    float scale = 1.0f;
-    const int rc = chz_plan_check(c, false, taps, ntaps, freq_words, nchan, sample_format, sample_scale, &scale, [&]() -> int {
-        if (decim < 2 || decim > CHZ_MAX_DECIM || ntaps > CHZ_MAX_TAPS || nchan > CHZ_MAX_CHANNELS) return MFB_ERR_UNSUPPORTED;
-        if (interp < 1 || interp > CHZR_MAX_INTERP) return MFB_ERR_UNSUPPORTED;
-        if (interp >= decim || ntaps < interp || !chzr_coprime(interp, decim)) return MFB_ERR_ARG;
-        return MFB_OK;
-    });
-    if (rc) return rc;
-    return guarded([&] { return chz_set_plan_body(c, chz_geom(kind, interp, decim, ntaps, 0), taps, freq_words, nchan, sample_format, scale); });
-}
-
-extern "C" int mfb_channelizer_set_plan(mfb_channelizer *c, int decim, const float *taps, int ntaps, const uint64_t *freq_words, int nchan,
-                                        int sample_format, float sample_scale) {
-    return chz_set_plan(c, CHZ_INTEGER, 1, decim, taps, ntaps, freq_words, nchan, sample_format, sample_scale);
-}
-
-extern "C" int mfb_channelizer_set_plan_rational(mfb_channelizer *c, int interp, int decim, const float *taps, int ntaps,
-                                                 const uint64_t *freq_words, int nchan, int sample_format, float sample_scale) {
-    return chz_set_plan(c, CHZ_RATIONAL, interp, decim, taps, ntaps, freq_words, nchan, sample_format, sample_scale);
-}
-
-static hipError_t chus_drop(mfb_channelizer *c) {
-    c->sv_L = 0;
-    c->sv_call = false;
-    hipError_t e = c->d_svpart.reset(), e2;
-    if ((e2 = c->d_svpower.reset()) != hipSuccess) e = e2;
-    if ((e2 = c->d_svfloor.reset()) != hipSuccess) e = e2;
-    if ((e2 = c->d_svmask.reset()) != hipSuccess) e = e2;
-    return e;
-}
-
-// e^{2 pi i q / M}, q < M, of chu_fft<M> (also the synthesiser's)
-static void chu_twiddles(int M, float2 *tw) {
-    for (int q = 0; q < M; ++q) {                    // rounded once from float64; the multiples of a quarter turn are exact
-        const int e = q % (M / 4), quad = q / (M / 4);
-        double re = 1.0, im = 0.0;
-        if (e) {
-            const double a = 2.0 * M_PI * (double)e / (double)M;
-            re = cos(a);
-            im = sin(a);
-        }
-        for (int i = 0; i < quad; ++i) {             // times i
-            const double t = re;
-            re = -im;
-            im = t;
-        }
-        tw[q] = make_float2((float)re, (float)im);
-    }
-}
-
-static int chu_set_plan_body(mfb_channelizer *c, int decim, const float *taps, int ntaps, const int32_t *bins, int nsel, int fmt, float scale) {
-    HIPCHK(hipSetDevice(c->device));
-    ChuPlan P;
-    memset(&P, 0, sizeof(P));
-    const int M = c->M;
-    chu_twiddles(M, P.tw);
-    for (int i = 0; i < nsel; ++i) P.col[i] = chu_column(M, bins[i]);
-    c->have_plan = false;
-    HIPCHK(chus_drop(c));                          // a survey belongs to the plan it was set under
-    HIPCHK(hipMemcpyAsync(c->d_h, taps, (size_t)ntaps * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_uplan, &P, sizeof(P), hipMemcpyHostToDevice, c->stream));
-    c->survey = chz_geom(CHZ_SURVEY, 1, decim, ntaps, M);
-    return chz_plan_commit(c, chz_geom(CHZ_UNIFORM, 1, decim, ntaps, M), nsel, 0, fmt, scale);
-}
-
-extern "C" int mfb_channelizer_set_plan_uniform(mfb_channelizer *c, int decim, const float *taps, int ntaps, const int32_t *bins, int nselected,
-                                                int sample_format, float sample_scale) {
-    float scale = 1.0f;
-    const int rc = chz_plan_check(c, true, taps, ntaps, bins, nselected, sample_format, sample_scale, &scale, [&]() -> int {
-        if (decim < 2 || decim > c->M || ntaps > CHU_MAX_TAPS || nselected > c->M) return MFB_ERR_UNSUPPORTED;
-        bool seen[CHU_MAX_BINS] = {};
-        for (int i = 0; i < nselected; ++i) {
-            if (bins[i] < 0 || bins[i] >= c->M || seen[bins[i]]) return MFB_ERR_ARG;
-            seen[bins[i]] = true;
-        }
-        return MFB_OK;
-    });
-    if (rc) return rc;
-    return guarded([&] { return chu_set_plan_body(c, decim, taps, ntaps, bins, nselected, sample_format, scale); });
-}
-
-extern "C" int mfb_channelizer_input_buffer(mfb_channelizer *c, int which, void **host, size_t *bytes) {
-    if (!c || !host || (which != 0 && which != 1)) return MFB_ERR_ARG;
-    if (!c->have_plan) return MFB_ERR_STATE;
-    return guarded([&]() {          // (also while a call is in flight: the other buffer is being filled)
-        HIPCHK(hipSetDevice(c->device));
-        if (!c->h_in[which]) HIPCHK(c->h_in[which].alloc((size_t)c->max_in * sizeof(float2), hip_host_malloc));
-        *host = c->h_in[which].get();
-        if (bytes) *bytes = (size_t)c->max_in * chz_sample_bytes(c->fmt);
-        return (int)MFB_OK;
-    });
-}
-
-extern "C" int mfb_channelizer_info(mfb_channelizer *c, int *outputs_per_workgroup, int *taps_capacity) {
-    if (!c) return MFB_ERR_ARG;
-    if (!c->have_plan) return MFB_ERR_STATE;
-    if (outputs_per_workgroup) *outputs_per_workgroup = c->plan.tile;
-    if (taps_capacity) *taps_capacity = c->max_taps;
-    return MFB_OK;
-}
-
-// ---- the launches: one function per kind of plan
-// f(tag) with tag::value the CHZ_FMT_* of the plan's sample format / the bins of a uniform handle: the kernels' template arguments
-template <class F>
-static void visit_chz_fmt(int fmt, F f) {
-    if (fmt == MFB_SAMPLES_SC16) f(std::integral_constant<int, CHZ_FMT_SC16>{});
-    else if (fmt == MFB_SAMPLES_SC8) f(std::integral_constant<int, CHZ_FMT_SC8>{});
-    else f(std::integral_constant<int, CHZ_FMT_CF32>{});
-}
-template <class F>
-static void visit_chu_bins(int M, F f) {
-    switch (M) {
-        case 8: f(std::integral_constant<int, 8>{}); break;
-        case 16: f(std::integral_constant<int, 16>{}); break;
-        case 32: f(std::integral_constant<int, 32>{}); break;
-        case 64: f(std::integral_constant<int, 64>{}); break;
-        case 128: f(std::integral_constant<int, 128>{}); break;
-        default: f(std::integral_constant<int, 256>{}); break;
-    }
-}
-
-// the call's window and the plan's D, T, scale: the fields that ChzArgs, ChzrArgs and ChuArgs share
-template <class Args>
-static Args chz_window(const mfb_channelizer *c, const ChzGeom &g, const mfb_channelizer_params *p) {
-    Args A;
-    A.in_base = p->in_base;
-    A.in_end = p->in_base + p->in_count;
-    A.out_base = p->out_base;
-    A.out_count = p->out_count;
-    A.D = g.D;
-    A.T = g.T;
-    A.out_stride = c->out_stride;
-    A.scale = c->scale;
-    return A;
-}
-
-static void chu_launch(mfb_channelizer *c, const mfb_channelizer_params *p, const void *raw) {
-    const ChzGeom &g = c->plan;
-    ChuArgs A = chz_window<ChuArgs>(c, g, p);
-    A.F = g.tile;
-    A.nsel = c->K;
-    visit_chu_bins(g.M, [&](auto m) {
-        visit_chz_fmt(c->fmt, [&](auto fmt) {
-            hipLaunchKernelGGL((k_chu<decltype(m)::value, decltype(fmt)::value>), dim3(chz_grid(g, p->out_count)), dim3(g.threads), g.lds_bytes,
-                               c->stream, A, (const ChuPlan *)c->d_uplan, raw, (const float *)c->d_h, c->d_out[p->buffer].get());
-        });
-    });
-}
-
-// the survey kernel, with or without the store, and the finishing kernel behind it
-static void chus_launch(mfb_channelizer *c, const mfb_channelizer_params *p, const void *raw, bool write) {
-    const ChzGeom &g = c->survey;
-    ChuArgs A = chz_window<ChuArgs>(c, g, p);
-    A.F = g.tile;
-    A.nsel = c->K;
-    ChusArgs V;
-    V.L = c->sv_L;
-    V.C = chus_chunk(g, c->sv_L);
-    V.M = g.M;
-    V.rank = c->sv_rank;
-    V.threshold = c->sv_thr;
-    auto launch = [&](auto wr) {
-        visit_chu_bins(g.M, [&](auto m) {
-            visit_chz_fmt(c->fmt, [&](auto fmt) {
-                hipLaunchKernelGGL((k_chus<decltype(m)::value, decltype(fmt)::value, decltype(wr)::value>), dim3(chz_grid(g, p->out_count)),
-                                   dim3(g.threads), g.lds_bytes, c->stream, A, V, (const ChuPlan *)c->d_uplan, raw, (const float *)c->d_h,
-                                   c->d_out[p->buffer].get(), c->d_svpart.get());
-            });
-        });
-    };
-    if (write) launch(std::true_type{});
-    else launch(std::false_type{});
-    hipLaunchKernelGGL(k_chus_finish, dim3((unsigned)(p->out_count / c->sv_L)), dim3(256), 0, c->stream, V, (const float *)c->d_svpart,
-                       c->d_svpower.get(), c->d_svfloor.get(), c->d_svmask.get());
-}
-
-static void chzr_launch(mfb_channelizer *c, const mfb_channelizer_params *p, const void *raw) {
-    const ChzGeom &g = c->plan;
-    ChzrArgs R = chz_window<ChzrArgs>(c, g, p);
-    R.U = g.U;
-    R.Tb = g.Tb;
-    R.L = g.L;
-    R.S = g.S;
-    R.rD = 1.0f / (float)g.D;
-    R.tap_stride = c->rtap_stride;
-    R.ncplx = c->ncplx;
-    R.nreal = c->K - c->ncplx;
-    visit_chz_fmt(c->fmt, [&](auto fmt) {
-        hipLaunchKernelGGL(k_chzr<decltype(fmt)::value>, dim3(chz_grid(g, p->out_count)), dim3(g.threads), g.lds_bytes, c->stream, R,
-                           (const ChzPlan *)c->d_plan, raw, (const float2 *)c->d_rtaps, c->d_out[p->buffer].get());
-    });
-}
-
-static void chz_launch(mfb_channelizer *c, const mfb_channelizer_params *p, const void *raw) {
-    const ChzGeom &g = c->plan;
-    ChzArgs A = chz_window<ChzArgs>(c, g, p);
-    A.L = g.L;
-    A.rD = 1.0f / (float)g.D;
-    A.tap_stride = c->max_taps;
-    A.ncplx = c->ncplx;
-    A.nreal = c->K - c->ncplx;
-    visit_chz_fmt(c->fmt, [&](auto fmt) {
-        hipLaunchKernelGGL(k_chz<decltype(fmt)::value>, dim3(chz_grid(g, p->out_count)), dim3(g.threads), g.lds_bytes, c->stream, A,
-                           (const ChzPlan *)c->d_plan, raw, (const float2 *)c->d_taps, c->d_out[p->buffer].get());
-    });
-}
-
-// kind: the plan's for a plain call, CHZ_SURVEY for a survey call, which writes the output set only if `write`
-static int chz_begin_body(mfb_channelizer *c, const mfb_channelizer_params *p, int kind, bool write = true) {
-    HIPCHK(hipSetDevice(c->device));
-    const size_t sb = chz_sample_bytes(c->fmt);
-    const void *raw = p->device_input;
-    if (p->input != MFB_CHZ_INPUT_DEVICE) {
-        const int w = p->input == MFB_CHZ_INPUT_PINNED1;
-        if (!c->d_in[w]) HIPCHK(c->d_in[w].alloc((size_t)c->max_in * sizeof(float2), hip_malloc));
-        HIPCHK(hipMemcpyAsync(c->d_in[w], c->h_in[w], (size_t)p->in_count * sb, hipMemcpyHostToDevice, c->stream));
-        raw = c->d_in[w].get();
-    }
-    c->count[p->buffer] = 0;
-    HIPCHK(hipEventRecord(c->t0, c->stream));
-    switch (kind) {
-        case CHZ_INTEGER: chz_launch(c, p, raw); break;
-        case CHZ_RATIONAL: chzr_launch(c, p, raw); break;
-        case CHZ_UNIFORM: chu_launch(c, p, raw); break;
-        default: chus_launch(c, p, raw, write); break;
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->t1, c->stream));
-    HIPCHK(hipEventRecord(c->done, c->stream));
-    c->cur = p->buffer;
-    c->count[p->buffer] = write ? p->out_count : 0;    // (0: the set was not written)
-    c->nchan[p->buffer] = c->K;
-    c->sv_call = kind == CHZ_SURVEY;
-    if (c->sv_call) {
-        c->sv_wrote = write;
-        c->sv_cells = p->out_count / c->sv_L;
-    }
-    c->busy = true;
-    return MFB_OK;
-}
-
-// what mfb_channelizer_begin refuses
-static int chz_begin_check(mfb_channelizer *c, const mfb_channelizer_params *p) {
-    if (!c || !p) return MFB_ERR_ARG;
-    if (p->in_count < 1 || p->out_count < 1 || p->in_base < 0 || p->out_base < 0 || (p->buffer != 0 && p->buffer != 1)) return MFB_ERR_ARG;
-    if (p->input != MFB_CHZ_INPUT_PINNED0 && p->input != MFB_CHZ_INPUT_PINNED1 && p->input != MFB_CHZ_INPUT_DEVICE) return MFB_ERR_ARG;
-    if (p->input == MFB_CHZ_INPUT_DEVICE && !p->device_input) return MFB_ERR_ARG;
-    if (p->in_count > CHZ_MAX_IN || p->out_count > CHZ_MAX_OUT || p->in_base >= ((int64_t)1 << 62)) return MFB_ERR_UNSUPPORTED;
-    if (p->in_count > c->max_in || p->out_count > c->max_out) return MFB_ERR_ARG;
-    if (c->busy) return MFB_ERR_STATE;
-    if (!c->have_plan) return MFB_ERR_STATE;
-    const int D = c->plan.D;
-    if (p->out_base >= (((int64_t)1 << 62) + D - 1) / D) return MFB_ERR_UNSUPPORTED;             // out_base * D < 2^62
-    if (p->input == MFB_CHZ_INPUT_DEVICE && ((uintptr_t)p->device_input & (chz_sample_bytes(c->fmt) - 1))) return MFB_ERR_ARG;
-    if (p->input != MFB_CHZ_INPUT_DEVICE && !c->h_in[p->input == MFB_CHZ_INPUT_PINNED1]) return MFB_ERR_STATE;
-    // every input an output reads, apart from the positions below 0, lies inside the call's input
-    int64_t first = 0, last = 0;
-    chz_input_span(c->plan, p->out_base, p->out_count, &first, &last);
-    if ((first > 0 ? first : 0) < p->in_base || last >= p->in_base + p->in_count) return MFB_ERR_ARG;
-    return MFB_OK;
-}
-
-extern "C" int mfb_channelizer_begin(mfb_channelizer *c, const mfb_channelizer_params *p) {
-    const int rc = chz_begin_check(c, p);
-    if (rc) return rc;
-    return guarded([&] { return chz_begin_body(c, p, c->plan.kind); });
-}
-
-// the output set of the call in flight to the host, on the stream
-static hipError_t chz_copy_out(mfb_channelizer *c, float *out_c64) {
-    const int b = c->cur;
-    const size_t row = (size_t)c->count[b] * sizeof(float2);
-    return hipMemcpy2DAsync(out_c64, row, c->d_out[b].get(), (size_t)c->out_stride * sizeof(float2), row, (size_t)c->nchan[b], hipMemcpyDeviceToHost,
-                            c->stream);
-}
-
-extern "C" int mfb_channelizer_end(mfb_channelizer *c, float *out_c64) {
-    if (!c) return MFB_ERR_ARG;
-    if (!c->busy || c->sv_call) return MFB_ERR_STATE;          // (a survey call ends with mfb_channelizer_survey_end)
-    HIPCHK(hipSetDevice(c->device));
-    if (out_c64) {
-        HIPCHK(chz_copy_out(c, out_c64));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    } else {
-        HIPCHK(hipEventSynchronize(c->done));
-    }
-    c->busy = false;
-    return MFB_OK;
-}
-
-extern "C" int mfb_channelizer_device_output(mfb_channelizer *c, int buffer, int channel, const void **dev_c64, int64_t *nsamples) {
-    if (!c || !dev_c64 || (buffer != 0 && buffer != 1) || channel < 0) return MFB_ERR_ARG;
-    if ((c->busy && c->cur == buffer) || !c->count[buffer] || channel >= c->nchan[buffer]) return MFB_ERR_STATE;
-    *dev_c64 = c->d_out[buffer].get() + (size_t)channel * c->out_stride;
-    if (nsamples) *nsamples = c->count[buffer];
-    return MFB_OK;
-}
-
-extern "C" int mfb_channelizer_elapsed_ms(mfb_channelizer *c, float *ms) {
-    if (!c || !ms) return MFB_ERR_ARG;
-    if (c->busy || !(c->count[0] || c->count[1] || c->sv_call)) return MFB_ERR_STATE;
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipEventElapsedTime(ms, c->t0, c->t1));
-    return MFB_OK;
-}
-
-// ---- the survey of a uniform plan (channelize_survey_kernels.hpp)
-static int chus_set_body(mfb_channelizer *c, int cell_frames, int rank, float threshold) {
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(chus_drop(c));
-    if (!cell_frames) return MFB_OK;
-    const ChusTables t = chus_tables(c->survey, cell_frames, c->max_out);
-    HIPCHK(c->d_svpart.alloc((size_t)t.chunks * c->M * sizeof(float), hip_malloc));
-    HIPCHK(c->d_svpower.alloc((size_t)t.cells * c->M * sizeof(float), hip_malloc));
-    HIPCHK(c->d_svfloor.alloc((size_t)t.cells * sizeof(float), hip_malloc));
-    HIPCHK(c->d_svmask.alloc((size_t)t.cells * t.words * sizeof(uint32_t), hip_malloc));
-    c->sv_rank = rank;
-    c->sv_thr = threshold;
-    c->sv_L = cell_frames;
-    return MFB_OK;
-}
-
-extern "C" int mfb_channelizer_set_survey(mfb_channelizer *c, int cell_frames, int rank, float threshold) {
-    if (!c) return MFB_ERR_ARG;
-    if (!c->M || !c->have_plan || c->busy) return MFB_ERR_STATE;
-    if (cell_frames) {
-        if (cell_frames < (1 << CHUS_MIN_LOG2) || cell_frames > (1 << CHUS_MAX_LOG2) || (cell_frames & (cell_frames - 1))) return MFB_ERR_ARG;
-        if (rank < 0 || rank >= c->M || !std::isfinite(threshold) || threshold < 1.0f) return MFB_ERR_ARG;
-        if (cell_frames > c->max_out) return MFB_ERR_ARG;      // no call of this handle holds one cell
-    }
-    const int rc = guarded([&] { return chus_set_body(c, cell_frames, rank, threshold); });
-    if (rc) (void)chus_drop(c);
-    return rc;
-}
-
-extern "C" int mfb_channelizer_survey_info(mfb_channelizer *c, int *cell_frames, int *frames_per_workgroup, int *rank, float *threshold) {
-    if (!c) return MFB_ERR_ARG;
-    if (!c->M || !c->have_plan) return MFB_ERR_STATE;
-    if (cell_frames) *cell_frames = c->sv_L;
-    if (frames_per_workgroup) *frames_per_workgroup = c->survey.tile;
-    if (rank) *rank = c->sv_rank;
-    if (threshold) *threshold = c->sv_thr;
-    return MFB_OK;
-}
-
-extern "C" int mfb_channelizer_survey_begin(mfb_channelizer *c, const mfb_channelizer_params *p, int write_outputs) {
-    if (!c || !p) return MFB_ERR_ARG;
-    if (!c->M) return MFB_ERR_STATE;
-    const int rc = chz_begin_check(c, p);
-    if (rc) return rc;
-    if (!c->sv_L) return MFB_ERR_STATE;
-    if (p->out_base % c->sv_L || p->out_count % c->sv_L) return MFB_ERR_ARG;
-    if ((int64_t)c->M * p->out_count > CHU_MAX_SET || (int64_t)c->M * (p->out_count / c->sv_L) > CHUS_MAX_TABLE) return MFB_ERR_UNSUPPORTED;
-    return guarded([&] { return chz_begin_body(c, p, CHZ_SURVEY, write_outputs != 0); });
-}
-
-extern "C" int mfb_channelizer_survey_end(mfb_channelizer *c, float *out_c64, float *power, float *floor, uint32_t *mask) {
-    if (!c) return MFB_ERR_ARG;
-    if (!c->busy || !c->sv_call) return MFB_ERR_STATE;         // (a plain call ends with mfb_channelizer_end)
-    if (out_c64 && !c->sv_wrote) return MFB_ERR_ARG;           // the call stays in flight
-    HIPCHK(hipSetDevice(c->device));
-    const size_t cells = (size_t)c->sv_cells;
-    if (out_c64) HIPCHK(chz_copy_out(c, out_c64));
-    if (power) HIPCHK(hipMemcpyAsync(power, c->d_svpower, cells * c->M * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (floor) HIPCHK(hipMemcpyAsync(floor, c->d_svfloor, cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (mask) HIPCHK(hipMemcpyAsync(mask, c->d_svmask, cells * ((c->M + 31) / 32) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    if (out_c64 || power || floor || mask) HIPCHK(hipStreamSynchronize(c->stream));
-    else HIPCHK(hipEventSynchronize(c->done));
-    c->busy = false;
-    return MFB_OK;
-}
-
-// ---- the synthesiser (synthesize_uniform_kernels.hpp; channelize_plan.hpp: its limits and the CHZ_SYNTHESIS geometry) --------------
-static_assert(sizeof(ChsyPlace) == sizeof(mfb_synthesizer_placement) && sizeof(ChsyPlace) == 32, "the placements are copied as they come");
-struct mfb_synthesizer {
-    Stream stream;             // (first: it goes last)
-    int device = 0, M = 0, max_taps = 0, max_out = 0, max_source = 0, max_frames = 0;
-    Event done, t0, t1;
-    HostBuf<ChsyCall> h_call;  // page-locked staging of a call's table and its sorted placements
-    HostBuf<ChsyPlace> h_place;
-    DevBuf<ChsyCall> d_call;
-    DevBuf<ChsyPlace> d_place;
-    DevBuf<float> d_h;
-    DevBuf<ChuPlan> d_plan;    // the twiddle table of chu_fft<M>
-    DevBuf<float2> d_out[2];
-    DevBuf<float2> d_src;      // a host source's copy, on demand
-    const float2 *src = nullptr;        // d_src, or the caller's device pointer
-    int64_t src_count = 0;
-    bool have_plan = false, busy = false, ran = false;
-    ChzGeom plan = {};         // CHZ_SYNTHESIS
-    int cur = 0;               // the output set of the call in flight
-    int count[2] = {0, 0};     // 0: never written
-};
-
-extern "C" int mfb_synthesizer_destroy(mfb_synthesizer *s) {
-    if (!s) return MFB_ERR_ARG;
-    (void)hipSetDevice(s->device);
-    if (s->stream) (void)hipStreamSynchronize(s->stream);
-    delete s;
-    return MFB_OK;
-}
-
-struct ChsyDestroy {
-    void operator()(mfb_synthesizer *s) const { (void)mfb_synthesizer_destroy(s); }
-};
-static int chsy_create_impl(mfb_synthesizer *s) {
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipStreamCreateWithFlags(out(s->stream), hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(out(s->done), hipEventDisableTiming));
-    HIPCHK(hipEventCreate(out(s->t0)));
-    HIPCHK(hipEventCreate(out(s->t1)));
-    HIPCHK(s->h_call.alloc(sizeof(ChsyCall), hip_host_malloc));
-    HIPCHK(s->h_place.alloc((size_t)s->max_frames * sizeof(ChsyPlace), hip_host_malloc));
-    HIPCHK(s->d_call.alloc(sizeof(ChsyCall), hip_malloc));
-    HIPCHK(s->d_place.alloc((size_t)s->max_frames * sizeof(ChsyPlace), hip_malloc));
-    HIPCHK(s->d_h.alloc((size_t)s->max_taps * sizeof(float), hip_malloc));
-    HIPCHK(s->d_plan.alloc(sizeof(ChuPlan), hip_malloc));
-    for (int b = 0; b < 2; ++b) HIPCHK(s->d_out[b].alloc((size_t)s->max_out * sizeof(float2), hip_malloc));
-    ChuPlan P;
-    memset(&P, 0, sizeof(P));
-    chu_twiddles(s->M, P.tw);
-    HIPCHK(hipMemcpy(s->d_plan, &P, sizeof(P), hipMemcpyHostToDevice));
-    return MFB_OK;
-}
-
-extern "C" int mfb_synthesizer_create(mfb_synthesizer **out, int device, int nbins, int max_taps, int max_out, int max_source, int max_frames) {
-    if (!out) return MFB_ERR_ARG;
-    *out = nullptr;
-    if (nbins < 1 || max_taps < 1 || max_out < 1 || max_source < 1 || max_frames < 1) return MFB_ERR_ARG;
-    if (!chu_bins_ok(nbins) || max_taps > CHU_MAX_TAPS || max_out > CHSY_MAX_OUT || max_source > CHSY_MAX_SOURCE || max_frames > CHSY_MAX_FRAMES)
-        return MFB_ERR_UNSUPPORTED;
-    int rc = device_ok(device, SYNC_MAX_DEVICES);
-    if (rc) return rc;
-    return guarded([&]() {
-        std::unique_ptr<mfb_synthesizer, ChsyDestroy> s(new mfb_synthesizer());
-        s->device = device;
-        s->M = nbins;
-        s->max_taps = max_taps;
-        s->max_out = max_out;
-        s->max_source = max_source;
-        s->max_frames = max_frames;
-        const int rc2 = chsy_create_impl(s.get());
-        if (rc2) return rc2;
-        *out = s.release();
-        return (int)MFB_OK;
-    });
-}
-
-static int chsy_set_plan_body(mfb_synthesizer *s, const ChzGeom &g, const float *taps) {
-    HIPCHK(hipSetDevice(s->device));
-    s->have_plan = false;
-    HIPCHK(hipMemcpyAsync(s->d_h, taps, (size_t)g.T * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));       // the taps are the caller's
-    s->plan = g;
-    s->count[0] = s->count[1] = 0;                 // what the sets hold belongs to the plan before
-    s->have_plan = true;
-    return MFB_OK;
-}
-
-extern "C" int mfb_synthesizer_set_plan(mfb_synthesizer *s, int interp, const float *taps, int ntaps) {
-    if (!s || !taps || ntaps < 1) return MFB_ERR_ARG;
-    if (interp < 2 || interp > s->M || ntaps > CHU_MAX_TAPS) return MFB_ERR_UNSUPPORTED;
-    if (ntaps > s->max_taps || !chz_taps_finite(taps, ntaps)) return MFB_ERR_ARG;
-    const ChzGeom g = chz_geom(CHZ_SYNTHESIS, interp, 1, ntaps, s->M);
-    if (!g.tile) return MFB_ERR_UNSUPPORTED;       // not even one frame's tile fits the LDS budget
-    if (s->busy) return MFB_ERR_STATE;
-    return guarded([&] { return chsy_set_plan_body(s, g, taps); });
-}
-
-extern "C" int mfb_synthesizer_set_source(mfb_synthesizer *s, const void *samples_c64, int64_t nsamples, int on_device) {
-    if (!s || !samples_c64 || nsamples < 1) return MFB_ERR_ARG;
-    if (!on_device && nsamples > s->max_source) return MFB_ERR_ARG;
-    if (on_device && ((uintptr_t)samples_c64 & 7)) return MFB_ERR_ARG;
-    if (s->busy) return MFB_ERR_STATE;
-    return guarded([&]() {
-        HIPCHK(hipSetDevice(s->device));
-        s->src = nullptr;
-        s->src_count = 0;
-        if (on_device) {
-            s->src = (const float2 *)samples_c64;
-        } else {
-            if (!s->d_src) HIPCHK(s->d_src.alloc((size_t)s->max_source * sizeof(float2), hip_malloc));
-            HIPCHK(hipMemcpy(s->d_src, samples_c64, (size_t)nsamples * sizeof(float2), hipMemcpyHostToDevice));
-            s->src = s->d_src;
-        }
-        s->src_count = nsamples;
-        return (int)MFB_OK;
-    });
-}
-
-// The call's placements into the staging, sorted by (bin, start), with the table of the occupied bins; false: two of one bin overlap.
-static bool chsy_sort_placements(mfb_synthesizer *s, const mfb_synthesizer_placement *pl, int n) {
-    std::vector<int> order((size_t)n);
-    for (int i = 0; i < n; ++i) order[(size_t)i] = i;
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return pl[a].bin != pl[b].bin ? pl[a].bin < pl[b].bin : pl[a].start < pl[b].start; });
-    ChsyCall &C = *s->h_call.get();
-    ChsyPlace *dst = s->h_place.get();
-    C.nocc = 0;
-    for (int i = 0; i < n; ++i) {
-        const mfb_synthesizer_placement &p = pl[order[(size_t)i]];
-        if (i && pl[order[(size_t)i - 1]].bin == p.bin) {
-            const mfb_synthesizer_placement &before = pl[order[(size_t)i - 1]];
-            if (p.start < before.start + before.length) return false;
-        } else {
-            C.bin[C.nocc] = p.bin;
-            C.first[C.nocc++] = i;
-        }
-        dst[i].start = p.start;
-        dst[i].src = p.src;
-        dst[i].length = p.length;
-        dst[i].bin = p.bin;
-        dst[i].gain = p.gain;
-        dst[i].reserved = 0;
-    }
-    C.first[C.nocc] = n;
-    return true;
-}
-
-static int chsy_begin_body(mfb_synthesizer *s, const mfb_synthesizer_params *p, const mfb_synthesizer_placement *pl, int n) {
-    if (!chsy_sort_placements(s, pl, n)) return MFB_ERR_ARG;
-    HIPCHK(hipSetDevice(s->device));
-    const ChzGeom &g = s->plan;
-    HIPCHK(hipMemcpyAsync(s->d_call, s->h_call, sizeof(ChsyCall), hipMemcpyHostToDevice, s->stream));
-    if (n) HIPCHK(hipMemcpyAsync(s->d_place, s->h_place, (size_t)n * sizeof(ChsyPlace), hipMemcpyHostToDevice, s->stream));
-    ChsyArgs A;
-    A.out_base = p->out_base;
-    A.q_first = p->out_base / g.U;
-    A.out_count = p->out_count;
-    A.I = g.U;
-    A.T = g.T;
-    A.J = g.Tb;
-    A.F = g.tile;
-    A.R = chsy_rows(g.U, g.T, g.tile);
-    s->count[p->buffer] = 0;
-    HIPCHK(hipEventRecord(s->t0, s->stream));
-    visit_chu_bins(g.M, [&](auto m) {
-        hipLaunchKernelGGL((k_chsy<decltype(m)::value>), dim3(chsy_grid(g, p->out_base, p->out_count)), dim3(g.threads), g.lds_bytes, s->stream, A,
-                           (const ChuPlan *)s->d_plan, (const ChsyCall *)s->d_call, (const ChsyPlace *)s->d_place, s->src, (const float *)s->d_h,
-                           s->d_out[p->buffer].get());
-    });
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(s->t1, s->stream));
-    HIPCHK(hipEventRecord(s->done, s->stream));
-    s->cur = p->buffer;
-    s->count[p->buffer] = p->out_count;
-    s->busy = true;
-    return MFB_OK;
-}
-
-extern "C" int mfb_synthesizer_begin(mfb_synthesizer *s, const mfb_synthesizer_params *p, const mfb_synthesizer_placement *pl, int n) {
-    if (!s || !p || n < 0 || (n > 0 && !pl)) return MFB_ERR_ARG;
-    if (p->out_count < 1 || p->out_base < 0 || (p->buffer != 0 && p->buffer != 1)) return MFB_ERR_ARG;
-    if (p->out_count > CHSY_MAX_OUT || p->out_base >= ((int64_t)1 << 62) || n > CHSY_MAX_FRAMES) return MFB_ERR_UNSUPPORTED;
-    if (p->out_count > s->max_out || n > s->max_frames) return MFB_ERR_ARG;
-    if (s->busy || !s->have_plan || !s->src) return MFB_ERR_STATE;
-    for (int i = 0; i < n; ++i) {
-        const mfb_synthesizer_placement &q = pl[i];
-        if (q.length < 1 || q.start < 0 || q.bin < 0 || q.bin >= s->M || !std::isfinite(q.gain)) return MFB_ERR_ARG;
-        if (q.start >= ((int64_t)1 << 62)) return MFB_ERR_UNSUPPORTED;
-        if (q.src < 0 || q.src > s->src_count - q.length) return MFB_ERR_ARG;
-    }
-    return guarded([&] { return chsy_begin_body(s, p, pl, n); });
-}
-
-extern "C" int mfb_synthesizer_end(mfb_synthesizer *s, float *out_c64) {
-    if (!s) return MFB_ERR_ARG;
-    if (!s->busy) return MFB_ERR_STATE;
-    HIPCHK(hipSetDevice(s->device));
-    if (out_c64) {
-        HIPCHK(hipMemcpyAsync(out_c64, s->d_out[s->cur], (size_t)s->count[s->cur] * sizeof(float2), hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(hipStreamSynchronize(s->stream));
-    } else {
-        HIPCHK(hipEventSynchronize(s->done));
-    }
-    s->busy = false;
-    s->ran = true;
-    return MFB_OK;
-}
-
-extern "C" int mfb_synthesizer_device_output(mfb_synthesizer *s, int buffer, const void **dev_c64, int64_t *nsamples) {
-    if (!s || !dev_c64 || (buffer != 0 && buffer != 1)) return MFB_ERR_ARG;
-    if ((s->busy && s->cur == buffer) || !s->count[buffer]) return MFB_ERR_STATE;
-    *dev_c64 = s->d_out[buffer].get();
-    if (nsamples) *nsamples = s->count[buffer];
-    return MFB_OK;
-}
-
-extern "C" int mfb_synthesizer_info(mfb_synthesizer *s, int *frames_per_workgroup, int *rows) {
-    if (!s) return MFB_ERR_ARG;
-    if (!s->have_plan) return MFB_ERR_STATE;
-    if (frames_per_workgroup) *frames_per_workgroup = s->plan.tile;
-    if (rows) *rows = chsy_rows(s->plan.U, s->plan.T, s->plan.tile);
-    return MFB_OK;
-}
-
-extern "C" int mfb_synthesizer_elapsed_ms(mfb_synthesizer *s, float *ms) {
-    if (!s || !ms) return MFB_ERR_ARG;
-    if (s->busy || !s->ran) return MFB_ERR_STATE;
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipEventElapsedTime(ms, s->t0, s->t1));
-    return MFB_OK;
-}
-
-// ---- packed sync correlation (sync_kernels.hpp, second half)-------------------------------------------------------------
-// One page-locked buffer per device, grown on demand: callers that produce their packed bit streams straight into it
-// (mfb_sync_pinned_buffer) get a true asynchronous host-to-device copy; any other host pointer works too (the runtime stages it).
-static std::mutex g_pin_mu;
-static HostBuf<uint8_t> *const g_pin = new HostBuf<uint8_t>[SYNC_MAX_DEVICES];     // never deleted: they live until the process exits, as before
-static size_t g_pin_cap[SYNC_MAX_DEVICES];
-
-extern "C" int mfb_sync_pinned_buffer(int device, size_t bytes, void **host) {
-    if (!host || bytes < 1) return MFB_ERR_ARG;
-    int rc = device_ok(device, SYNC_MAX_DEVICES);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(g_pin_mu);
-    HIPCHK(reserve(g_pin[device], g_pin_cap[device], bytes, bytes, hip_host_malloc));
-    *host = g_pin[device];
-    return MFB_OK;
-}
-
-extern "C" int mfb_sync_find_packed(int device, const uint8_t *packed, int B, int L, int row_bytes, const int8_t *tmpl, int T,
-                                    int threshold, int max_total, int32_t *hit_idx, int32_t *hit_score, int32_t *counts,
-                                    int32_t *total_hits, float *device_ms) {
-    if (!packed || !tmpl || !hit_idx || !hit_score || !counts || !total_hits || B < 1 || L < 1 || T < 1 || T > 64 * SYNCP_MAXK ||
-        max_total < 1 || row_bytes < (L + 7) / 8)
-        return MFB_ERR_ARG;
-    const int K = (T + 63) / 64;
-    std::vector<unsigned long long> masks(2 * (size_t)K, 0ull);
-    for (int t = 0; t < T; ++t) {
-        if (tmpl[t] == 1) masks[t / 64] |= 1ull << (t % 64);
-        else if (tmpl[t] == -1) masks[K + t / 64] |= 1ull << (t % 64);
-        else if (tmpl[t] != 0) return MFB_ERR_UNSUPPORTED;       // the packed form takes taps in {-1, 0, +1} only
-    }
-    int rc = device_ok(device, SYNC_MAX_DEVICES);
-    if (rc) return rc;
-    WsLease lease{device, ws_acquire(device)};
-    if (!lease.w) return MFB_ERR_HIP;
-    SyncWs &w = *lease.w;
-    const int nseg = (L + T - 1 + SYNCP_SEG - 1) / SYNCP_SEG;
-    const size_t nbytes = (size_t)B * row_bytes;
-    if ((rc = ws_reserve(&w.bits, &w.cap_bits, nbytes))) return rc;
-    if ((rc = ws_reserve(&w.tmpl, &w.cap_tmpl, masks.size() * sizeof(unsigned long long)))) return rc;
-    if ((rc = ws_reserve(&w.seg, &w.cap_seg, ((size_t)2 * B * nseg + 2 * (size_t)B + 1) * sizeof(int)))) return rc;
-    if ((rc = ws_reserve(&w.hits, &w.cap_hits, (size_t)2 * max_total * sizeof(int32_t)))) return rc;
-    if ((rc = ws_reserve(&w.d_stage, &w.cap_dstage, (size_t)B * nseg * SYNCP_THREADS))) return rc;       // hits per thread, one byte
-    int *segcnt = w.seg, *segoff = segcnt + (size_t)B * nseg, *d_counts = segoff + (size_t)B * nseg, *d_streamoff = d_counts + B;
-    int32_t *d_idx = w.hits, *d_sc = w.hits + max_total;
-    uint8_t *d_tcnt = w.d_stage;
-    Event e0, e1;
-    if (device_ms) {
-        HIPCHK(hipEventCreate(out(e0)));
-        HIPCHK(hipEventCreate(out(e1)));
-    }
-    HIPCHK(hipMemcpyAsync(w.bits, packed, nbytes, hipMemcpyHostToDevice, w.stream));
-    HIPCHK(hipMemcpyAsync(w.tmpl, masks.data(), masks.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, w.stream));
-    if (e0) HIPCHK(hipEventRecord(e0, w.stream));
-    const unsigned long long *d_masks = (const unsigned long long *)w.tmpl.get();
-#define SYNCP_LAUNCH(WRITE_, KT_)                                                                                                        \
-    hipLaunchKernelGGL((k_sync_packed<WRITE_, KT_>), dim3(nseg, B), dim3(SYNCP_THREADS), 0, w.stream, (const uint8_t *)w.bits, row_bytes, L, T, \
-                       K, d_masks, threshold, nseg, segcnt, d_tcnt, (const int *)segoff, (const int *)d_streamoff, max_total, d_idx, d_sc)
-    if (K == 1) SYNCP_LAUNCH(false, 1);
-    else if (K == 2) SYNCP_LAUNCH(false, 2);
-    else SYNCP_LAUNCH(false, 0);
-    hipLaunchKernelGGL(k_sync_scan, dim3((B + 63) / 64), dim3(64), 0, w.stream, (const int *)segcnt, segoff, d_counts, B, nseg);
-    hipLaunchKernelGGL(k_sync_stream_scan, dim3(1), dim3(256), 0, w.stream, (const int *)d_counts, d_streamoff, B);
-    if (K == 1) SYNCP_LAUNCH(true, 1);
-    else if (K == 2) SYNCP_LAUNCH(true, 2);
-    else SYNCP_LAUNCH(true, 0);
-#undef SYNCP_LAUNCH
-    HIPCHK(hipGetLastError());
-    if (e1) HIPCHK(hipEventRecord(e1, w.stream));
-    // counts and the grand total first, then exactly the hits
-    std::vector<int> hc((size_t)2 * B + 1);
-    HIPCHK(hipMemcpyAsync(hc.data(), d_counts, hc.size() * sizeof(int), hipMemcpyDeviceToHost, w.stream));
-    HIPCHK(hipStreamSynchronize(w.stream));
-    memcpy(counts, hc.data(), (size_t)B * sizeof(int));
-    const int total = hc[(size_t)2 * B];
-    *total_hits = total;
-    const int n = total < max_total ? total : max_total;
-    if (n > 0) {
-        HIPCHK(hipMemcpyAsync(hit_idx, d_idx, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, w.stream));
-        HIPCHK(hipMemcpyAsync(hit_score, d_sc, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, w.stream));
-        HIPCHK(hipStreamSynchronize(w.stream));
-    }
-    if (device_ms) HIPCHK(hipEventElapsedTime(device_ms, e0, e1));
-    return MFB_OK;
-}
+// ---- the side handles (stage_handle.hpp: what they share).  Each part is included here, once, where its code stood.
+#include "sync_api.hpp"
+#include "combine_api.hpp"
+#include "mod_api.hpp"
+#include "channel_api.hpp"
+#include "channelize_api.hpp"
+#include "synthesize_uniform_api.hpp"
 
 // ---- N4: bit-stream alignment cross-correlation (reference lib/customXCorr.py:5-18) -----------------
 // out = ifft( fft(a, N) * conj(fft(b, N)) ) with N the handle's block length: a and b are real

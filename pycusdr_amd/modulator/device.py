@@ -4,6 +4,7 @@ import ctypes as C
 import numpy as np
 
 from .. import _lib
+from .._handle import Handle
 
 MAX_FRAME_BITS, MAX_FRAMES, MAX_BITS, MAX_SAMPLES = 1 << 17, 4096, 1 << 22, 1 << 24
 
@@ -24,7 +25,9 @@ class DeviceBatch:
         return int(self.sample_off[f + 1] - self.sample_off[f])
 
 
-class DeviceModulator:
+class DeviceModulator(Handle):
+    PREFIX = 'mfb_modulator'
+
     def __init__(self, max_bits, max_samples, device=0):
         self.lib = _lib.load()
         self.h = C.c_void_p()
@@ -32,27 +35,16 @@ class DeviceModulator:
         _lib.check(self.lib.mfb_modulator_create(C.byref(self.h), device, self.max_bits, self.max_samples), 'mfb_modulator_create')
         self._B = 0
 
-    def close(self):
-        if self.h:
-            self.lib.mfb_modulator_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def set_lut(self, kind, lut_rad):
         lut = np.ascontiguousarray(lut_rad, dtype=np.float64)
-        _lib.check(self.lib.mfb_modulator_set_lut(self.h, kind, lut.ctypes.data, lut.shape[0], lut.shape[1]), 'mfb_modulator_set_lut')
+        self._call('mfb_modulator_set_lut', kind, lut.ctypes.data, lut.shape[0], lut.shape[1])
 
     def set_pad(self, noise, pad_len, min_len):
         if noise is None:
-            _lib.check(self.lib.mfb_modulator_set_pad(self.h, None, 0, pad_len, min_len), 'mfb_modulator_set_pad')
+            self._call('mfb_modulator_set_pad', None, 0, pad_len, min_len)
             return
         noise = np.ascontiguousarray(noise, dtype=np.complex64)
-        _lib.check(self.lib.mfb_modulator_set_pad(self.h, noise.ctypes.data, len(noise), pad_len, min_len), 'mfb_modulator_set_pad')
+        self._call('mfb_modulator_set_pad', noise.ctypes.data, len(noise), pad_len, min_len)
 
     @staticmethod
     def pack(frames):
@@ -71,8 +63,7 @@ class DeviceModulator:
         d = None if dphi_rad is None else np.ascontiguousarray(dphi_rad, dtype=np.float64)
         if d is not None and len(d) != B:
             raise ValueError('one phase increment per frame')
-        _lib.check(self.lib.mfb_modulator_begin(self.h, bits.ctypes.data if len(bits) else None, off.ctypes.data,
-                                                None if d is None else d.ctypes.data, B), 'mfb_modulator_begin')
+        self._call('mfb_modulator_begin', bits.ctypes.data if len(bits) else None, off.ctypes.data, None if d is None else d.ctypes.data, B)
         self._B = B
 
     def end(self, copy=True, pinned=False):
@@ -80,20 +71,20 @@ class DeviceModulator:
         of the handle's page-locked buffer (valid until the next call) instead of a fresh array."""
         off = np.zeros(self._B + 1, dtype=np.int64)
         if not copy:
-            _lib.check(self.lib.mfb_modulator_end(self.h, None, off.ctypes.data), 'mfb_modulator_end')
+            self._call('mfb_modulator_end', None, off.ctypes.data)
             ptr, n = C.c_void_p(), C.c_int64()
-            _lib.check(self.lib.mfb_modulator_device_output(self.h, C.byref(ptr), C.byref(n)), 'mfb_modulator_device_output')
+            self._call('mfb_modulator_device_output', C.byref(ptr), C.byref(n))
             return DeviceBatch(ptr.value, off)
         host = C.POINTER(C.c_float)()
-        _lib.check(self.lib.mfb_modulator_host_buffer(self.h, C.byref(host)), 'mfb_modulator_host_buffer')
-        _lib.check(self.lib.mfb_modulator_end(self.h, host, off.ctypes.data), 'mfb_modulator_end')
+        self._call('mfb_modulator_host_buffer', C.byref(host))
+        self._call('mfb_modulator_end', host, off.ctypes.data)
         view = np.ctypeslib.as_array(host, shape=(2 * self.max_samples,))[:2 * int(off[-1])].view(np.complex64)
         return (view if pinned else view.copy()), off
 
     def phase_words(self):
         """The test seam mfb_debug_mod_phase: the uint64 phase word of every sample of the batch ended last."""
         ptr, n = C.c_void_p(), C.c_int64()
-        _lib.check(self.lib.mfb_modulator_device_output(self.h, C.byref(ptr), C.byref(n)), 'mfb_modulator_device_output')
+        self._call('mfb_modulator_device_output', C.byref(ptr), C.byref(n))
         words = np.zeros(n.value, dtype=np.uint64)
-        _lib.check(self.lib.mfb_debug_mod_phase(self.h, words.ctypes.data, n.value), 'mfb_debug_mod_phase')
+        self._call('mfb_debug_mod_phase', words.ctypes.data, n.value)
         return words

@@ -37,8 +37,9 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._handle import OutputStage
 from .modulator import phase
-from .modulator.device import DeviceBatch
+from .modulator.device import DeviceBatch         # noqa: F401  (a source ``set_source`` takes: callers name it from here)
 
 _U = np.uint64
 BINS, MAX_TAPS, MAX_FRAMES, MAX_OUT, MAX_SOURCE = (8, 16, 32, 64, 128, 256), 4096, 4096, 1 << 24, 1 << 26
@@ -120,9 +121,10 @@ def pack_placements(placements):
     return a
 
 
-class UniformSynthesizer:
+class UniformSynthesizer(OutputStage):
     """Streams onto a raster: bin b of ``nbins = M`` sits at ``b * fs / M`` of the wide stream of rate ``fs``; a narrow stream runs
     at ``fs / interp``.  The module docstring has the definition."""
+    PREFIX = 'mfb_synthesizer'
 
     def __init__(self, fs, nbins, interp, taps, backend='hip', device=0, max_out=1 << 20, max_source=1 << 20, max_frames=4096):
         if backend not in ('hip', 'host'):
@@ -142,19 +144,11 @@ class UniformSynthesizer:
             self.lib = _lib.load()
             _lib.check(self.lib.mfb_synthesizer_create(C.byref(self.h), device, self.nbins, self.T, self.max_out, self.max_source,
                                                        self.max_frames), 'mfb_synthesizer_create')
-            _lib.check(self.lib.mfb_synthesizer_set_plan(self.h, self.interp, self.taps.ctypes.data, self.T), 'mfb_synthesizer_set_plan')
+            self._call('mfb_synthesizer_set_plan', self.interp, self.taps.ctypes.data, self.T)
 
     def close(self):
-        if self.h:
-            self.lib.mfb_synthesizer_destroy(self.h)
-            self.h = C.c_void_p()
+        super().close()
         self._keep = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @property
     def freqs_hz(self):
@@ -166,31 +160,20 @@ class UniformSynthesizer:
     def info(self):
         """(frames per workgroup F, the F + ceil(T / I) - 1 frames it transforms) of the plan in force (hip)."""
         a, b = C.c_int(), C.c_int()
-        _lib.check(self.lib.mfb_synthesizer_info(self.h, C.byref(a), C.byref(b)), 'mfb_synthesizer_info')
+        self._call('mfb_synthesizer_info', C.byref(a), C.byref(b))
         return a.value, b.value
 
     def elapsed_ms(self):
         ms = C.c_float()
-        _lib.check(self.lib.mfb_synthesizer_elapsed_ms(self.h, C.byref(ms)), 'mfb_synthesizer_elapsed_ms')
+        self._call('mfb_synthesizer_elapsed_ms', C.byref(ms))
         return ms.value
 
     def set_source(self, samples):
         """What the placements read: complex samples (copied in), a ``DeviceBatch`` of the device modulator, or ``(device_ptr,
         count)`` of complex64 -- both used in place, hip back end only, valid as long as their owner keeps them."""
-        if isinstance(samples, (DeviceBatch, tuple)):
-            if self.backend != 'hip':
-                raise ValueError("device memory is a source of the 'hip' back end")
-            ptr, n = (samples.ptr, samples.total) if isinstance(samples, DeviceBatch) else (int(samples[0]), int(samples[1]))
-            _lib.check(self.lib.mfb_synthesizer_set_source(self.h, C.c_void_p(ptr), n, 1), 'mfb_synthesizer_set_source')
-            self._keep, self.source_len = samples, n
-            return
-        src = np.ascontiguousarray(samples, dtype=np.complex64).reshape(-1)
-        if not 1 <= len(src) <= self.max_source:
-            raise ValueError(f'1 <= source samples <= max_source = {self.max_source}')
-        if self.backend == 'hip':
-            _lib.check(self.lib.mfb_synthesizer_set_source(self.h, src.ctypes.data, len(src), 0), 'mfb_synthesizer_set_source')
-        self._src = src.copy()
-        self.source_len = len(src)
+        src = self._set_source(samples)
+        if src is not None:                                   # (on either back end: ``model`` reads them)
+            self._src = src.copy()
 
     def placement(self, bin, start, src, length, gain=1.0):
         """A descriptor; ``bin``: -M/2 <= bin < M, taken modulo M."""
@@ -234,25 +217,15 @@ class UniformSynthesizer:
         self._buffer = (self._buffer ^ 1) if buffer is None else int(buffer)
         P = _lib.SynthesizerParams(out_base=out_base, out_count=out_count, buffer=self._buffer)
         pl = pack_placements(placements)
-        _lib.check(self.lib.mfb_synthesizer_begin(self.h, C.byref(P), pl.ctypes.data if len(pl) else None, len(pl)), 'mfb_synthesizer_begin')
+        self._call('mfb_synthesizer_begin', C.byref(P), pl.ctypes.data if len(pl) else None, len(pl))
         self._count = out_count
 
     def end(self, copy=True):
-        if self.backend == 'host':
-            out, self._host = self._host, None
-            return out
-        if copy:
-            out = np.empty(self._count, dtype=np.complex64)
-            _lib.check(self.lib.mfb_synthesizer_end(self.h, out.ctypes.data), 'mfb_synthesizer_end')
-            return out
-        _lib.check(self.lib.mfb_synthesizer_end(self.h, None), 'mfb_synthesizer_end')
-        return None
+        return self._end(copy)                                # (not ``copy``: None; ask ``device_output``)
 
     def device_output(self, buffer):
         """(device_ptr, count) of output set ``buffer``."""
-        ptr, n = C.c_void_p(), C.c_int64()
-        _lib.check(self.lib.mfb_synthesizer_device_output(self.h, buffer, C.byref(ptr), C.byref(n)), 'mfb_synthesizer_device_output')
-        return ptr.value, n.value
+        return self._device_output(buffer)
 
     def model(self, out_base, out_count, placements, form='direct'):
         """The definition in float64 before rounding, from the host samples of ``set_source``: (w complex128 [out_count], S float64

@@ -94,8 +94,9 @@ MOVED_LIMITS = ('CHZ_MAX_CHANNELS', 'CHZ_MAX_DECIM', 'CHZ_MAX_TAPS', 'CHZ_MAX_TH
 def test_each_helper_and_limit_is_defined_once():
     src = lambda name: open(os.path.join(CSRC, name)).read()                             # noqa: E731
     plan = src('channelize_plan.hpp')
-    others = {name: src(name) for name in ('mfbank.hip', 'channelize_kernels.hpp', 'channelize_rational_kernels.hpp',
-                                           'channelize_uniform_kernels.hpp', 'channelize_survey_kernels.hpp')}
+    others = {name: src(name) for name in ('mfbank.hip', 'channelize_api.hpp', 'synthesize_uniform_api.hpp', 'channelize_kernels.hpp',
+                                           'channelize_rational_kernels.hpp', 'channelize_uniform_kernels.hpp',
+                                           'channelize_survey_kernels.hpp')}
     for name in MOVED_HELPERS:
         define = rf'^[ \w]*\b{name}\s*\([^;]*\)\s*\{{'                                   # a function's head, at the start of a line
         assert len(re.findall(define, plan, re.M)) == 1, name
@@ -105,8 +106,8 @@ def test_each_helper_and_limit_is_defined_once():
         assert len(re.findall(define, plan, re.M)) == 1, name
         assert not any(re.search(define, text, re.M) for text in others.values()), name
     # the handle states its plan as a ChzGeom, not as a pair of booleans
-    hip = others['mfbank.hip']
-    handle = hip[hip.index('struct mfb_channelizer {'):]
+    hip = others['channelize_api.hpp']                      # (the channeliser's host side: a part of mfbank.hip's translation unit)
+    handle = hip[hip.index('struct mfb_channelizer '):]
     handle = handle[:handle.index('\n};')]
     assert 'ChzGeom plan' in handle and not re.search(r'\bbool\b[^;]*\b(uniform|rational)\b', handle)
     # the plan is host arithmetic: no HIP header, no runtime call, no handle

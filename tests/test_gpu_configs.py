@@ -313,6 +313,39 @@ def test_failed_create_frees_everything():
     assert abs(free2 - free3) < (32 << 20), (free2, free3)
 
 
+def test_failed_side_handle_create_frees_everything():
+    """The same for the creates of the six side handles (sync finder, combiner, modulator, channel, both channelisers, synthesiser)
+    at their smallest shapes: a simulated failure at each of a create's device allocations, by status and by std::bad_alloc, is
+    MFB_ERR_ALLOC, leaves *out NULL and the device's free memory where it was; past the last allocation the create succeeds."""
+    import ctypes as C
+    import torch
+    from pycusdr_amd import _lib
+    from side_handles import CREATES, create, destroy
+    lib = _lib.load()
+    for name in CREATES:                     # code objects, context, the runtime's pools: resident before the baseline is read
+        destroy(lib, name, create(lib, name))
+    torch.cuda.synchronize()
+    free0, _ = torch.cuda.mem_get_info()
+    for name, (make, _, nalloc) in CREATES.items():
+        for nth in range(1, nalloc + 2):
+            for sign in (1, -1):
+                h = C.c_void_p(0xDEAD)
+                lib.mfb_debug_fail_alloc(sign * nth)
+                try:
+                    rc = make(lib, C.byref(h))
+                finally:
+                    lib.mfb_debug_fail_alloc(0)
+                if nth <= nalloc:
+                    assert rc == _lib.MFB_ERR_ALLOC and h.value is None, (name, sign * nth, rc, h.value)
+                else:                        # the countdown outlives the create's allocations: every one of them was walked
+                    assert rc == _lib.MFB_OK and h.value, (name, sign * nth, rc)
+                    destroy(lib, name, h)
+                torch.cuda.synchronize()
+                free1, _ = torch.cuda.mem_get_info()
+                print(f'{name} nth {sign * nth}: rc {rc}, free {free1 - free0:+d} bytes')
+                assert free1 == free0, (name, sign * nth, free0, free1)
+
+
 def test_two_handles_and_concurrent_sync_calls():
     """Two handles on one device used from two threads, each interleaving searches with sync-correlator
     calls: per-call workspaces and streams, results equal to the single-threaded ones."""

@@ -205,6 +205,44 @@ def main():
         cmb.combine(bits[:4096], np.ones(4096, np.int8), [], 3.0, 16)
         cmb.close()
 
+    small_taps = np.array([0.25, 0.5, 0.25], dtype=np.float32)
+    small_in = (np.arange(64) % 7 - 3 + 1j * (np.arange(64) % 5 - 2)).astype(np.complex64)
+    small_bits = np.zeros(64, np.uint8)
+    small_bits[20:36] = 1
+
+    def side_handles():
+        """The six side handles (csrc/stage_handle.hpp) at the smallest shapes each accepts -- those of tests/side_handles.py --:
+        created, run once, destroyed."""
+        from pycusdr_amd.channel import Channel
+        from pycusdr_amd.channelizer import Channelizer, UniformChannelizer
+        from pycusdr_amd.mfbank import Combiner, SyncFinder
+        from pycusdr_amd.modulator.device import DeviceModulator
+        from pycusdr_amd.synthesizer import UniformSynthesizer
+        sf = SyncFinder([np.ones(16, np.int8)], [16], max_hits=4, max_bits=64)
+        sf.find(small_bits)
+        sf.close()
+        cmb = Combiner(max_bits=64, max_slaves=0)
+        cmb.combine(small_bits, np.full(64, 5, np.int8), [], 3.0, 16)
+        cmb.close()
+        mod = DeviceModulator(2, 4)
+        mod.set_lut(0, np.array([[-0.3, -0.3], [0.3, 0.3]]))
+        mod.begin([np.array([1, 0])])
+        mod.end(copy=False)
+        mod.close()
+        ch = Channel(1.0, seed=5, max_samples=3, max_source=4, max_frames=1)
+        ch.render(1, 3, sigma=1.0)
+        ch.close()
+        chz = Channelizer(1.0, 2, small_taps, [0.25], max_in=16, max_out=8)
+        chz.process(0, small_in[:16], 0, 4)
+        chz.close()
+        chu = UniformChannelizer(1.0, 8, 2, small_taps, bins=[1], max_in=64, max_out=8)
+        chu.process(0, small_in, 0, 4)
+        chu.close()
+        syn = UniformSynthesizer(1.0, 8, 2, small_taps, max_out=5, max_source=4, max_frames=1)
+        syn.set_source(small_in[:4])
+        syn.process(0, 5, [syn.placement(1, 0, 0, 4)])
+        syn.close()
+
     stages = [('hip_streams', hip_streams), ('hip_priority_streams', hip_priority_streams), ('hip_events', hip_events),
               ('hip_pinned', hip_pinned), ('hip_device', hip_device), ('handle_only', handle_only), ('handle_search', handle_search),
               ('handle_blocks', handle_blocks), ('runner_b1', runner(1)), ('runner_b4', runner(4)), ('runner_auto', runner(0)),
@@ -212,7 +250,8 @@ def main():
               ('runner_b16_gc', runner(16, collect=True)), ('runner_b16_48', runner(16, blocks=48)), ('decoder_only', decoder_only), ('runner_b32', runner(32)), ('handle_windows4', handle_windows(4)),
               ('handle_windows32', handle_windows(32)), ('batch_once', batch_handle(False, 1)), ('batch_x3', batch_handle(False, 3)),
               ('batch_stages_once', batch_handle(True, 1)), ('batch_stages_x3', batch_handle(True, 3)), ('host_copy', host_copy),
-              ('pinned_big', pinned_big), ('device_big', device_big), ('late_allocations', late_allocations)]
+              ('pinned_big', pinned_big), ('device_big', device_big), ('late_allocations', late_allocations),
+              ('side_handles', side_handles)]
     for name, f in stages:
         if only and name not in only:
             continue
