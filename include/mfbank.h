@@ -907,6 +907,36 @@ int mfb_channelizer_set_plan_rational(mfb_channelizer *c, int interp, int decim,
 int mfb_channelizer_create_uniform(mfb_channelizer **out, int device, int nbins, int max_selected, int max_taps, int max_in, int max_out);
 int mfb_channelizer_set_plan_uniform(mfb_channelizer *c, int decim, const float *taps, int ntaps, const int32_t *bins, int nselected,
                                      int sample_format, float sample_scale);
+/* Rational resampling on the raster (csrc/channelize_uniform_rational_kernels.hpp): a plan of a handle of
+ * mfb_channelizer_create_uniform that resamples every bin by U / D instead of decimating it by D, for capture rates that are no
+ * integer multiple of the bank's (2.4 MHz -> 153.6 kHz is 8 / 125).  No reference counterpart: the reference takes one narrowband
+ * stream at the bank's own rate (pyCuSDR.py:245-251).
+ * The definition is mfb_channelizer_set_plan_rational's with the exact words freq_k = k 2^64 / M, for which it collapses as the
+ * integer one does.  With real taps h[0..T) at the virtual rate U fs, q(m) = (m D) div U and r(m) = (m D) mod U:
+ *     y_k[m] = sum_{j : r + j U < T} h[r + j U] x[q - j] e^{-2 pi i k (q - j) / M}               x[n] = 0 for n < 0
+ *            = sum_{s < M} v_m[s] e^{+2 pi i k s / M}
+ *     u_m[p] = sum_{i : r + (p + i M) U < T} h[r + (p + i M) U] x[q - p - i M]       p = 0 .. M - 1
+ *     v_m[s] = u_m[(s + q) mod M]
+ * A branch sum starts from (-0, -0) and adds its terms in the order i = 0, 1, ..., one fused multiply-add per component and tap,
+ * exactly the taps with r + (p + i M) U < T; the transform is mfb_channelizer_set_plan_uniform's.  y_k[m] is a pure function of
+ * (h, U, D, M, the samples it reads, m): any cut of a span, any input window that covers it, any selection of bins and either output
+ * set give the same bits.  Against the float64 definition every component is within (ceil(Tb / M) + 3 log2 M + 2) 2^-24 S_m with
+ * Tb = ceil(T / U) and S_m = sum_j |h[r + j U]| |x[q - j]|; where S_m = 0 the output is zero exactly.  With U = 1 the definition and
+ * the bits are mfb_channelizer_set_plan_uniform's, but this call always selects the rational kernel, also at interp = 1;
+ * mfb_channelizer_set_plan_uniform keeps its own.
+ * Every other call of the handle works under such a plan as under a uniform one, with these differences.  The handle's max_taps
+ * bounds the taps of a branch, ceil(T / U), not T.  mfb_channelizer_begin: the outputs [out_base, out_base + out_count) read the
+ * inputs [q(out_base) - (Tb - 1), q(out_base + out_count - 1)], the rule of mfb_channelizer_set_plan_rational.  mfb_channelizer_info:
+ * outputs_per_workgroup is F, the consecutive frames a workgroup makes under this plan (the largest that 64 KiB of LDS hold, F M a
+ * multiple of 256), taps_capacity is max_taps.  The survey stays a matter of integer plans: mfb_channelizer_set_survey under such a
+ * plan, and this call while a survey is set, are MFB_ERR_UNSUPPORTED.
+ * Limits (MFB_ERR_UNSUPPORTED beyond): 1 <= U <= 32; 2 <= D <= U M, the output rate may not fall below the bin spacing;
+ * ceil(T / U) <= 4096; 1..M selected bins; those of mfb_channelizer_begin.  MFB_ERR_ARG: a common factor of U and D, U >= D (net
+ * rate reduction only), T < U (every branch has at least one tap), ceil(T / U) above the handle's max_taps, and everything
+ * mfb_channelizer_set_plan_uniform refuses with it.  MFB_ERR_STATE: a handle of mfb_channelizer_create; a call in flight.  Misuse is
+ * an error code, never a fault. */
+int mfb_uniform_channelizer_set_plan_rational(mfb_channelizer *c, int interp, int decim, const float *taps, int ntaps,
+                                              const int32_t *bins, int nselected, int sample_format, float sample_scale);
 /* The survey of the raster (csrc/channelize_survey_kernels.hpp): how much power every one of the M bins of a uniform plan held in
  * each stretch of time, what the noise floor was, and which (bin, stretch) cells stand above it -- reduced on the device from the
  * frames a call makes anyway, with or without writing any of them.  No reference counterpart: the reference takes one narrowband

@@ -238,6 +238,7 @@ PROTOTYPES = {
     'mfb_channelizer_set_plan_rational': (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _i, C.c_float]),
     'mfb_channelizer_create_uniform': (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i, _i]),
     'mfb_channelizer_set_plan_uniform': (_i, [_vp, _i, _vp, _i, _vp, _i, _i, C.c_float]),
+    'mfb_uniform_channelizer_set_plan_rational': (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _i, C.c_float]),
     'mfb_channelizer_set_survey': (_i, [_vp, _i, _i, C.c_float]),
     'mfb_channelizer_survey_info': (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _fp]),
     'mfb_channelizer_survey_begin': (_i, [_vp, C.POINTER(ChannelizerParams), _i]),

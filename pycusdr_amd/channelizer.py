@@ -43,6 +43,16 @@ centre a multiple of ``fs / M``, M a power of two, the words ``freq_k = k 2**64 
 M branch sums with real taps, a circular shift and one M-point transform per output frame give all M bins: 2 T + 5 M log2 M flops
 instead of 8 M T.  The yardstick stays the float64 model above on those words.
 
+Resampling on the raster (``UniformChannelizer(..., interp=U)``; mfb_uniform_channelizer_set_plan_rational,
+csrc/channelize_uniform_rational_kernels.hpp).  The rational definition collapses on those words in the same way, with ``q`` in the
+place of ``m D`` and the frame's branch ``h[r + jU]`` in the place of the taps:
+
+    y_k[m] = sum_{s < M} v_m[s] exp(+2 pi i k s / M)       v_m[s] = u_m[(s + q) mod M]
+    u_m[p] = sum over i with r + (p + iM) U < T of h[r + (p + iM) U] x[q - p - iM]        p = 0 .. M - 1
+
+1 <= U <= 32, U < D <= U M (the output rate does not fall below the bin spacing), ``ceil(T / U) <= 4096``.  The yardstick is the
+rational model above on those words; per component the device is within ``(ceil(ceil(T / U) / M) + 3 log2 M + 2) 2**-24 S_m``.
+
 The survey of the raster (``UniformChannelizer.set_survey`` / ``survey``; mfb_channelizer_set_survey,
 csrc/channelize_survey_kernels.hpp): which bins hold a signal, and when, without writing any of them.  With ``y_k[m]`` the uniform
 plan's complex64 output of bin k = 0 .. M - 1 and a cell length ``L = 2**l`` frames, 2 <= l <= 16:
@@ -391,17 +401,24 @@ class Channelizer(OutputStage):
         return y, S
 
 
-def check_plan_uniform(nbins, decim, taps, bins, sample_format, sample_scale):
-    """The checks of mfb_channelizer_create_uniform and mfb_channelizer_set_plan_uniform, as ValueError: (M, decim, taps float32,
-    bins int32 in [0, M), scale).  ``bins``: indices -M/2 <= b < M, taken modulo M; None: all M in index order."""
-    M, decim = int(nbins), int(decim)
+def check_plan_uniform(nbins, decim, taps, bins, sample_format, sample_scale, interp=1):
+    """The checks of mfb_channelizer_create_uniform and mfb_channelizer_set_plan_uniform and, for ``interp``, of
+    mfb_uniform_channelizer_set_plan_rational, as ValueError: (M, decim, taps float32, bins int32 in [0, M), scale).  ``bins``:
+    indices -M/2 <= b < M, taken modulo M; None: all M in index order."""
+    M, decim, interp = int(nbins), int(decim), int(interp)
     if M not in UNIFORM_BINS:
         raise ValueError(f'nbins is one of {UNIFORM_BINS}')
-    if not 2 <= decim <= M:
-        raise ValueError('2 <= decim <= nbins')
+    if not 1 <= interp <= MAX_INTERP:
+        raise ValueError(f'1 <= interp <= {MAX_INTERP}')
+    if not 2 <= decim <= interp * M:
+        raise ValueError('2 <= decim <= interp * nbins: the output rate does not fall below the bin spacing')
+    if interp >= decim or math.gcd(interp, decim) != 1:
+        raise ValueError('interp < decim, and the two have no common factor')
     taps = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
-    if not 1 <= len(taps) <= UNIFORM_MAX_TAPS or not np.all(np.isfinite(taps)):
-        raise ValueError(f'1 .. {UNIFORM_MAX_TAPS} finite taps')
+    if not 1 <= -(-len(taps) // interp) <= UNIFORM_MAX_TAPS or not np.all(np.isfinite(taps)):
+        raise ValueError(f'1 .. {UNIFORM_MAX_TAPS} finite taps per branch (interp * {UNIFORM_MAX_TAPS} in all)')
+    if len(taps) < interp:
+        raise ValueError('at least interp taps: every branch has one')
     b = np.arange(M, dtype=np.int64) if bins is None else np.atleast_1d(np.asarray(bins)).reshape(-1)
     if b.dtype.kind not in 'iu':
         raise ValueError('bins are integers')
@@ -423,6 +440,25 @@ def check_plan_uniform(nbins, decim, taps, bins, sample_format, sample_scale):
     return M, decim, taps, b, scale
 
 
+def uniform_rate(fs_in, fs_out, nbins):
+    """(U, D), the ratio ``fs_out / fs_in`` in lowest terms (taken with ``fractions.Fraction``), for a
+    ``UniformChannelizer(fs_in, nbins, D, design_taps(D, interp=U), interp=U)``: ``uniform_rate(2.4e6, 153600, 64) == (8, 125)``.
+    ValueError where one plan cannot do it: nbins outside the set, a ratio >= 1, U > 32, or D > U * nbins (an output rate below the
+    bin spacing)."""
+    M = int(nbins)
+    if M not in UNIFORM_BINS:
+        raise ValueError(f'nbins is one of {UNIFORM_BINS}')
+    ratio = Fraction(fs_out) / Fraction(fs_in)
+    if not 0 < ratio < 1:
+        raise ValueError('0 < fs_out < fs_in: net rate reduction only')
+    U, D = ratio.numerator, ratio.denominator
+    if U > MAX_INTERP:
+        raise ValueError(f'{U}/{D}: interp <= {MAX_INTERP}')
+    if D > U * M:
+        raise ValueError(f'{U}/{D}: decim <= interp * nbins = {U * M}, the output rate does not fall below the bin spacing')
+    return U, D
+
+
 class UniformChannelizer(Channelizer):
     """The channels of a raster: bin b of ``nbins = M`` (8 .. 256, a power of two) sits at ``b * fs / M``, is filtered with the real
     ``taps`` and decimated by ``decim`` (2 <= D <= M; D need not divide M, critical sampling is D = M).  The definition is
@@ -431,22 +467,37 @@ class UniformChannelizer(Channelizer):
     ``bins`` -- indices, signed or unsigned: -M/2 <= b < M, taken modulo M; None: all M in index order --, row i of the output
     being ``bins[i]``.  ``design_taps(decim)`` is the prototype for it.  Everything else is ``Channelizer``'s surface: ``K`` is the
     number of selected bins, ``interp`` is 1, ``info()`` gives (frames per workgroup, tap capacity); ``backend='host'`` and
-    ``model`` are the same float64 arithmetic on the exact words.  ``ChannelizerSource`` and ``ChannelWide`` take it as it is."""
+    ``model`` are the same float64 arithmetic on the exact words.  ``ChannelizerSource`` and ``ChannelWide`` take it as it is.
+
+    ``interp = U > 1`` resamples every bin by U / decim instead (the module docstring; mfb_uniform_channelizer_set_plan_rational,
+    csrc/channelize_uniform_rational_kernels.hpp): 1 <= U <= 32, U < D <= U M, no common factor, taps at the virtual rate ``U fs``
+    with U <= T and ``ceil(T / U) <= 4096``; ``design_taps(decim, interp=U)`` is the prototype, ``uniform_rate`` gives (U, D) for
+    two rates.  ``interp`` and ``rational`` are then set as ``Channelizer`` sets them, so ``needed_input``, ``model``,
+    ``backend='host'`` and ``ChannelizerSource`` are the rational ones; ``info()`` gives the frames per workgroup of that plan and
+    the taps of the longest branch; ``set_survey`` raises."""
 
     def __init__(self, fs, nbins, decim, taps, bins=None, sample_format='cf32', sample_scale=1.0, backend='hip', device=0, max_in=1 << 20,
-                 max_out=None):
+                 max_out=None, interp=1, force_rational=False):
+        """``interp = U``: resample every bin by U / decim (the class docstring); 1 takes the integer kernel, unless
+        ``force_rational`` (the tests' seam) sends that plan through the rational kernel too."""
         self._check_backend(fs, backend, device)
-        self.nbins, self.decim, self.taps, self.bins, self.scale = check_plan_uniform(nbins, decim, taps, bins, sample_format, sample_scale)
+        self.nbins, self.decim, self.taps, self.bins, self.scale = check_plan_uniform(nbins, decim, taps, bins, sample_format, sample_scale,
+                                                                                      interp)
         # exact: M is a power of two.  (The float route signed_quantise(2 pi f / fs) rounds some of them differently from M = 64 on.)
         self.words = np.array([(int(b) << 64) // self.nbins for b in self.bins], dtype=np.uint64)
-        self.interp, self.rational = 1, False
+        self.interp = int(interp)
+        self.rational = self.interp > 1 or bool(force_rational)
         self.sample_format, self.T, self.K = sample_format, len(self.taps), len(self.bins)
         self._init_tail(max_in, max_out, UNIFORM_MAX_SET)
         if backend == 'hip':
-            _lib.check(self.lib.mfb_channelizer_create_uniform(C.byref(self.h), device, self.nbins, self.K, self.T, self.max_in, self.max_out),
+            # the handle's tap capacity: the taps of a frame -- T, or the longest branch of a rational plan
+            _lib.check(self.lib.mfb_channelizer_create_uniform(C.byref(self.h), device, self.nbins, self.K, self.Tb, self.max_in, self.max_out),
                        'mfb_channelizer_create_uniform')
-            self._call('mfb_channelizer_set_plan_uniform', self.decim, self.taps.ctypes.data, self.T, self.bins.ctypes.data, self.K,
-                       FORMATS[sample_format], self.scale)
+            plan = (self.decim, self.taps.ctypes.data, self.T, self.bins.ctypes.data, self.K, FORMATS[sample_format], self.scale)
+            if self.rational:
+                self._call('mfb_uniform_channelizer_set_plan_rational', self.interp, *plan)
+            else:
+                self._call('mfb_channelizer_set_plan_uniform', *plan)
 
     @property
     def freqs_hz(self):
@@ -459,7 +510,10 @@ class UniformChannelizer(Channelizer):
 
     def set_survey(self, cell_frames, rank=None, threshold=4.0):
         """The cell length L (a power of two, 4 .. 65536, at most ``max_out``), the floor's rank (default M / 4) and the mask's
-        threshold (finite, >= 1) of the ``survey`` calls to come.  ``cell_frames = 0`` turns the survey off."""
+        threshold (finite, >= 1) of the ``survey`` calls to come.  ``cell_frames = 0`` turns the survey off.  The survey is a matter
+        of integer plans: ValueError under a rational one (``interp > 1`` or ``force_rational``)."""
+        if self.rational:
+            raise ValueError('the survey is not available under a rational plan')
         L = int(cell_frames)
         if L == 0:
             self._survey = None

@@ -1,14 +1,15 @@
-// channelize_api.hpp -- the host side of the channeliser (mfb_channelizer_*): the four kinds of plan and the survey.
+// channelize_api.hpp -- the host side of the channeliser (mfb_channelizer_*): the five kinds of plan and the survey.
 // A part of mfbank.hip's one translation unit: included there once, behind the channelize_*_kernels.hpp and channelize_plan.hpp and stage_handle.hpp.  Host code only.
 #pragma once
 
 // ---- the channeliser (channelize_plan.hpp: the limits and what a plan of each kind launches; the kernels: channelize_kernels.hpp,
-// channelize_rational_kernels.hpp, channelize_uniform_kernels.hpp, channelize_survey_kernels.hpp) -------------------------------
+// channelize_rational_kernels.hpp, channelize_uniform_kernels.hpp, channelize_uniform_rational_kernels.hpp,
+// channelize_survey_kernels.hpp) -----------------------------------------------------------------------------------------------
 // the output sets: [max_channels][out_stride] each
 struct mfb_channelizer : StageHandle, OutputSets, CallTimer {
     int max_channels = 0, max_taps = 0, max_in = 0, max_out = 0;
     int M = 0;                 // the bins of a handle made by mfb_channelizer_create_uniform, which takes plans of
-                               // mfb_channelizer_set_plan_uniform only; 0: made by mfb_channelizer_create
+                               // mfb_channelizer_set_plan_uniform and mfb_uniform_channelizer_set_plan_rational only; 0: mfb_channelizer_create
     int out_stride = 0;        // float2 between two channels of an output set: max_out made even, so every channel is 16-byte aligned
     HostBuf<uint8_t> h_in[2];  // page-locked raw staging, on demand (mfb_channelizer_input_buffer)
     DevBuf<uint8_t> d_in[2];   // their device copies, on demand
@@ -22,6 +23,7 @@ struct mfb_channelizer : StageHandle, OutputSets, CallTimer {
     int K = 0, fmt = 0, ncplx = 0;
     int rtap_stride = 0;       // max_taps + CHZR_MAX_INTERP - 1 >= U Tb
     DevBuf<ChuPlan> d_uplan;   // a uniform handle's twiddle table and the selected bins' columns
+    DevBuf<float> d_ubr;       // a uniform rational plan's taps by branch, [U][ceil(T / U)] within CHZR_MAX_INTERP max_taps, on demand
     float scale = 1.0f;
     int nchan[2] = {0, 0};     // the plan's channels when a set was written
     // the survey of a uniform plan (mfb_channelizer_set_survey)
@@ -91,15 +93,16 @@ extern "C" int mfb_channelizer_create_uniform(mfb_channelizer **out, int device,
 
 // What every set_plan refuses, in the order of the codes: `which` are the plan's n tuning words or selected bins; kind_tests() the
 // limits and the arguments of the one kind of plan, MFB_ERR_UNSUPPORTED before MFB_ERR_ARG.  *scale: the scale the plan runs with.
+// branch_interp: the U of a rational plan on the raster, whose handle holds max_taps taps per branch; 1 for every other kind.
 template <class KindTests>
 static int chz_plan_check(mfb_channelizer *c, bool uniform, const float *taps, int ntaps, const void *which, int n, int fmt, float sample_scale,
-                          float *scale, KindTests kind_tests) {
+                          float *scale, KindTests kind_tests, int branch_interp = 1) {
     if (!c || !taps || !which || ntaps < 1 || n < 1) return MFB_ERR_ARG;
     if ((c->M != 0) != uniform) return MFB_ERR_STATE;
     if (!chz_format_ok(fmt)) return MFB_ERR_ARG;
     const int rc = kind_tests();
     if (rc) return rc;
-    if (ntaps > c->max_taps || n > c->max_channels) return MFB_ERR_ARG;
+    if (chzr_branch_taps(branch_interp, ntaps) > c->max_taps || n > c->max_channels) return MFB_ERR_ARG;
     if (!chz_plan_scale(fmt, sample_scale, chan_scale_ok, scale) || !chz_taps_finite(taps, ntaps)) return MFB_ERR_ARG;
     return c->busy ? MFB_ERR_STATE : MFB_OK;
 }
@@ -201,19 +204,41 @@ static void chu_twiddles(int M, float2 *tw) {
     }
 }
 
-static int chu_set_plan_body(mfb_channelizer *c, int decim, const float *taps, int ntaps, const int32_t *bins, int nsel, int fmt, float scale) {
+// kind: CHZ_UNIFORM (interp 1) or CHZ_UNIFORM_RATIONAL, which runs k_chur also at U = 1
+static int chu_set_plan_body(mfb_channelizer *c, int kind, int interp, int decim, const float *taps, int ntaps, const int32_t *bins, int nsel,
+                             int fmt, float scale) {
     HIPCHK(hipSetDevice(c->device));
     ChuPlan P;
     memset(&P, 0, sizeof(P));
     const int M = c->M;
     chu_twiddles(M, P.tw);
     for (int i = 0; i < nsel; ++i) P.col[i] = chu_column(M, bins[i]);
+    const ChzGeom g = chz_geom(kind, interp, decim, ntaps, M);
+    std::vector<float> branches;                   // [r][j] = h[r + j U], rows of Tb; 0, never read, where r + j U >= T
     c->have_plan = false;
     HIPCHK(chus_drop(c));                          // a survey belongs to the plan it was set under
-    HIPCHK(hipMemcpyAsync(c->d_h, taps, (size_t)ntaps * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (kind == CHZ_UNIFORM_RATIONAL) {
+        if (!c->d_ubr) HIPCHK(c->d_ubr.alloc((size_t)CHZR_MAX_INTERP * c->max_taps * sizeof(float), hip_malloc));
+        branches.assign((size_t)g.U * g.Tb, 0.0f);
+        for (int t = 0; t < ntaps; ++t) branches[(size_t)(t % g.U) * g.Tb + t / g.U] = taps[t];
+        HIPCHK(hipMemcpyAsync(c->d_ubr, branches.data(), branches.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        c->survey = {};                            // the survey is a matter of integer plans
+    } else {
+        HIPCHK(hipMemcpyAsync(c->d_h, taps, (size_t)ntaps * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        c->survey = chz_geom(CHZ_SURVEY, 1, decim, ntaps, M);
+    }
     HIPCHK(hipMemcpyAsync(c->d_uplan, &P, sizeof(P), hipMemcpyHostToDevice, c->stream));
-    c->survey = chz_geom(CHZ_SURVEY, 1, decim, ntaps, M);
-    return chz_plan_commit(c, chz_geom(CHZ_UNIFORM, 1, decim, ntaps, M), nsel, 0, fmt, scale);
+    return chz_plan_commit(c, g, nsel, 0, fmt, scale);                           // (waits: `branches` and P have been read)
+}
+
+// MFB_ERR_ARG for a selected bin outside [0, M) or named twice
+static int chu_bins_check(const mfb_channelizer *c, const int32_t *bins, int nselected) {
+    bool seen[CHU_MAX_BINS] = {};
+    for (int i = 0; i < nselected; ++i) {
+        if (bins[i] < 0 || bins[i] >= c->M || seen[bins[i]]) return MFB_ERR_ARG;
+        seen[bins[i]] = true;
+    }
+    return MFB_OK;
 }
 
 extern "C" int mfb_channelizer_set_plan_uniform(mfb_channelizer *c, int decim, const float *taps, int ntaps, const int32_t *bins, int nselected,
@@ -221,15 +246,28 @@ extern "C" int mfb_channelizer_set_plan_uniform(mfb_channelizer *c, int decim, c
     float scale = 1.0f;
     const int rc = chz_plan_check(c, true, taps, ntaps, bins, nselected, sample_format, sample_scale, &scale, [&]() -> int {
         if (decim < 2 || decim > c->M || ntaps > CHU_MAX_TAPS || nselected > c->M) return MFB_ERR_UNSUPPORTED;
-        bool seen[CHU_MAX_BINS] = {};
-        for (int i = 0; i < nselected; ++i) {
-            if (bins[i] < 0 || bins[i] >= c->M || seen[bins[i]]) return MFB_ERR_ARG;
-            seen[bins[i]] = true;
-        }
-        return MFB_OK;
+        return chu_bins_check(c, bins, nselected);
     });
     if (rc) return rc;
-    return guarded([&] { return chu_set_plan_body(c, decim, taps, ntaps, bins, nselected, sample_format, scale); });
+    return guarded([&] { return chu_set_plan_body(c, CHZ_UNIFORM, 1, decim, taps, ntaps, bins, nselected, sample_format, scale); });
+}
+
+extern "C" int mfb_uniform_channelizer_set_plan_rational(mfb_channelizer *c, int interp, int decim, const float *taps, int ntaps,
+                                                         const int32_t *bins, int nselected, int sample_format, float sample_scale) {
+    float scale = 1.0f;
+    const int rc = chz_plan_check(
+        c, true, taps, ntaps, bins, nselected, sample_format, sample_scale, &scale,
+        [&]() -> int {
+            if (interp < 1 || interp > CHZR_MAX_INTERP || decim < 2 || decim > interp * c->M || nselected > c->M) return MFB_ERR_UNSUPPORTED;
+            if (chzr_branch_taps(interp, ntaps) > CHU_MAX_TAPS) return MFB_ERR_UNSUPPORTED;
+            if (c->sv_L) return MFB_ERR_UNSUPPORTED;                             // a survey is set: it stays with integer plans
+            if (interp >= decim || ntaps < interp || !chzr_coprime(interp, decim)) return MFB_ERR_ARG;
+            return chu_bins_check(c, bins, nselected);
+        },
+        interp);
+    if (rc) return rc;
+    return guarded(
+        [&] { return chu_set_plan_body(c, CHZ_UNIFORM_RATIONAL, interp, decim, taps, ntaps, bins, nselected, sample_format, scale); });
 }
 
 extern "C" int mfb_channelizer_input_buffer(mfb_channelizer *c, int which, void **host, size_t *bytes) {
@@ -296,6 +334,38 @@ static void chu_launch(mfb_channelizer *c, const mfb_channelizer_params *p, cons
         visit_chz_fmt(c->fmt, [&](auto fmt) {
             hipLaunchKernelGGL((k_chu<decltype(m)::value, decltype(fmt)::value>), dim3(chz_grid(g, p->out_count)), dim3(g.threads), g.lds_bytes,
                                c->stream, A, (const ChuPlan *)c->d_uplan, raw, (const float *)c->d_h, c->d_out[p->buffer].get());
+        });
+    });
+}
+
+// U / gcd(U, 256 / M): frames that far apart in a lane's walk share a branch (channelize_uniform_rational_kernels.hpp)
+static int chur_share(int U, int M) {
+    int a = U, b = CHU_THREADS / M;
+    while (b) {
+        const int r = a % b;
+        a = b;
+        b = r;
+    }
+    return U / a;
+}
+
+static void chur_launch(mfb_channelizer *c, const mfb_channelizer_params *p, const void *raw) {
+    const ChzGeom &g = c->plan;
+    ChurArgs A = chz_window<ChurArgs>(c, g, p);
+    A.U = g.U;
+    A.Tb = g.Tb;
+    A.F = g.tile;
+    A.nsel = c->K;
+    A.span = g.S;
+    A.share = chur_share(g.U, g.M);
+    const int step = (CHU_THREADS / g.M) * g.D;                   // positions at the virtual rate between two frames of a lane's walk
+    A.share_dq = A.share * step / g.U;                            // exact: share (256 / M) is a multiple of U
+    A.step_dq = step / g.U;
+    A.step_r = step % g.U;
+    visit_chu_bins(g.M, [&](auto m) {
+        visit_chz_fmt(c->fmt, [&](auto fmt) {
+            hipLaunchKernelGGL((k_chur<decltype(m)::value, decltype(fmt)::value>), dim3(chz_grid(g, p->out_count)), dim3(g.threads), g.lds_bytes,
+                               c->stream, A, (const ChuPlan *)c->d_uplan, raw, (const float *)c->d_ubr, c->d_out[p->buffer].get());
         });
     });
 }
@@ -375,6 +445,7 @@ static int chz_begin_body(mfb_channelizer *c, const mfb_channelizer_params *p, i
         case CHZ_INTEGER: chz_launch(c, p, raw); break;
         case CHZ_RATIONAL: chzr_launch(c, p, raw); break;
         case CHZ_UNIFORM: chu_launch(c, p, raw); break;
+        case CHZ_UNIFORM_RATIONAL: chur_launch(c, p, raw); break;
         default: chus_launch(c, p, raw, write); break;
     }
     HIPCHK(hipGetLastError());
@@ -467,6 +538,7 @@ static int chus_set_body(mfb_channelizer *c, int cell_frames, int rank, float th
 extern "C" int mfb_channelizer_set_survey(mfb_channelizer *c, int cell_frames, int rank, float threshold) {
     if (!c) return MFB_ERR_ARG;
     if (!c->M || !c->have_plan || c->busy) return MFB_ERR_STATE;
+    if (c->plan.kind == CHZ_UNIFORM_RATIONAL) return MFB_ERR_UNSUPPORTED;      // the survey is a matter of integer plans
     if (cell_frames) {
         if (cell_frames < (1 << CHUS_MIN_LOG2) || cell_frames > (1 << CHUS_MAX_LOG2) || (cell_frames & (cell_frames - 1))) return MFB_ERR_ARG;
         if (rank < 0 || rank >= c->M || !std::isfinite(threshold) || threshold < 1.0f) return MFB_ERR_ARG;

@@ -1,7 +1,8 @@
 // channelize_plan.hpp -- the channeliser's launch plan: the ONE statement of its limits, of the arithmetic that sizes a workgroup's
 // LDS image, and of what a plan of each kind launches (mfb_channelizer_* and mfb_synthesizer_* in mfbank.hip; the kernels are
-// channelize_kernels.hpp, channelize_rational_kernels.hpp, channelize_uniform_kernels.hpp, channelize_survey_kernels.hpp and
-// synthesize_uniform_kernels.hpp, which include this for the limits their argument structs and launch bounds use).  Host only and
+// channelize_kernels.hpp, channelize_rational_kernels.hpp, channelize_uniform_kernels.hpp, channelize_uniform_rational_kernels.hpp,
+// channelize_survey_kernels.hpp and synthesize_uniform_kernels.hpp, which include this for the limits their argument structs and
+// launch bounds use).  Host only and
 // free of HIP, so a plain C++ compiler builds it (tests/csrc/channelize_plan_print.cpp and synthesize_plan_print.cpp;
 // tests/golden/channelize_plans.json was recorded from the helpers below before ChzGeom was built on them).
 #pragma once
@@ -70,6 +71,23 @@ static inline int chu_frames(int M, int D, int T) {
     return F;
 }
 
+// A rational plan on the raster (channelize_uniform_rational_kernels.hpp): F consecutive frames read the positions
+// q(m0) - (Tb - 1) .. q(m0 + F - 1), q(m) = (m D) div U, and q(m0 + F - 1) - q(m0) <= ((F - 1) D + U - 1) div U, reached where
+// (m0 D) mod U = U - 1.  With U = 1 the span, the bytes and the frames are chu_lds_bytes' and chu_frames'.
+static inline int chur_span(int U, int D, int T, int F) { return chzr_branch_taps(U, T) + (int)(((int64_t)(F - 1) * D + U - 1) / U); }
+static inline size_t chur_lds_bytes(int M, int U, int D, int T, int F) {
+    return ((size_t)chur_span(U, D, T, F) + (size_t)F * (M + 1) + M) * CHZ_CF_BYTES;
+}
+
+// frames per workgroup: chu_frames' rule with that span.  F = 1 at M = 256 always fits: (4096 + 257 + 256) * 8 bytes.
+static inline int chur_frames(int M, int U, int D, int T) {
+    const int step = 256 / M > 16 ? 256 / M : 16;
+    int F = 4096 / M > 128 ? 128 : 4096 / M;
+    while (F > step && chur_lds_bytes(M, U, D, T, F) > (size_t)CHU_LDS_BUDGET) F -= step;
+    while (F * M > 256 && chur_lds_bytes(M, U, D, T, F) > (size_t)CHU_LDS_BUDGET) F >>= 1;
+    return F;
+}
+
 // the synthesiser (synthesize_uniform_kernels.hpp): the image of the F + J - 1 input frames that the outputs of F frames read,
 // J = ceil(T / I), rows of M + 1 words; the twiddle table; the taps
 static inline int chsy_rows(int I, int T, int F) { return F + chzr_branch_taps(I, T) - 1; }
@@ -98,27 +116,28 @@ static inline int chus_frames(int M, int D, int T) {
 }
 
 // ---- what a plan launches
-enum ChzKind { CHZ_INTEGER = 0, CHZ_RATIONAL = 1, CHZ_UNIFORM = 2, CHZ_SURVEY = 3, CHZ_SYNTHESIS = 4 };   // k_chz, k_chzr, k_chu, k_chus, k_chsy
+// k_chz, k_chzr, k_chu, k_chus, k_chsy, k_chur (appended: recorded plans keep their values)
+enum ChzKind { CHZ_INTEGER = 0, CHZ_RATIONAL = 1, CHZ_UNIFORM = 2, CHZ_SURVEY = 3, CHZ_SYNTHESIS = 4, CHZ_UNIFORM_RATIONAL = 5 };
 
 struct ChzGeom {
     int kind;
     int U, D, T;           // interpolation (1 unless rational; the synthesiser's I), decimation (the synthesiser's is 1), taps
     int Tb;                // ceil(T / U): the taps of the longest branch
-    int M;                 // the raster's bins (uniform, survey, synthesis); 0 otherwise
+    int M;                 // the raster's bins (uniform, uniform rational, survey, synthesis); 0 otherwise
     int threads;           // lanes of a workgroup
     int tile;              // outputs per workgroup: threads, U threads, F or Fs by kind; synthesis: the F input frames whose F I
                            // outputs a workgroup makes, 0 where the plan does not fit
     int L;                 // float2 per LDS row (integer, rational); 0 otherwise
-    int S;                 // staged positions of a rational plan; 0 otherwise
+    int S;                 // staged positions of a rational plan, on the raster or not; 0 otherwise
     size_t lds_bytes;      // dynamic LDS of the launch
 };
 
-// U is read for a rational plan and for a synthesis (its I, with D = 1), M for a uniform plan, its survey or a synthesis; the
-// limits are the caller's to check
+// U is read for a rational plan, on the raster or not, and for a synthesis (its I, with D = 1), M for a plan on the raster, its
+// survey or a synthesis; the limits are the caller's to check
 static inline ChzGeom chz_geom(int kind, int U, int D, int T, int M) {
     ChzGeom g = {};
     g.kind = kind;
-    g.U = (kind == CHZ_RATIONAL || kind == CHZ_SYNTHESIS) ? U : 1;
+    g.U = (kind == CHZ_RATIONAL || kind == CHZ_SYNTHESIS || kind == CHZ_UNIFORM_RATIONAL) ? U : 1;
     g.D = D;
     g.T = T;
     g.Tb = chzr_branch_taps(g.U, T);
@@ -141,6 +160,13 @@ static inline ChzGeom chz_geom(int kind, int U, int D, int T, int M) {
             g.tile = chu_frames(M, D, T);
             g.lds_bytes = chu_lds_bytes(M, D, T, g.tile);
             break;
+        case CHZ_UNIFORM_RATIONAL:
+            g.M = M;
+            g.threads = CHU_THREADS;
+            g.tile = chur_frames(M, U, D, T);
+            g.S = chur_span(U, D, T, g.tile);
+            g.lds_bytes = chur_lds_bytes(M, U, D, T, g.tile);
+            break;
         case CHZ_SYNTHESIS:
             g.M = M;
             g.threads = CHU_THREADS;
@@ -157,7 +183,7 @@ static inline ChzGeom chz_geom(int kind, int U, int D, int T, int M) {
     return g;
 }
 
-// workgroups of a call of out_count outputs
+// workgroups of a call of out_count outputs (every kind but a synthesis tiles the outputs: tile is threads, U threads, F or Fs)
 static inline unsigned chz_grid(const ChzGeom &g, int out_count) { return (unsigned)((out_count + g.tile - 1) / g.tile); }
 
 // A synthesis tiles the input frames, not the outputs: the wide outputs [out_base, out_base + out_count) belong to the frames
@@ -173,8 +199,8 @@ static inline unsigned chsy_grid(const ChzGeom &g, int64_t out_base, int out_cou
 }
 
 // Every input that the outputs [out_base, out_base + out_count) read lies in [*first, *last]; *first may be negative, positions
-// below 0 read as zero.  A rational plan: [q(out_base) - (Tb - 1), q(out_base + out_count - 1)] with q(m) = (m D) div U, one
-// sample generous for short branches.
+// below 0 read as zero.  A rational plan, on the raster or not: [q(out_base) - (Tb - 1), q(out_base + out_count - 1)] with
+// q(m) = (m D) div U, one sample generous for short branches.
 static inline void chz_input_span(const ChzGeom &g, int64_t out_base, int out_count, int64_t *first, int64_t *last) {
     *first = out_base * g.D / g.U - (g.Tb - 1);
     *last = (out_base + out_count - 1) * g.D / g.U;

@@ -71,6 +71,7 @@
 #include "channelize_kernels.hpp"
 #include "channelize_rational_kernels.hpp"
 #include "channelize_uniform_kernels.hpp"
+#include "channelize_uniform_rational_kernels.hpp"
 #include "synthesize_uniform_kernels.hpp"
 #include "channelize_survey_kernels.hpp"
 #include "energy_kernels.hpp"
