@@ -39,8 +39,6 @@ struct mfb_channelizer : StageHandle, OutputSets, CallTimer {
     int sv_cells = 0;          // its cells
 };
 
-static size_t chz_sample_bytes(int fmt) { return fmt == MFB_SAMPLES_SC16 ? 4 : fmt == MFB_SAMPLES_SC8 ? 2 : 8; }
-
 extern "C" int mfb_channelizer_destroy(mfb_channelizer *c) { return stage_destroy(c); }
 
 static int chz_create_impl(mfb_channelizer *c) {
@@ -277,7 +275,7 @@ extern "C" int mfb_channelizer_input_buffer(mfb_channelizer *c, int which, void 
         HIPCHK(hipSetDevice(c->device));
         if (!c->h_in[which]) HIPCHK(c->h_in[which].alloc((size_t)c->max_in * sizeof(float2), hip_host_malloc));
         *host = c->h_in[which].get();
-        if (bytes) *bytes = (size_t)c->max_in * chz_sample_bytes(c->fmt);
+        if (bytes) *bytes = (size_t)c->max_in * sample_bytes(c->fmt);
         return (int)MFB_OK;
     });
 }
@@ -431,7 +429,7 @@ static void chz_launch(mfb_channelizer *c, const mfb_channelizer_params *p, cons
 // kind: the plan's for a plain call, CHZ_SURVEY for a survey call, which writes the output set only if `write`
 static int chz_begin_body(mfb_channelizer *c, const mfb_channelizer_params *p, int kind, bool write = true) {
     HIPCHK(hipSetDevice(c->device));
-    const size_t sb = chz_sample_bytes(c->fmt);
+    const size_t sb = sample_bytes(c->fmt);
     const void *raw = p->device_input;
     if (p->input != MFB_CHZ_INPUT_DEVICE) {
         const int w = p->input == MFB_CHZ_INPUT_PINNED1;
@@ -475,7 +473,7 @@ static int chz_begin_check(mfb_channelizer *c, const mfb_channelizer_params *p) 
     if (!c->have_plan) return MFB_ERR_STATE;
     const int D = c->plan.D;
     if (p->out_base >= (((int64_t)1 << 62) + D - 1) / D) return MFB_ERR_UNSUPPORTED;             // out_base * D < 2^62
-    if (p->input == MFB_CHZ_INPUT_DEVICE && ((uintptr_t)p->device_input & (chz_sample_bytes(c->fmt) - 1))) return MFB_ERR_ARG;
+    if (p->input == MFB_CHZ_INPUT_DEVICE && ((uintptr_t)p->device_input & (sample_bytes(c->fmt) - 1))) return MFB_ERR_ARG;
     if (p->input != MFB_CHZ_INPUT_DEVICE && !c->h_in[p->input == MFB_CHZ_INPUT_PINNED1]) return MFB_ERR_STATE;
     // every input an output reads, apart from the positions below 0, lies inside the call's input
     int64_t first = 0, last = 0;

@@ -1,5 +1,5 @@
 // channelize_plan.hpp -- the channeliser's launch plan: the ONE statement of its limits, of the arithmetic that sizes a workgroup's
-// LDS image, and of what a plan of each kind launches (mfb_channelizer_* and mfb_synthesizer_* in mfbank.hip; the kernels are
+// LDS image, and of what a plan of each kind launches (mfb_channelizer_* in channelize_api.hpp and mfb_synthesizer_* in synthesize_uniform_api.hpp; the kernels are
 // channelize_kernels.hpp, channelize_rational_kernels.hpp, channelize_uniform_kernels.hpp, channelize_uniform_rational_kernels.hpp,
 // channelize_survey_kernels.hpp and synthesize_uniform_kernels.hpp, which include this for the limits their argument structs and
 // launch bounds use).  Host only and
@@ -230,7 +230,7 @@ static inline ChusTables chus_tables(const ChzGeom &sv, int cell_frames, int max
 static inline bool chz_format_ok(int fmt) { return fmt == 0 || fmt == 1 || fmt == 2; }
 
 // The scale a plan runs with: 1 for complex64; for integers sample_scale, or 2^-15 (sc16) / 2^-7 (sc8) where that is 0.
-// false: scale_ok (chan_scale_ok of mfbank.hip: a power of two within 2^-100 .. 2^98) refuses it.
+// false: scale_ok (chan_scale_ok of channel_api.hpp: a power of two within 2^-100 .. 2^98) refuses it.
 static inline bool chz_plan_scale(int fmt, float sample_scale, bool (*scale_ok)(float), float *scale) {
     *scale = 1.0f;
     if (fmt == 0) return true;

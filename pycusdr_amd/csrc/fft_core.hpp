@@ -682,7 +682,7 @@ DEVI void dit_fused(cf (&v)[1 << LEVELS], const cf (&twr)[NTW]) {
 struct F256Regs {
     cf ct[8];
 };
-// table: [16 lanes][8] pairs behind the W_L table (mfbank.hip, append_fused_tables)
+// table: [16 lanes][8] pairs behind the W_L table (bank_lifecycle_api.hpp, append_fused_tables)
 DEVI void f256_setup(F256Regs &r, const cf *__restrict__ table, const int g) {
     sfor<0, 8>([&](auto k) { r.ct[decltype(k)::value] = table[g * 8 + decltype(k)::value]; });
 }

@@ -36,7 +36,7 @@ inline hipError_t hip_host_malloc(void **p, size_t bytes) { return hipHostMalloc
 // ... for memory the host reads while the kernel that writes it still runs
 inline hipError_t hip_host_malloc_coherent(void **p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocCoherent); }
 
-// The untyped part (what a group of buffers of different element types has in common: grow_buffers in mfbank.hip).
+// The untyped part (what a group of buffers of different element types has in common: grow_buffers in bank_ctx.hpp).
 template <class Del>
 class Mem {
     std::unique_ptr<void, Del> p_;

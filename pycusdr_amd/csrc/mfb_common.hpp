@@ -18,6 +18,9 @@
         }                                                                                    \
     } while (0)
 
+// bytes of one IQ sample in the format MFB_SAMPLES_* (the bank's inputs and windows, the channeliser's)
+static size_t sample_bytes(int fmt) { return fmt == MFB_SAMPLES_SC16 ? 4 : fmt == MFB_SAMPLES_SC8 ? 2 : 8; }
+
 // per-device tables (the sync workspaces, the page-locked sync buffers) are indexed by the device: the handles take none above it
 #define SYNC_MAX_DEVICES 64
 

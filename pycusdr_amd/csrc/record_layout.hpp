@@ -5,7 +5,7 @@
 //
 // Every piece starts on a 16-byte boundary; the record is contiguous so that ONE copy brings it to the host.  Host only and free of
 // HIP, so a plain C++ compiler builds it (tests/csrc/record_layout_print.cpp).  The sizes it depends on keep their definitions where
-// the kernels use them (mfbank.hip, stream_kernels.hpp) and arrive here as a RecordConsts.
+// the kernels use them (bank_ctx.hpp, stream_kernels.hpp) and arrive here as a RecordConsts.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

@@ -1,6 +1,6 @@
 // search_plan.hpp -- everything that DECIDES how the segment search runs, and nothing that launches: host arithmetic on a dozen
 // integers, no HIP call, no handle.  resolve_segments settles path, segment length and basis for a bank; plan_search takes every launch
-// and table decision of one search, once.  mfbank.hip fills a SearchInputs from a handle (search_inputs) and consumes the plan: the
+// and table decision of one search, once.  bank_search_api.hpp fills a SearchInputs from a handle (search_inputs) and consumes the plan: the
 // launches, mfb_get_search_info and the eager table build read the SAME answer, and mfb_debug_search_plan shows it to the tests.
 #pragma once
 #include <stdio.h>
@@ -197,7 +197,7 @@ inline void seg_slots(int N, const Segments &sg, int *full, int *total) {
     *total = (sg.Q + g.CT - 1) / g.CT;
 }
 
-// the matched-filter pass of nb blocks (SEG_STORE; demod_enqueue in mfbank.hip)
+// the matched-filter pass of nb blocks (SEG_STORE; demod_enqueue in bank_flight_api.hpp)
 inline SegPlan plan_store(const SearchInputs &in, const Segments &sg, int nb) {
     int nfull, ntotal;
     seg_slots(in.N, sg, &nfull, &ntotal);

@@ -585,3 +585,6 @@ __global__ void k_code_rate_block(const cf *P, float *out, int offset, int len, 
     }
 }
 
+__global__ void k_scale_c(cf *p, float s, int n) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) p[i] = p[i] * s;
+}

@@ -1,4 +1,4 @@
-"""Child of tests/test_gpu_pick_wait.py: picks taken from the handle's page-locked slot when they arrive (read_pick in mfbank.hip),
+"""Child of tests/test_gpu_pick_wait.py: picks taken from the handle's page-locked slot when they arrive (read_pick in csrc/bank_search_api.hpp),
 not after a synchronise.  Two 2^15-sample blocks stay resident on the device; block b's spectrum sits in the band that bin CARRIER[b]
 of the table shifts onto the filters' band, on a noise floor, so the two carriers lie 20 bins apart.  Every assertion is made here;
 the parent runs a mode under a timeout.

@@ -1,6 +1,6 @@
 """numpy model of the single-pass overlap-save search (test infrastructure).
 
-Restates, index for index, what ``k_seg`` in pycusdr_amd/csrc/mfbank.hip does with L-point
+Restates, index for index, what ``k_seg`` in pycusdr_amd/csrc/seg_kernels.hpp does with L-point
 segments, so that the algebra (support window, rotated taps, validity ranges, output offset,
 power-of-two scaling) is checked on the CPU against the reference formulation
 ``IFFT_N(X[(k+s) mod N] * H_m[k])`` (reference cuda_kernels.cu:339-373 + demodulator_base.py:578-591)

@@ -174,7 +174,7 @@ def test_wave_local_2048_point_transform_is_an_inverse_dft():
         assert len(slots) == len({l >> 1 for l in grp})
 
 
-# ---- the fused-twiddle transforms of round 6 (fft_core.hpp: bf_ct, dit_fused, fft256_fused, fft_w32_fused; mfbank.hip: ct_pair) ----
+# ---- the fused-twiddle transforms of round 6 (fft_core.hpp: bf_ct, dit_fused, fft256_fused, fft_w32_fused; bank_lifecycle_api.hpp: ct_pair) ----
 # Register-level model with fp32 rounding after every packed operation: radix-2 decimation in time, in place, every twiddled
 # butterfly in tangent form -- b' = b + t (i b), a +- c b' -- the same slots, stage twiddles, table order and exchange addresses.
 def _r32(x):
@@ -182,7 +182,7 @@ def _r32(x):
 
 
 def _ct_pair(u, L):
-    """(cos, tan) of 2 pi u / L as the host builds them (mfbank.hip ct_pair): fp32 values; exactly pi/2 becomes (2^-40, 2^40)."""
+    """(cos, tan) of 2 pi u / L as the host builds them (bank_lifecycle_api.hpp, ct_pair): fp32 values; exactly pi/2 becomes (2^-40, 2^40)."""
     ang = 2.0 * np.pi * u / L
     c, s = np.cos(ang), np.sin(ang)
     if abs(c) < 1e-9:

@@ -2,7 +2,7 @@
 plain exact reference (tests/combiner_model.py, held to the definition and to numpy by test_combiner_model.py).  Every
 comparison is ``==`` / ``array_equal``; there is no tolerance in this file.
 
-What decides the shapes (cmb_enqueue_xcorr, mfbank.hip): N = 2^ceil(log2 n) lags, NW = max(N / 32, 1) slave words,
+What decides the shapes (cmb_enqueue_xcorr, combine_api.hpp): N = 2^ceil(log2 n) lags, NW = max(N / 32, 1) slave words,
 gx = ceil(NW / 256) workgroups along the lags, tiles = ceil(ceil(min(m, n) / 32) / 64) tiles of 64 master words,
 gy = min(1024 / gx, tiles): a workgroup of k_cmb_xcorr walks more than one tile only when gx * tiles > 1024, that is from
 N = 2^18 with more than 65 536 master bits on.  The peak stages take 4096 lags per workgroup (16 per thread, lag

@@ -1,8 +1,9 @@
 """Lifetime of what a handle owns (csrc/hip_owned.hpp): a handle whose buffers have all been regrown computes what a fresh handle
 computes, and create / use / close cycles give their memory back.
 
-A. Every grow-only reserve of mfbank.hip is driven through its regrow branch -- the old buffer exists and is too small -- and the
-   result is compared with a handle that was sized for the work from the start.  Which call reaches which branch:
+A. Every grow-only reserve of the bank (csrc/bank_ctx.hpp and the bank's parts beside it) and the sync finder's are driven through
+   their regrow branch -- the old buffer exists and is too small -- and the result is compared with a handle that was sized for the
+   work from the start.  Which call reaches which branch:
      batch_reserve (work buffers, d_Z, the records, d_Z2), clip_reserve (flight buffers, workspace), staging_reserve:
          a batch of 1, of 3, of 8.  The library sizes these for the WINDOWS' capacity, not for the batch (one set of buffers serves
          batches of 1 ... B), so batches of growing size on the same windows regrow nothing: the windows are remade for 1, 3 and 8
@@ -19,7 +20,7 @@ B. A cycle that creates, uses and closes a handle with everything that allocates
    must return device memory to within the 32 MiB that test_gpu_configs.test_failed_create_frees_everything allows.  At N = 2^18 one
    leaked N-sized complex64 buffer per cycle is 2 MiB, 40 MiB after 20 cycles.  Buffers below about 1.6 MiB (32 MiB / 20) are not
    seen by this reading, nor is page-locked memory: those are covered by construction (no hipFree / hipHostFree / hipEventDestroy /
-   hipStreamDestroy is written out in mfbank.hip any more) and by tools/leak_probe.py."""
+   hipStreamDestroy is written out in mfbank.hip or its parts any more) and by tools/leak_probe.py."""
 import numpy as np
 import pytest
 

@@ -1,4 +1,4 @@
-"""The host takes a pick from the handle's page-locked slot when it arrives (read_pick in mfbank.hip; k_pick stores {two floats, the
+"""The host takes a pick from the handle's page-locked slot when it arrives (read_pick in csrc/bank_search_api.hpp; k_pick stores {two floats, the
 pick's number, a check word} in one 16-byte store) and no longer waits for the stream to drain.  What could go wrong is a pick that is
 not this call's: the slot still holding the pick before.  So two resident 2^15-sample blocks whose carriers lie 20 bins apart alternate
 through 300 find_carrier calls on one handle, and through 300 each on two handles in two threads; pick and pick_column on a device

@@ -54,7 +54,8 @@ def test_gap_fill_is_shared():
 def test_peak_clip_entry_points_declared_cited_exported():
     from pycusdr_amd import _lib
     hdr = open(os.path.join(ROOT, 'include', 'mfbank.h')).read()
-    src = open(os.path.join(ROOT, 'pycusdr_amd', 'csrc', 'mfbank.hip')).read()
+    import tu_source
+    src = ''.join(tu_source.host_files().values())          # (the translation unit's host files: mfbank.hip and its parts)
     assert os.path.exists(os.path.join(ROOT, 'pycusdr_amd', 'csrc', 'clip_kernels.hpp'))
     for name in ENTRY:
         m = re.search(r'((?:/\*(?:(?!\*/).)*\*/\s*)+)int ' + name + r'\(', hdr, re.S)

@@ -10,7 +10,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, 'tests', 'csrc', 'record_layout_print.cpp')
 
-# the sizes the layout depends on, as mfbank.hip / stream_kernels.hpp define them (the program takes them on its command line)
+# the sizes the layout depends on, as bank_ctx.hpp / stream_kernels.hpp define them (the program takes them on its command line)
 HEAD, POST_MAX, END_MAX, MAX_TMPL, MAX_HITS, EDGE_CANDS = 256, 512, 32, 2, 64, 4
 EDGE_BYTES = 4 * (1 + 1 + 2 + 2 * 8 + 2 * 8)        # StreamEdge: a_rel, valid, n[2], idx[2][8], score[2][8], int32 each
 CONSTS = [HEAD, POST_MAX, END_MAX, MAX_TMPL, MAX_HITS, EDGE_CANDS, EDGE_BYTES]

@@ -94,7 +94,8 @@ def _src(name):
 
 
 def test_each_decision_is_written_once():
-    hip, plan = _src('mfbank.hip'), _src('search_plan.hpp')
+    import tu_source
+    hip, plan = tu_source.bank_text(), _src('search_plan.hpp')      # (mfbank.hip and the bank's parts: what used to be mfbank.hip)
     both = hip + plan
     assert both.count('(size_t)in.Dtot * MU * 16384 <= ((size_t)256 << 20)') == 1 and '* 16384 <=' not in hip       # the filter-side predicate
     assert both.count('span || in.uniform_mult') == 1 and hip.count('std::all_of(c->h_mult') == 1              # the presum test
